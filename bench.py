@@ -8,15 +8,20 @@ A "step" is one EM iteration (`Model.make_iteration`, src/TrigenicInteractionPre
 scaling); the final log-likelihoods are gathered over RCCL at the end (:1262-1279 analogue).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--K 10] [--samples 1]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events on the launch stream:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the
+headline (`value`, `ms_per_step`, the final log-likelihood, the plan); `--dump-outputs DIR` also
+writes the parameters and log-likelihoods the timed iterations left as DIR/<name>.npy.
+Everything below needs `--full`.  `roofline` is measured live with HIP events on the launch stream:
 the dominant kernel (the E-step) is launched back to back right after the timed region and
 its average duration divides the algorithmic FLOPs of one launch; `kernel_us` also gives each
 kernel's in-loop time from event pairs around the warmup iterations' launches (those include the
 dependent-launch boundary; the timed steps run without events).  `cpu_baseline` times the
 pure-Python CPU restatement of the reference path (oracle/, test infrastructure) on a bounded
-sample of the same workload, on this host, rank 0 at N=1 only.
+sample of the same workload, on this host, rank 0 at N=1 only.  With a process group the
+gathered per-sample results are replayed as one batch and compared bit for bit (`replay_check`).
 """
 from __future__ import annotations
 
@@ -48,17 +53,25 @@ def parse():
     ap.add_argument("--P", type=int, default=1500)
     ap.add_argument("--E", type=int, default=90000, help="unique triples, train + test")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the CPU baseline, "
+                         "the per-kernel times (in-loop events, back-to-back launches), the roofline "
+                         "record and, with a process group, the one-batch replay check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they left (theta, pr and loglik of this "
+                         "rank's samples) as DIR/<name>.npy, float64, at most 64 MB in all (a "
+                         "fixed seeded sample of a larger array)")
     ap.add_argument("--hub", default="",
                     help="FRAC,SHARE: hub-heavy synthetic fold (SHARE of the triples take one gene "
                          "from the first FRAC of the genes; data.FoldSpec.hub_*), e.g. 0.02,0.3")
-    ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0, help="with --full")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--backend", default="nccl",
                     help="collective backend: nccl (= RCCL over xGMI); gloo only to rehearse "
                          "several ranks sharing one GPU")
-    ap.add_argument("--no-events", action="store_true", help="do not time kernels (overhead probe)")
+    ap.add_argument("--no-events", action="store_true", help="with --full: do not time kernels (overhead probe)")
     ap.add_argument("--roofline-launches", type=int, default=1000,
-                    help="back-to-back E-step launches timed for the roofline")
+                    help="with --full: back-to-back E-step launches timed for the roofline")
     ap.add_argument("--shard", choices=("samples", "links"), default="samples",
                     help="samples: independent restarts per rank (weak scaling, the default); "
                          "links: ONE batch of samples whose train links are split over the ranks, "
@@ -336,6 +349,38 @@ def cpu_baseline(train, test, K, seed, seconds, cores):
     return rec
 
 
+DUMP_BUDGET = 64 * 2 ** 20     # bytes of --dump-outputs, all files of one rank together
+
+
+def _bounded(a, budget):
+    """`a` as a flat float64 array of at most `budget` bytes: all of it, or the elements at a
+    fixed (seeded, sorted) sample of flat indices, the same for every run of one shape."""
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    n = budget // 8
+    if a.size <= n:
+        return a, None
+    idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+    return a[idx], idx
+
+
+def dump_outputs(out_dir, runner, L, world, rank):
+    """What the timed iterations left, as a caller receives it (EMEngine.download() and
+    loglik()): theta [B][P][K], pr [B][K][K][K][R] and the train log-likelihoods [B], float64,
+    as <name>.npy (rank r > 0 of several: <name>.rank<r>.npy).  An array over its share of
+    DUMP_BUDGET is written as a flat sample (_bounded: the indices follow from the shape alone)."""
+    os.makedirs(out_dir, exist_ok=True)
+    theta, pr = runner.download()
+    suffix = ".rank%d" % rank if world > 1 and rank else ""
+    small = 2 ** 20
+    for name, a, budget in (("theta", theta, (DUMP_BUDGET - 2 * small) // 2),
+                            ("pr", pr, (DUMP_BUDGET - 2 * small) // 2),
+                            ("loglik", np.asarray(L), small)):
+        full_shape = np.shape(a)
+        flat, idx = _bounded(a, budget)
+        np.save(os.path.join(out_dir, name + suffix + ".npy"),
+                flat.reshape(full_shape) if idx is None else flat)
+
+
 def launch_check(args, world, rank):
     """The N-rank path without GPU work: every rank takes its block of sample ids, and the
     end-of-run gather (RCCL all_gather under nccl) collects them on every rank."""
@@ -383,7 +428,7 @@ def main():
             return 2
     train, test = make_fold(args.P, args.E, rank, args.hub, args.test_frac)
     cpu_rec = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cores = args.cpu_cores or min(len(os.sched_getaffinity(0)), 16)
         cpu_rec = cpu_baseline(train, test, args.K, args.seed, args.cpu_baseline_seconds, cores)
 
@@ -449,15 +494,18 @@ def main():
     # per-kernel in-loop times come from event pairs in the (untimed) warmup iterations: an
     # event record between two dependent launches costs the loop ~1-2 us, so the timed region
     # runs without them
-    # (the first warmup iteration runs without them: it includes the code objects' lazy load)
+    # (the first warmup iteration runs without them: it includes the code objects' lazy load;
+    # a plain run takes no per-kernel times at all)
     first_w = min(1, args.warmup)
     runner.iterate(first_w)
-    eng.timing(0 if args.no_events else args.event_stride)
+    if args.full:
+        eng.timing(0 if args.no_events else args.event_stride)
     runner.iterate(args.warmup - first_w)
     torch.cuda.synchronize(dev)
-    labels = eng.kernels()
-    in_loop = {k: eng.timing_result(k) for k in labels}
-    eng.timing(False)
+    if args.full:
+        labels = eng.kernels()
+        in_loop = {k: eng.timing_result(k) for k in labels}
+        eng.timing(False)
     if dist_on:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -467,11 +515,15 @@ def main():
     t1 = time.perf_counter()
     if dist_on:
         dist.barrier()
-    # each kernel of the iteration alone, back to back on the launch stream (per-launch duration
-    # for the roofline; the in-loop events above also time the dependent-launch boundary)
-    b2b = {k: eng.time_kernel(k, args.roofline_launches) for k in labels}
+    if args.full:
+        # each kernel of the iteration alone, back to back on the launch stream (per-launch
+        # duration for the roofline; the in-loop events above also time the dependent-launch
+        # boundary)
+        b2b = {k: eng.time_kernel(k, args.roofline_launches) for k in labels}
     elapsed = t1 - t0
     L = runner.loglik(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner, L, world, rank)
     rows = result_rows(sample_ids, L)
     if dist_on:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll)
@@ -481,7 +533,7 @@ def main():
             rows = gather_rows(rows, B * world, device=coll)
     n_gathered = int(rows.shape[0])
     scale_check = None
-    if rank == 0 and dist_on and not links_mode:
+    if args.full and rank == 0 and dist_on and not links_mode:
         # every sample replayed as ONE batch on this GPU: within one kernel family a sample's bits
         # do not depend on its batch or rank, so the gathered values must equal the replay bit for bit
         def factory(nb):
@@ -495,7 +547,6 @@ def main():
         iters_total = args.steps * B * (1 if links_mode else world)
         value = iters_total / elapsed
         iter_s = elapsed / args.steps
-        roofline = roofline_record(K, host.P, 2, B, E_obs, plan, iter_s, b2b, build_id)
         wl = ("fold0 stand-in" if (args.P, args.E) == (1500, 90000) else
               "synthetic P=%d, E=%d" % (host.P, args.E))
         if args.hub:
@@ -528,22 +579,27 @@ def main():
                         "rows": rows.tolist() if n_gathered <= 64 else None,
                         "replay_check": scale_check},
             "build_id": build_id,
-            "roofline": roofline,
-            # both bases of the roofline fraction, whichever `roofline.frac` reports
-            "frac_credited": roofline["frac_credited"],
-            "frac_executed": roofline["frac_executed"],
+            "full": args.full,
             "kernel_family": {0: "large-K", 1: "small-K two-pass", 2: "SK_U", 3: "SK_Y"}[plan["small_k"]],
             "iteration": {"us": iter_s * 1e6},
+            "plan": plan,
+        }
+        if args.full:
+            roofline = roofline_record(K, host.P, 2, B, E_obs, plan, iter_s, b2b, build_id)
+            line["roofline"] = roofline
+            # both bases of the roofline fraction, whichever `roofline.frac` reports
+            line["frac_credited"] = roofline["frac_credited"]
+            line["frac_executed"] = roofline["frac_executed"]
             # the kernels the iteration launches (EMEngine.kernels(): the fused small-K E-step
             # has no pass B, the large-K iteration runs pass A, the gene kernel and the update)
-            "kernel_us": {k: {"back_to_back": b2b[k] * 1e3,
-                              "in_loop": in_loop[k][0] * 1e3 / max(in_loop[k][1], 1)}
-                          for k in labels},
-            "plan": plan,
-            "cpu_baseline": cpu_rec,
-        }
+            line["kernel_us"] = {k: {"back_to_back": b2b[k] * 1e3,
+                                     "in_loop": in_loop[k][0] * 1e3 / max(in_loop[k][1], 1)}
+                                 for k in labels}
+            line["cpu_baseline"] = cpu_rec
         if cpu_rec is not None:
             line["vs_cpu_baseline"] = value / cpu_rec["value"]
+        if args.dump_outputs:
+            line["dump_outputs"] = args.dump_outputs
         print(json.dumps(line), flush=True)
     rc = 0
     if scale_check is not None and not scale_check["bitwise_equal"]:

@@ -40,3 +40,33 @@ def test_roofline_headline_basis():
     assert fast["frac_basis"].startswith("executed") and fast["frac"] == fast["executed"]["frac"]
     assert fast["credited"]["frac"] > 1.0
     assert fast["dominant_kernel"]["kernel"].startswith("pass_kernel<20")
+
+
+class _Runner:
+    """Stands in for EMEngine.download(): a small theta and a pr over the dump's per-array share."""
+    def __init__(self, n_pr):
+        import numpy as np
+        self.theta = np.arange(2 * 5 * 3, dtype=np.float64).reshape(2, 5, 3)
+        self.pr = np.arange(n_pr, dtype=np.float64)
+
+    def download(self):
+        return self.theta, self.pr
+
+
+def test_dump_outputs_whole_arrays_and_bounded_sample(tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 2 * 2 ** 20 + 2 * 8 * 1000)   # 1,000 values per array
+    r = _Runner(5000)
+    L = np.array([-1.5, -2.5])
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), r, L, 1, 0)
+    got = {f: np.load(str(tmp_path / "a" / f)) for f in sorted(os.listdir(str(tmp_path / "a")))}
+    assert sorted(got) == ["loglik.npy", "pr.npy", "theta.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    np.testing.assert_array_equal(got["theta.npy"], r.theta)          # under the share: whole, shaped
+    np.testing.assert_array_equal(got["loglik.npy"], L)
+    pr = got["pr.npy"]                                                # over it: a fixed sorted sample
+    assert pr.shape == (1000,) and np.all(np.diff(pr) > 0) and set(pr) <= set(r.pr)
+    for f, a in got.items():                                          # the same from run to run
+        np.testing.assert_array_equal(np.load(str(tmp_path / "b" / f)), a)
+    assert sum(a.nbytes for a in got.values()) <= 64 * 2 ** 20

@@ -143,9 +143,9 @@ def _bench(*args):
 
 
 def test_bench_process_group_one_gpu():
-    """bench.py --gpus 1 --process-group: the nccl init with device_id (bench.py's N-rank line),
+    """bench.py --full --gpus 1 --process-group: the nccl init with device_id (bench.py's N-rank line),
     the RCCL gather of the rows and the replay check on the one GPU."""
-    rec = _bench("--process-group", "--samples", "2", "--steps", "5", "--warmup", "2",
+    rec = _bench("--full", "--process-group", "--samples", "2", "--steps", "5", "--warmup", "2",
                  "--no-cpu-baseline", "--roofline-launches", "5")
     assert rec["process_group"] == "nccl" and rec["world_size"] == 1
     assert rec["gathered_samples"] == 2
@@ -153,8 +153,8 @@ def test_bench_process_group_one_gpu():
 
 
 def test_bench_process_group_link_shard_one_gpu():
-    """bench.py --gpus 1 --process-group --shard links: one RCCL all-reduce per iteration."""
-    rec = _bench("--process-group", "--shard", "links", "--K", "20", "--steps", "3", "--warmup", "1",
+    """bench.py --full --gpus 1 --process-group --shard links: one RCCL all-reduce per iteration."""
+    rec = _bench("--full", "--process-group", "--shard", "links", "--K", "20", "--steps", "3", "--warmup", "1",
                  "--no-cpu-baseline", "--roofline-launches", "3")
     assert rec["process_group"] == "nccl" and rec["scaling"] == "strong"
     assert np.isfinite(rec["final_loglik"])

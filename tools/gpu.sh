@@ -8,7 +8,7 @@
 # stops at the first failure (no step is retried).  Steps:
 #   tests [pytest args]            the GPU suite (pytest -m gpu), e.g. `tests -k pool`
 #   smoke                          __graft_entry__.smoke()
-#   bench NAME [bench.py args]     one bench line -> NAME.json (prints a summary)
+#   bench NAME [bench.py args]     one `bench.py --full` line -> NAME.json (prints a summary)
 #   configs                        the headline (2,000 and 20 steps) and the BASELINE config lines
 #   prof NAME TRACE_STEPS PMC_STEPS [bench.py args]
 #                                  rocprofv3 kernel-trace stats, the PMC passes (one counter
@@ -41,7 +41,7 @@ PY
 
 bench() {
   local name=$1; shift
-  timeout -k 10 500 python -u bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || { echo "bench $name failed"; tail -20 "$OUT/$name.err"; return 1; }
+  timeout -k 10 500 python -u bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || { echo "bench $name failed"; tail -20 "$OUT/$name.err"; return 1; }
   summ "$OUT/$name.json"
 }
 
@@ -66,13 +66,13 @@ step() {
     local name=$1 ts=$2 ps=$3; shift 3
     local P=$OUT/$name
     mkdir -p "$P"
-    ( cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$P/trace" -o run --output-format csv -- python3 "$R/bench.py" --steps "$ts" --warmup 5 --no-cpu-baseline --no-events "$@" > "$P/trace.json" 2> "$P/trace.err" ) || { echo "trace failed"; tail -20 "$P/trace.err"; return 1; }
+    ( cd "$TMPDIR" && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$P/trace" -o run --output-format csv -- python3 "$R/bench.py" --full --steps "$ts" --warmup 5 --no-cpu-baseline --no-events "$@" > "$P/trace.json" 2> "$P/trace.err" ) || { echo "trace failed"; tail -20 "$P/trace.err"; return 1; }
     local i=0
     for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA SQ_INSTS_LDS" \
                "SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU GRBM_GUI_ACTIVE FETCH_SIZE" \
                "WRITE_SIZE TCC_HIT_sum TCC_MISS_sum"; do
       i=$((i+1))
-      ( cd /tmp && timeout -s KILL 240 rocprofv3 --pmc $grp --kernel-trace -d "$P/p$i" -o run --output-format csv -- python3 "$R/bench.py" --steps "$ps" --warmup 2 --no-cpu-baseline --no-events --roofline-launches 3 "$@" > "$P/p$i.log" 2>&1 ) || { echo "pmc pass $i failed"; tail -5 "$P/p$i.log"; return 1; }
+      ( cd "$TMPDIR" && timeout -s KILL 240 rocprofv3 --pmc $grp --kernel-trace -d "$P/p$i" -o run --output-format csv -- python3 "$R/bench.py" --full --steps "$ps" --warmup 2 --no-cpu-baseline --no-events --roofline-launches 3 "$@" > "$P/p$i.log" 2>&1 ) || { echo "pmc pass $i failed"; tail -5 "$P/p$i.log"; return 1; }
     done
     python3 tools/pmc_summary.py "$P" > "$P/pmc_summary.txt" 2>&1
     read -r K E_OBS B < <(python3 -c "import json; c=json.load(open('$P/trace.json'))['config']; print(c['K'], c['E_obs'], c['samples_per_gpu'])")
@@ -95,13 +95,13 @@ PY
       if [ "${v#*+env:}" != "$v" ]; then lib="${v%%+env:*}"; envs=$(echo "${v#*+env:}" | tr ',' ' ');
       elif [ "${v#env:}" != "$v" ]; then lib="-"; envs=$(echo "${v#env:}" | tr ',' ' '); fi
       if [ "$lib" != "-" ]; then export MMSBM_LIB=$R/$lib; fi
-      timeout -k 10 500 env $envs python -u bench.py --no-cpu-baseline $args > "$OUT/${name}_$i.json" 2> "$OUT/${name}_$i.err" || { echo "ab $name variant $v failed"; tail -10 "$OUT/${name}_$i.err"; return 1; }
+      timeout -k 10 500 env $envs python -u bench.py --full --no-cpu-baseline $args > "$OUT/${name}_$i.json" 2> "$OUT/${name}_$i.err" || { echo "ab $name variant $v failed"; tail -10 "$OUT/${name}_$i.err"; return 1; }
       echo -n "[$v] "; summ "$OUT/${name}_$i.json"
     done
     unset MMSBM_LIB ;;
   stamp)
     local name=$1 lib=$2; shift 2
-    MMSBM_STAMP=1 MMSBM_STAMP_DUMP="$OUT/$name.bin" MMSBM_LIB="$R/$lib" timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --roofline-launches 5 "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || { echo "stamp $name failed"; tail -5 "$OUT/$name.err"; return 1; }
+    MMSBM_STAMP=1 MMSBM_STAMP_DUMP="$OUT/$name.bin" MMSBM_LIB="$R/$lib" timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --roofline-launches 5 "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || { echo "stamp $name failed"; tail -5 "$OUT/$name.err"; return 1; }
     python3 tools/stamp_analyze.py "$OUT/$name.bin" "$OUT/$name.json" > "$OUT/$name.txt" && rm -f "$OUT/$name.bin"
     head -60 "$OUT/$name.txt" ;;
   py)
