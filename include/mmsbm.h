@@ -127,6 +127,32 @@ int mmsbm_loglik(mmsbm_ctx *ctx, int32_t which, const double *theta, const doubl
 int mmsbm_predict(mmsbm_ctx *ctx, const int32_t *ids, int64_t n, const double *theta,
                   const double *pr, double *out, void *stream);
 
+/* Genome-wide scan: the exact top N of Model.do_prediction (:530-547, no eps) over every triple of
+ * DISTINCT genes, each taken once in the reference's key order (:349-358: ids sorted as decimal
+ * strings).  order[P] (device) = the gene ids sorted by str(id); a triple is three positions
+ * a < b < c of it, its score do_prediction(order[a], order[b], order[c]) and its packed key
+ * (a P + b) P + c.  known (device; NULL = none) = n_known packed keys, sorted ascending, of triples
+ * to skip (the measured ones); keys of no triple are ignored.  sample >= 0 scans that slot of the
+ * active prefix (mmsbm_set_active); -1 scans the ensemble: the scores of slots [0, n_active) added
+ * in slot order, then divided by n_active (the per-triplet mean of testResultsReducer.py:153-184).
+ * Result (device): the first *out_count rows of out_scores f64[N] and out_ids int32[N][3] (gene
+ * ids in key order) hold the best triples under the total order (score descending; equal scores:
+ * smaller packed key first); *out_count < N when fewer are eligible (P < 3: 0); the tail is
+ * NaN / -1.  That list is unique, so it does not depend on the grid, the device or the batch the
+ * sample sits in.  1 <= N <= mmsbm_scan_max_n() (4096); above it MMSBM_ERR_UNSUPPORTED, as for an
+ * ensemble whose W tile exceeds the LDS (n_active (K + 5) > 512: scan the slots one by one).
+ * ws: mmsbm_scan_workspace_bytes(ctx, N) bytes of device scratch, 16-byte aligned, the caller's
+ * (independent of mmsbm_set_workspace).  theta and pr are only read; all launches go to `stream`
+ * and nothing synchronises.  Needs R >= 2.  The caller guarantees that order is a permutation of
+ * [0, P) (ids outside it score as zero rows).  Replaces nothing in the reference, which predicts
+ * listed triplets only (calculate_test_set_results, :557-569). */
+int mmsbm_scan_max_n(void);
+int mmsbm_scan_workspace_bytes(const mmsbm_ctx *ctx, int32_t N, int64_t *bytes);
+int mmsbm_scan_topn(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known, int64_t n_known,
+                    const double *theta, const double *pr, int32_t sample, int32_t N, void *ws,
+                    int64_t ws_bytes, double *out_scores, int32_t *out_ids, int64_t *out_count,
+                    void *stream);
+
 /* Link-sharded iteration (single sample over N ranks): each rank's context
  * holds 1/N of the train links (mmsbm_set_links) and the GLOBAL degree (mmsbm_set_degree).
  * Step 1, the accumulation half of make_iteration (:986-1012) over this rank's links:

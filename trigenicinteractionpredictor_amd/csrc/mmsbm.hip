@@ -1824,6 +1824,19 @@ int mmsbm_detail_fail(int code, const char* msg) {
   return code;
 }
 
+// scan.hip (same library): the context's device, shape, active prefix and compute-unit count
+int mmsbm_detail_scan_shape(const mmsbm_ctx* c, int* device, int* K, int* R, int* B, int* P, int* nact,
+                            int* ncu) {
+  *device = c->device;
+  *K = c->K;
+  *R = c->R;
+  *B = c->B;
+  *P = c->P;
+  *nact = nb_of(c);
+  *ncu = c->ncu;
+  return MMSBM_OK;
+}
+
 extern "C" {
 
 int mmsbm_version(void) { return 2; }

@@ -1,0 +1,671 @@
+// scan.hip — MI355X (gfx950) kernels + C ABI (include/mmsbm.h, mmsbm_scan_*) of the genome-wide
+// scan: the exact top N of do_prediction (:530-547) over every triple of distinct genes.
+//
+// A triple is three rank positions a < b < c of the genes sorted by str(id) (the reference's key
+// order, :349-358); its score is P(r = 1) = sum th_i[x] th_j[y] th_k[z] p_1[x][y][z] with
+// i, j, k = order[a], order[b], order[c].  With Th' = theta in rank order the scores factor
+// through the first gene (the engine's pivot factorisation, one level up):
+//   T_a[y][z] = sum_x Th'[a][x] p_1[x][y][z]            K^3 per gene         (scan_prep_kernel)
+//   W_a[b][z] = sum_y Th'[b][y] T_a[y][z]               K^2 per (a, b)       (scan_kernel, LDS)
+//   S_a[b][c] = sum_z W_a[b][z] Th'[c][z]               K per triple         (v_mfma_f64_16x16x4)
+// so the score phase is a batched FP64 GEMM of inner size K: 2 K C(P,3) FLOP per sample.
+//
+// scan_kernel: a work item is (a, a block of 16 WB rows b); the workgroup's 4 waves hold WB b-tiles
+// x 4 / WB interleaved c-tiles, W_a of the item's rows in LDS (every sample of the ensemble), the
+// Th' operand k-major from global (the same words for the waves that share a c-tile).  For the
+// ensemble each sample's tile is accumulated from zero and the tiles are added in slot order, then
+// divided by the sample count.  Items go to workgroups round-robin (no workgroup waits on another).
+//
+// Selection: every workgroup keeps a candidate buffer (LDS when it fits, else workspace) of a
+// power-of-two capacity >= 2N.  A wave appends, by ballot compaction and one LDS compare-exchange
+// that reserves the whole tile's entries, every eligible score not behind the workgroup's
+// threshold; the exclusion test (binary search in the sorted known keys) runs only for those.
+// When a reservation does not fit the workgroup sorts the buffer (bitonic, total order: score
+// descending, packed key ascending), keeps the best N, and raises its threshold to the N-th.  The
+// N-th score is also published with an agent-scope atomic max (positive doubles order as integers)
+// and read once per item: a workgroup's N-th best is a lower bound of the global N-th, so pruning
+// scores strictly below it never drops a member of the result, seen or not.  For P >= 200 a seeding
+// pass runs first: the same scan and merge over every 61st item, whose exact N-th score (a subset's
+// N-th best is such a lower bound too) is published before the full pass starts, so the full pass
+// appends about 61 N candidates in all instead of filling every buffer from nothing.  At the end each
+// workgroup writes its sorted best N; scan_merge_kernel (own launches, fan-in 32) merges the lists
+// with the same buffer and order.  The exact top N under a total order is unique: the result does
+// not depend on the grid, the arrival order or the batch.  Scores are never combined by atomics
+// and every sum has a fixed order.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+
+#include "mmsbm.h"
+
+int mmsbm_detail_fail(int code, const char* msg);  // mmsbm.hip: the library's error channel
+int mmsbm_detail_scan_shape(const mmsbm_ctx* c, int* device, int* K, int* R, int* B, int* P, int* nact,
+                            int* ncu);
+
+namespace {
+
+constexpr int NT = 256;          // threads per workgroup of every scan kernel
+constexpr int SCAN_MAX_N = 4096; // documented cap of N (include/mmsbm.h)
+constexpr int FAN = 32;          // lists merged by one workgroup of scan_merge_kernel
+constexpr int SEED_STRIDE = 61;  // the seeding pass scans every 61st item (prime: spreads over a and b)
+constexpr int SEED_MIN_P = 200;  // below it one pass: the seeding launches would cost more than they save
+constexpr int LDS_MAX = 144 * 1024;
+constexpr int W_LDS_MAX = 64 * 1024;
+
+int fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  return mmsbm_detail_fail(code, buf);
+}
+
+#define HIP_TRY(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess) return fail(MMSBM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) (void)hipSetDevice(dev);
+  }
+  ~DeviceGuard() {
+    int cur = -1;
+    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+};
+
+typedef double d4v __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------------------------------
+// Selection state of one workgroup (LDS) and its candidate buffer
+// ------------------------------------------------------------------------------------------
+struct Sel {
+  int count;        // entries in the buffer
+  int overflow;     // a wave's reservation did not fit: sort and keep the best N
+  double thr_s;     // the workgroup's N-th best (score, key); (-inf, max) until it has N
+  long long thr_k;
+  double gthr;      // the published bound as read at the item's start (-inf: none)
+  long long klo, khi;  // the item's first gene a: its known keys are known[klo, khi)
+  double pad[2];
+};
+static_assert(sizeof(Sel) == 64, "Sel is the first 64 bytes of the dynamic LDS");
+
+__device__ __forceinline__ double neg_inf() { return -__builtin_huge_val(); }
+
+// the total order: score descending, packed key ascending
+__device__ __forceinline__ bool before(double s1, long long k1, double s2, long long k2) {
+  return s1 > s2 || (s1 == s2 && k1 < k2);
+}
+
+__device__ __forceinline__ void sel_init(Sel* st) {
+  st->count = 0;
+  st->overflow = 0;
+  st->thr_s = neg_inf();
+  st->thr_k = LLONG_MAX;
+  st->gthr = neg_inf();
+  st->klo = st->khi = 0;
+}
+
+// Reserve n entries for this wave (lane 0, one LDS compare-exchange); -1: no room, nothing taken.
+__device__ __forceinline__ int wave_reserve(Sel* st, int n, int cap) {
+  int base = 0;
+  if ((threadIdx.x & 63) == 0) {
+    int old = __hip_atomic_load(&st->count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    for (;;) {
+      if (old + n > cap) {
+        old = -1;
+        __hip_atomic_store(&st->overflow, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        break;
+      }
+      if (__hip_atomic_compare_exchange_strong(&st->count, &old, old + n, __ATOMIC_RELAXED,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
+        break;
+    }
+    base = old;
+  }
+  return __shfl(base, 0, 64);
+}
+
+// Sort the buffer under the total order, keep the best N, raise the threshold.  Called by the
+// whole workgroup; begins and ends with a barrier.
+// Inlined, so that a buffer in LDS is sorted with LDS instructions (the address space is inferred).
+__device__ __forceinline__ void wg_keep_best(Sel* st, double* cs, long long* ck, int N,
+                                             unsigned long long* shared) {
+  __syncthreads();
+  const int cnt = st->count;
+  int sz = 1;
+  while (sz < cnt) sz <<= 1;
+  for (int i = cnt + threadIdx.x; i < sz; i += NT) {
+    cs[i] = neg_inf();
+    ck[i] = LLONG_MAX;
+  }
+  __syncthreads();
+  for (int k = 2; k <= sz; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < (sz >> 1); t += NT) {  // one compare-exchange per pair (i, i + j)
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), x = i | j;
+        const double si = cs[i], sx = cs[x];
+        const long long ki = ck[i], kx = ck[x];
+        const bool up = (i & k) == 0;
+        if (up ? before(sx, kx, si, ki) : before(si, ki, sx, kx)) {
+          cs[i] = sx;
+          ck[i] = kx;
+          cs[x] = si;
+          ck[x] = ki;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x == 0) {
+    const int keep = cnt < N ? cnt : N;
+    st->count = keep;
+    st->overflow = 0;
+    if (keep == N) {
+      const double t = cs[N - 1];
+      st->thr_s = t;
+      st->thr_k = ck[N - 1];
+      if (shared && t > 0.0)
+        __hip_atomic_fetch_max(shared, (unsigned long long)__double_as_longlong(t), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  __syncthreads();
+}
+
+// ------------------------------------------------------------------------------------------
+// Prep: Th' k-major and zero-padded (thT[s][KP][P16]) and T_a (T[s][P][K][KP]) of every gene.
+// grid (P16, samples).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(NT) void scan_prep_kernel(const int* __restrict__ order,
+                                                       const double* __restrict__ theta,
+                                                       const double* __restrict__ pr,
+                                                       double* __restrict__ thT, double* __restrict__ T,
+                                                       int K, int KP, int R, int P, int P16, int s0) {
+  __shared__ double th[MMSBM_MAX_K];
+  const int a = blockIdx.x, s = blockIdx.y;
+  const size_t K2 = (size_t)K * K, K3 = K2 * K;
+  int g = a < P ? order[a] : -1;
+  if (g < 0 || g >= P) g = -1;  // outside the table: a zero row (the binding checks the permutation)
+  const double* __restrict__ row = theta + ((size_t)(s0 + s) * P + (g < 0 ? 0 : g)) * K;
+  if (threadIdx.x < KP) {
+    const double v = (g >= 0 && (int)threadIdx.x < K) ? row[threadIdx.x] : 0.0;
+    if ((int)threadIdx.x < K) th[threadIdx.x] = v;
+    thT[((size_t)s * KP + threadIdx.x) * P16 + a] = v;
+  }
+  __syncthreads();
+  if (a >= P) return;
+  const double* __restrict__ p1 = pr + ((size_t)(s0 + s) * R + 1) * K3;
+  double* __restrict__ Ta = T + ((size_t)s * P + a) * K * KP;
+  for (int idx = threadIdx.x; idx < K * KP; idx += NT) {
+    const int y = idx / KP, z = idx % KP;
+    double v = 0.0;
+    if (z < K)
+      for (int x = 0; x < K; ++x) v = fma(th[x], p1[x * K2 + y * K + z], v);
+    Ta[idx] = v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Scan
+// ------------------------------------------------------------------------------------------
+struct ScanArgs {
+  const double* thT;          // [ns][KP][P16]
+  const double* T;            // [ns][P][K][KP]
+  const long long* known;     // sorted packed keys (null: none)
+  long long n_known;
+  double* cand_s;             // workspace candidate buffers [G][cap] (null: LDS)
+  long long* cand_k;
+  double* list_s;             // per-workgroup results [G][N]
+  long long* list_k;
+  int* list_n;                // [G]
+  unsigned long long* shared; // published threshold bits
+  int K, P, P16, ns, N, cap, WB, select;
+  int stride;                 // 1: every item; > 1: the seeding pass over every stride-th item
+};
+
+// first index in known[lo, hi) whose key is not below `key`
+__device__ __forceinline__ long long lower_bound(const long long* __restrict__ known, long long lo,
+                                                 long long hi, long long key) {
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (known[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ bool is_known(const long long* __restrict__ known, long long lo, long long hi,
+                                         long long key) {
+  const long long at = lower_bound(known, lo, hi, key);
+  return at < hi && known[at] == key;
+}
+
+template <int KS>
+__global__ __launch_bounds__(NT) void scan_kernel(ScanArgs A) {
+  constexpr int KP = 4 * KS, WS = KP + 2;  // W row stride: conflict-free A-operand reads
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  Sel* st = reinterpret_cast<Sel*>(smem);
+  double* W = reinterpret_cast<double*>(smem + sizeof(Sel));
+  const int RB = 16 * A.WB;                     // rows b of one item
+  const int P = A.P, P16 = A.P16, K = A.K, ns = A.ns;
+  double* lcs = W + (size_t)ns * RB * WS;  // the candidate buffer when it is in LDS
+  long long* lck = reinterpret_cast<long long*>(lcs + A.cap);
+  double* cs = lcs;
+  long long* ck = lck;
+  if (A.cand_s) {
+    cs = A.cand_s + (size_t)blockIdx.x * A.cap;
+    ck = A.cand_k + (size_t)blockIdx.x * A.cap;
+  }
+  // the sort, on the buffer where it is (a workgroup-uniform branch around the inlined copies)
+  auto keep_best = [&]() {
+    if (A.cand_s) wg_keep_best(st, cs, ck, A.N, A.shared);
+    else wg_keep_best(st, lcs, lck, A.N, A.shared);
+  };
+  if (threadIdx.x == 0) sel_init(st);
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = lane & 15, kk = lane >> 4;
+  const int wb = wave % A.WB, wc = wave / A.WB, CW = 4 / A.WB;
+  const int nct = P16 / 16;
+  const int nbq = (P + RB - 1) / RB;
+  const long long PP = (long long)P;
+  const double inv_div = (double)ns;
+
+  // items round-robin over the workgroups; the seeding pass takes every A.stride-th item only
+  for (long long q = (long long)blockIdx.x * A.stride; q < PP * nbq; q += (long long)gridDim.x * A.stride) {
+    const int a = (int)(q / nbq), bq = (int)(q % nbq);
+    if (a >= P - 2 || bq * RB + RB - 1 <= a || bq * RB >= P - 1) continue;  // no a < b < c here
+    __syncthreads();  // the previous item's W is read
+    if (threadIdx.x == 0) {
+      const unsigned long long g = __hip_atomic_load(A.shared, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      st->gthr = g ? __longlong_as_double((long long)g) : neg_inf();
+    }
+    if (threadIdx.x == 64 && A.n_known > 0) {  // the known keys whose first gene is a
+      st->klo = lower_bound(A.known, 0, A.n_known, (long long)a * PP * PP);
+      st->khi = lower_bound(A.known, st->klo, A.n_known, (long long)(a + 1) * PP * PP);
+    }
+    // W_a of the item's rows, every sample
+    for (int idx = threadIdx.x; idx < ns * RB * KP; idx += NT) {
+      const int z = idx % KP, r = (idx / KP) % RB, s = idx / (KP * RB);
+      const int rowb = bq * RB + r;
+      double v = 0.0;
+      if (rowb < P) {
+        const double* __restrict__ Ta = A.T + ((size_t)s * P + a) * K * KP + z;
+        const double* __restrict__ tb = A.thT + (size_t)s * KP * P16 + rowb;
+        for (int y = 0; y < K; ++y) v = fma(tb[(size_t)y * P16], Ta[y * KP], v);
+      }
+      W[((size_t)s * RB + r) * WS + z] = v;
+    }
+    __syncthreads();
+
+    const int btile = bq * A.WB + wb, b0 = btile * 16;
+    const bool wave_on = b0 < P - 1 && b0 + 15 > a;
+    double areg[KS];
+    if (wave_on && ns == 1) {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) areg[ks] = W[(size_t)(wb * 16 + m) * WS + 4 * ks + kk];
+    }
+    int ct = bq * A.WB + wc;
+    while (ct < btile) ct += CW;  // every c of those tiles is below every b
+    const long long klo = st->klo, khi = st->khi;
+    for (;;) {
+      // the thresholds change only when the workgroup sorts its buffer (behind a barrier)
+      const double thr_s = st->thr_s, gthr = st->gthr;
+      const long long thr_k = st->thr_k;
+      const double cut = fmax(thr_s, gthr);
+      if (wave_on) {
+        double bnext[KS];  // single sample: the next tile's Th' operand is in flight
+        if (ns == 1 && ct < nct) {
+          const double* __restrict__ tc = A.thT + (size_t)kk * P16 + ct * 16 + m;
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) bnext[ks] = tc[(size_t)(4 * ks) * P16];
+        }
+        for (; ct < nct; ct += CW) {
+          const int c0 = ct * 16;
+          d4v tot = {0.0, 0.0, 0.0, 0.0};
+          if (ns == 1) {
+            double bcur[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) bcur[ks] = bnext[ks];
+            if (ct + CW < nct) {
+              const double* __restrict__ tc = A.thT + (size_t)kk * P16 + c0 + 16 * CW + m;
+#pragma unroll
+              for (int ks = 0; ks < KS; ++ks) bnext[ks] = tc[(size_t)(4 * ks) * P16];
+            }
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+              tot = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ks], bcur[ks], tot, 0, 0, 0);
+          } else {
+            for (int s = 0; s < ns; ++s) {
+              const double* __restrict__ tc = A.thT + ((size_t)s * KP + kk) * P16 + c0 + m;
+              const double* wr = W + ((size_t)s * RB + wb * 16 + m) * WS + kk;
+              d4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+              for (int ks = 0; ks < KS; ++ks)
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[4 * ks], tc[(size_t)(4 * ks) * P16], acc, 0, 0, 0);
+              tot = s == 0 ? acc : tot + acc;  // samples added in slot order
+            }
+            tot = tot / inv_div;
+          }
+          if (!A.select) continue;
+          // lane holds S[b0 + kk + 4 i][c0 + m].  First the score alone against the larger of the
+          // two bounds (equal scores stay in: the key decides below); nearly every tile ends here
+          if (!__ballot(tot[0] >= cut || tot[1] >= cut || tot[2] >= cut || tot[3] >= cut)) continue;
+          const int c = c0 + m;
+          bool pass[4];
+          long long key[4];
+          unsigned long long mk[4];
+          int n = 0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int b = b0 + kk + 4 * i;
+            key[i] = ((long long)a * PP + b) * PP + c;
+            pass[i] = a < b && b < c && c < P && !(tot[i] < gthr) && before(tot[i], key[i], thr_s, thr_k);
+            if (pass[i] && khi > klo) pass[i] = !is_known(A.known, klo, khi, key[i]);
+            mk[i] = __ballot(pass[i]);
+            n += __popcll(mk[i]);
+          }
+          if (!n) continue;
+          int pos = wave_reserve(st, n, A.cap);
+          if (pos < 0) break;  // the tile is redone after the workgroup made room
+          const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (pass[i]) {
+              const int at = pos + __popcll(mk[i] & below);
+              cs[at] = tot[i];
+              ck[at] = key[i];
+            }
+            pos += __popcll(mk[i]);
+          }
+        }
+      }
+      __syncthreads();
+      if (!st->overflow) break;
+      keep_best();
+    }
+  }
+  keep_best();
+  const int cnt = st->count;
+  for (int i = threadIdx.x; i < cnt; i += NT) {
+    A.list_s[(size_t)blockIdx.x * A.N + i] = cs[i];
+    A.list_k[(size_t)blockIdx.x * A.N + i] = ck[i];
+  }
+  if (threadIdx.x == 0) A.list_n[blockIdx.x] = cnt;
+}
+
+// ------------------------------------------------------------------------------------------
+// Merge: workgroup w keeps the best N of lists [FAN w, FAN (w + 1)); the last level (one
+// workgroup) writes the result: scores, gene ids in key order, count, NaN / -1 tail.
+// ------------------------------------------------------------------------------------------
+struct MergeArgs {
+  const double* in_s;
+  const long long* in_k;
+  const int* in_n;
+  int n_in;
+  double* out_s;      // next level's lists (null on the last level)
+  long long* out_k;
+  int* out_n;
+  const int* order;   // last level
+  double* scores;
+  int* ids;
+  long long* count;
+  unsigned long long* shared;  // last level of the seeding pass: publish the N-th score, no output
+  int N, cap, P;
+};
+
+__global__ __launch_bounds__(NT) void scan_merge_kernel(MergeArgs A) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  Sel* st = reinterpret_cast<Sel*>(smem);
+  double* cs = reinterpret_cast<double*>(smem + sizeof(Sel));
+  long long* ck = reinterpret_cast<long long*>(cs + A.cap);
+  if (threadIdx.x == 0) sel_init(st);
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int l0 = blockIdx.x * FAN, l1 = min(l0 + FAN, A.n_in);
+  for (int l = l0; l < l1; ++l) {
+    const int cnt = min(A.in_n[l], A.N);
+    for (int base = 0; base < cnt; base += NT) {
+      const int i = base + threadIdx.x;
+      double s = 0.0;
+      long long k = 0;
+      bool pass = false;
+      if (i < cnt) {
+        s = A.in_s[(size_t)l * A.N + i];
+        k = A.in_k[(size_t)l * A.N + i];
+        pass = before(s, k, *(volatile double*)&st->thr_s, *(volatile long long*)&st->thr_k);
+      }
+      bool done = false;
+      for (;;) {
+        if (!done) {
+          const unsigned long long mk = __ballot(pass);
+          const int n = __popcll(mk);
+          int pos = n ? wave_reserve(st, n, A.cap) : 0;
+          if (pos >= 0) {
+            if (pass) {
+              pos += __popcll(mk & ((1ull << lane) - 1ull));
+              cs[pos] = s;
+              ck[pos] = k;
+            }
+            done = true;
+          }
+        }
+        __syncthreads();
+        const int full = st->overflow;
+        __syncthreads();  // everyone has read the flag before the next chunk can raise it
+        if (!full) break;
+        wg_keep_best(st, cs, ck, A.N, nullptr);
+      }
+    }
+  }
+  wg_keep_best(st, cs, ck, A.N, A.shared);  // seeding pass: publishes the subset's N-th score
+  if (A.shared) return;
+  const int cnt = st->count;
+  if (A.out_s) {
+    for (int i = threadIdx.x; i < cnt; i += NT) {
+      A.out_s[(size_t)blockIdx.x * A.N + i] = cs[i];
+      A.out_k[(size_t)blockIdx.x * A.N + i] = ck[i];
+    }
+    if (threadIdx.x == 0) A.out_n[blockIdx.x] = cnt;
+    return;
+  }
+  const long long PP = A.P;
+  for (int i = threadIdx.x; i < A.N; i += NT) {
+    if (i < cnt) {
+      const long long k = ck[i];
+      A.scores[i] = cs[i];
+      A.ids[3 * i] = A.order[k / (PP * PP)];
+      A.ids[3 * i + 1] = A.order[(k / PP) % PP];
+      A.ids[3 * i + 2] = A.order[k % PP];
+    } else {
+      A.scores[i] = __builtin_nan("");
+      A.ids[3 * i] = A.ids[3 * i + 1] = A.ids[3 * i + 2] = -1;
+    }
+  }
+  if (threadIdx.x == 0) *A.count = cnt;
+}
+
+// ------------------------------------------------------------------------------------------
+// Host side
+// ------------------------------------------------------------------------------------------
+struct ScanPlan {
+  int device, K, KP, R, B, P, P16, nact, ncu;
+  int N, cap, G, G2;
+  size_t off_thT, off_T, off_cs, off_ck, off_ls[2], off_lk[2], off_ln[2], total;
+};
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Everything that sizes the workspace follows the context's shape and N only (not the sample
+// argument), so one workspace serves every call of that shape.
+int make_plan(const mmsbm_ctx* c, int N, ScanPlan* p) {
+  mmsbm_detail_scan_shape(c, &p->device, &p->K, &p->R, &p->B, &p->P, &p->nact, &p->ncu);
+  if (p->K < 1 || p->K > MMSBM_MAX_K)
+    return fail(MMSBM_ERR_UNSUPPORTED, "K=%d outside [1, %d]: call mmsbm_set_shape", p->K, MMSBM_MAX_K);
+  if (p->R < 2 || p->B < 1 || p->P < 0) return fail(MMSBM_ERR_INVALID, "scan needs R >= 2, B >= 1 (mmsbm_set_shape)");
+  if (N < 1) return fail(MMSBM_ERR_INVALID, "N=%d < 1", N);
+  if (N > SCAN_MAX_N) return fail(MMSBM_ERR_UNSUPPORTED, "N=%d above the scan's cap of %d", N, SCAN_MAX_N);
+  if ((long long)p->P > 2000000) return fail(MMSBM_ERR_UNSUPPORTED, "P=%d: packed keys overflow", p->P);
+  p->KP = (p->K + 3) / 4 * 4;
+  p->P16 = std::max(16, (p->P + 15) / 16 * 16);
+  p->N = N;
+  p->cap = 512;
+  while (p->cap < 2 * N) p->cap <<= 1;
+  const long long per_cu = N <= 1024 ? 4 : N <= 2048 ? 2 : 1;
+  const long long items = std::max<long long>(1, (long long)p->P * (p->P16 / 16));
+  p->G = (int)std::min<long long>(per_cu * p->ncu, items);
+  p->G2 = (p->G + FAN - 1) / FAN;
+  const size_t B = p->B, P = p->P, K = p->K, KP = p->KP, P16 = p->P16, G = p->G, cap = p->cap;
+  size_t off = 256;  // [0, 256): the published threshold
+  p->off_thT = off, off = align256(off + sizeof(double) * B * KP * P16);
+  p->off_T = off, off = align256(off + sizeof(double) * B * P * K * KP);
+  p->off_cs = off, off = align256(off + sizeof(double) * G * cap);
+  p->off_ck = off, off = align256(off + sizeof(long long) * G * cap);
+  const size_t nl[2] = {G, (size_t)p->G2};
+  for (int i = 0; i < 2; ++i) {
+    p->off_ls[i] = off, off = align256(off + sizeof(double) * nl[i] * N);
+    p->off_lk[i] = off, off = align256(off + sizeof(long long) * nl[i] * N);
+    p->off_ln[i] = off, off = align256(off + sizeof(int) * nl[i]);
+  }
+  p->total = off;
+  return MMSBM_OK;
+}
+
+template <int KS>
+int launch_scan(const ScanArgs& a, int G, int lds, hipStream_t s) {
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_kernel<KS>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  scan_kernel<KS><<<G, NT, lds, s>>>(a);
+  HIP_TRY(hipGetLastError());
+  return MMSBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmsbm_scan_max_n(void) { return SCAN_MAX_N; }
+
+int mmsbm_scan_workspace_bytes(const mmsbm_ctx* c, int32_t N, int64_t* bytes) {
+  if (!c || !bytes) return fail(MMSBM_ERR_INVALID, "null argument");
+  ScanPlan p;
+  int rc = make_plan(c, N, &p);
+  if (rc) return rc;
+  *bytes = (int64_t)p.total;
+  return MMSBM_OK;
+}
+
+int mmsbm_scan_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
+                    const double* theta, const double* pr, int32_t sample, int32_t N, void* ws,
+                    int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count,
+                    void* stream) {
+  if (!c) return fail(MMSBM_ERR_INVALID, "null context");
+  ScanPlan p;
+  int rc = make_plan(c, N, &p);
+  if (rc) return rc;
+  if (!order || !theta || !pr || !out_scores || !out_ids || !out_count)
+    return fail(MMSBM_ERR_INVALID, "null pointer");
+  if (n_known < 0 || (n_known > 0 && !known)) return fail(MMSBM_ERR_INVALID, "bad known-key table");
+  if (sample < -1 || sample >= p.nact)
+    return fail(MMSBM_ERR_INVALID, "sample %d outside the active prefix [0, %d)", sample, p.nact);
+  if (!ws || ws_bytes < (int64_t)p.total || ((uintptr_t)ws & 15))
+    return fail(MMSBM_ERR_INVALID, "scan workspace missing, misaligned or too small (mmsbm_scan_workspace_bytes)");
+  const int ns = sample >= 0 ? 1 : p.nact, s0 = sample >= 0 ? sample : 0;
+  const int WS = p.KP + 2;
+  int WB = 4;
+  while (WB > 1 && (size_t)ns * 16 * WB * WS * sizeof(double) > (size_t)W_LDS_MAX) WB >>= 1;
+  const size_t w_bytes = (size_t)ns * 16 * WB * WS * sizeof(double);
+  if (w_bytes > (size_t)W_LDS_MAX)
+    return fail(MMSBM_ERR_UNSUPPORTED, "an ensemble of %d samples at K=%d exceeds the scan's LDS tile: scan the samples one by one",
+                ns, p.K);
+  const size_t cand_bytes = (size_t)p.cap * 16;
+  const bool cand_lds = sizeof(Sel) + w_bytes + cand_bytes <= (size_t)LDS_MAX;
+  const int lds = (int)(sizeof(Sel) + w_bytes + (cand_lds ? cand_bytes : 0));
+  const int merge_lds = (int)(sizeof(Sel) + cand_bytes);
+  bool select = true;
+  if (const char* e = getenv("MMSBM_SCAN_SELECT")) select = atoi(e) != 0;  // measurement: the bare score phase
+
+  DeviceGuard g(p.device);
+  hipStream_t s = (hipStream_t)stream;
+  char* w = (char*)ws;
+  HIP_TRY(hipMemsetAsync(w, 0, 256, s));
+  int* ln[2] = {(int*)(w + p.off_ln[0]), (int*)(w + p.off_ln[1])};
+  double* ls[2] = {(double*)(w + p.off_ls[0]), (double*)(w + p.off_ls[1])};
+  long long* lk[2] = {(long long*)(w + p.off_lk[0]), (long long*)(w + p.off_lk[1])};
+  if (merge_lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_merge_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, merge_lds));
+  if (p.P >= 3) {
+    scan_prep_kernel<<<dim3(p.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
+                                                    (double*)(w + p.off_T), p.K, p.KP, p.R, p.P, p.P16, s0);
+    HIP_TRY(hipGetLastError());
+  }
+  // Pass 0 (large P only) seeds the bound: the same scan and merge over every SEED_STRIDE-th item,
+  // whose exact N-th score (a subset's N-th best is a lower bound of the whole's) is published
+  // instead of written out.  Pass 1 scans every item and starts from that bound, so it appends
+  // about N SEED_STRIDE candidates in all instead of filling every workgroup's buffer from nothing.
+  // The bound only prunes: the result does not depend on it.
+  for (int pass = (select && p.P >= SEED_MIN_P) ? 0 : 1; pass < 2; ++pass) {
+    const bool seeding = pass == 0;
+    int n_lists = 0;
+    if (p.P >= 3) {
+      ScanArgs a{};
+      a.thT = (const double*)(w + p.off_thT);
+      a.T = (const double*)(w + p.off_T);
+      a.known = (const long long*)known;
+      a.n_known = n_known;
+      a.cand_s = cand_lds ? nullptr : (double*)(w + p.off_cs);
+      a.cand_k = cand_lds ? nullptr : (long long*)(w + p.off_ck);
+      a.list_s = ls[0];
+      a.list_k = lk[0];
+      a.list_n = ln[0];
+      a.shared = (unsigned long long*)w;
+      a.K = p.K, a.P = p.P, a.P16 = p.P16, a.ns = ns, a.N = N, a.cap = p.cap, a.WB = WB, a.select = select;
+      a.stride = seeding ? SEED_STRIDE : 1;
+      n_lists = seeding ? std::min(p.G, p.ncu) : p.G;
+      switch (p.KP / 4) {
+        case 1: rc = launch_scan<1>(a, n_lists, lds, s); break;
+        case 2: rc = launch_scan<2>(a, n_lists, lds, s); break;
+        case 3: rc = launch_scan<3>(a, n_lists, lds, s); break;
+        case 4: rc = launch_scan<4>(a, n_lists, lds, s); break;
+        case 5: rc = launch_scan<5>(a, n_lists, lds, s); break;
+        case 6: rc = launch_scan<6>(a, n_lists, lds, s); break;
+        case 7: rc = launch_scan<7>(a, n_lists, lds, s); break;
+        default: rc = launch_scan<8>(a, n_lists, lds, s); break;
+      }
+      if (rc) return rc;
+    }
+    int cur = 0;
+    for (;;) {
+      const bool last = n_lists <= FAN;
+      MergeArgs ma{};
+      ma.in_s = ls[cur], ma.in_k = lk[cur], ma.in_n = ln[cur], ma.n_in = n_lists;
+      if (!last) ma.out_s = ls[cur ^ 1], ma.out_k = lk[cur ^ 1], ma.out_n = ln[cur ^ 1];
+      ma.order = order, ma.scores = out_scores, ma.ids = out_ids, ma.count = (long long*)out_count;
+      ma.shared = (seeding && last) ? (unsigned long long*)w : nullptr;
+      ma.N = N, ma.cap = p.cap, ma.P = std::max(p.P, 1);
+      const int n_out = last ? 1 : (n_lists + FAN - 1) / FAN;
+      scan_merge_kernel<<<n_out, NT, merge_lds, s>>>(ma);
+      HIP_TRY(hipGetLastError());
+      if (last) break;
+      n_lists = n_out;
+      cur ^= 1;
+    }
+  }
+  return MMSBM_OK;
+}
+
+}  // extern "C"

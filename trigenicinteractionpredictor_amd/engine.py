@@ -61,6 +61,8 @@ class EMEngine:
         self.active = self.B
         self._sets = set()
         self.workspace = None
+        self._scan_ws = None      # scan_top's scratch and rank order (built on first use)
+        self._scan_order = None
         self.theta = torch.zeros((self.B, self.P, self.K), dtype=torch.float64, device=self.device)
         self.pr = torch.zeros((self.B, self.R, self.K3), dtype=torch.float64, device=self.device)
 
@@ -193,6 +195,44 @@ class EMEngine:
             _lib.check(self.lib.mmsbm_predict(self.ctx, _ptr(ids_d), n, _ptr(self.theta), _ptr(self.pr),
                                               _ptr(out), self._stream()))
         return out[:, :n].cpu().numpy()
+
+    def scan_top_async(self, n: int, known: np.ndarray = None, sample: int = None, stream=None):
+        """scan_top without the host copy: -> device tensors (scores f64[n], ids int32[n][3],
+        count int64[1]); rows from `count` on are NaN / -1.  Nothing synchronises."""
+        from .scan import rank_order
+        n = int(n)
+        known = np.zeros(0, np.int64) if known is None else np.ascontiguousarray(known, dtype=np.int64)
+        if known.size > 1 and not (known[1:] > known[:-1]).all():
+            raise ValueError("known keys must be sorted and unique (scan.known_keys)")
+        if sample is not None and not 0 <= int(sample) < self.active:
+            raise ValueError("sample %r outside the active prefix [0, %d)" % (sample, self.active))
+        nbytes = ctypes.c_int64()
+        _lib.check(self.lib.mmsbm_scan_workspace_bytes(self.ctx, n, ctypes.byref(nbytes)))
+        if self._scan_ws is None or self._scan_ws.numel() < nbytes.value:
+            self._scan_ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        if self._scan_order is None:
+            self._scan_order = torch.from_numpy(rank_order(max(self.P, 1))).to(self.device)
+        known_d = torch.from_numpy(known).to(self.device)
+        scores = torch.empty(n, dtype=torch.float64, device=self.device)
+        ids = torch.empty((n, 3), dtype=torch.int32, device=self.device)
+        count = torch.empty(1, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.mmsbm_scan_topn(
+            self.ctx, _ptr(self._scan_order), _ptr(known_d) if known.size else None, int(known.size),
+            _ptr(self.theta), _ptr(self.pr), -1 if sample is None else int(sample), n,
+            _ptr(self._scan_ws), self._scan_ws.numel(), _ptr(scores), _ptr(ids), _ptr(count),
+            self._stream(stream)))
+        return scores, ids, count
+
+    def scan_top(self, n: int, known: np.ndarray = None, sample: int = None, stream=None):
+        """The n most probable triples of distinct genes (include/mmsbm.h mmsbm_scan_topn):
+        -> (scores f64[n'], ids int32[n'][3] in key order) on the host, best first, n' <= n.
+        known: sorted int64 packed keys to skip (scan.known_keys); sample: a slot of the active
+        prefix, or None for the mean over it."""
+        scores, ids, count = self.scan_top_async(n, known, sample, stream)
+        if stream is not None:
+            stream.synchronize()
+        m = int(count.cpu()[0])
+        return scores[:m].cpu().numpy(), ids[:m].cpu().numpy()
 
     # ---------------------------------------------------------- measurement
     def kernels(self) -> dict:

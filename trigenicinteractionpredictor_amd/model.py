@@ -415,6 +415,17 @@ class Model:
         eng = self._push()
         return float(eng.predict(np.array([ids], dtype=np.int32))[0, 0])
 
+    def predict_novel(self, n, exclude=("train", "test")):
+        """The n most probable triples of distinct genes outside the `exclude`d link tables, best
+        first: [probability, "i_j_k", [name1, name2, name3]] with the key as `links` spells it
+        (:349-358), the probability of do_prediction (:530-547) and the names sorted as the
+        `nlinks` keys are.  One scan of all C(P, 3) triples on the GPU (engine.scan_top)."""
+        from .scan import known_keys
+        eng = self._push()
+        scores, ids = eng.scan_top(int(n), known_keys(self, exclude), sample=0)
+        return [[float(p), "_".join(str(int(g)) for g in row), sorted(self.id_gene[int(g)] for g in row)]
+                for p, row in zip(scores, ids)]
+
     def calculate_test_set_results(self):
         tids, _ = self._link_arrays(1)
         keys = list(self.test_links.keys())

@@ -1,0 +1,188 @@
+"""Genome-wide scan: the most probable trigenic interactions nobody has measured.
+
+Host helpers of `EMEngine.scan_top` / `Model.predict_novel` (include/mmsbm.h, mmsbm_scan_topn) and
+a small driver.  The helpers import without a GPU.
+
+The reference keys a link by its three gene ids sorted as decimal strings
+(src/TrigenicInteractionPredictor.py:349-358: '10' < '2' < '9'), and slots 1, 2, 3 of
+pr[i][j][k] follow that order.  `rank_order(P)` is the gene ids in that order; a triple of distinct
+genes is three positions a < b < c of it and its packed key is (a P + b) P + c.
+
+    python -m trigenicinteractionpredictor_amd.scan -t train0.dat -e test0.dat -k 10 -n 8 -i 200 \
+        --top 1000 [--exclude train,test|train|none] [--best] [--seed S] [-o novel.tsv]
+
+fits the -n restarts as one batch for -i iterations (the initial states come from the same stdlib
+`random` stream as `Model.initialize_parameters`, seeded once), scans once (the ensemble mean, or
+with --best the restart of the highest train likelihood) and writes a TSV with the columns
+rank, probability, ids, names.
+"""
+from __future__ import annotations
+
+import getopt
+import random
+import sys
+
+import numpy as np
+
+SETS = ("train", "test")
+MAX_TOP = 4096   # mmsbm_scan_max_n() (include/mmsbm.h): the largest N one scan returns
+
+
+def rank_order(P: int) -> np.ndarray:
+    """Gene ids 0..P-1 sorted by str(id): rank_order(12) = [0, 1, 10, 11, 2, ..., 9]."""
+    return np.array(sorted(range(int(P)), key=str), dtype=np.int32)
+
+
+def rank_of(order: np.ndarray) -> np.ndarray:
+    """The inverse permutation: rank[id] = position of the id in `order`."""
+    order = np.asarray(order)
+    rank = np.empty(order.shape[0], dtype=np.int64)
+    rank[order] = np.arange(order.shape[0], dtype=np.int64)
+    return rank
+
+
+def pack_keys(ids, rank, P: int) -> np.ndarray:
+    """ids int[n][3] (gene ids) -> int64[n] packed keys (a P + b) P + c of their rank positions,
+    each row's positions sorted ascending (a key's string-sorted ids already are)."""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1, 3)
+    pos = np.sort(np.asarray(rank, dtype=np.int64)[ids], axis=1)
+    return (pos[:, 0] * int(P) + pos[:, 1]) * int(P) + pos[:, 2]
+
+
+def _id_tables(source, exclude):
+    if isinstance(source, (tuple, list)):   # (P, train ids, test ids); a table may be None
+        P, tables = int(source[0]), dict(zip(SETS, source[1:]))
+    else:                                   # a Model
+        P, tables = int(source.P), {name: source._link_arrays(i)[0] for i, name in enumerate(SETS)
+                                    if name in exclude}
+    return P, [np.asarray(tables[name], dtype=np.int64).reshape(-1, 3) for name in exclude
+               if tables.get(name) is not None]
+
+
+def parse_exclude(text):
+    """'train,test' | 'train' | 'test' | 'none' -> tuple of set names; ValueError otherwise."""
+    if isinstance(text, (tuple, list)):
+        names = tuple(text)
+    else:
+        names = () if text.strip() in ("", "none") else tuple(t.strip() for t in text.split(","))
+    for n in names:
+        if n not in SETS:
+            raise ValueError("exclude: %r is none of train, test, none" % (n,))
+    return tuple(dict.fromkeys(names))
+
+
+def known_keys(source, exclude=SETS) -> np.ndarray:
+    """Sorted, unique int64 packed keys of the measured triples of distinct genes: `source` is a
+    Model or (P, train_ids, test_ids); keys with a repeated gene are dropped (never candidates)."""
+    exclude = parse_exclude(exclude)
+    P, tables = _id_tables(source, exclude)
+    if not tables:
+        return np.zeros(0, dtype=np.int64)
+    ids = np.concatenate(tables, axis=0)
+    distinct = (ids[:, 0] != ids[:, 1]) & (ids[:, 1] != ids[:, 2]) & (ids[:, 0] != ids[:, 2])
+    return np.unique(pack_keys(ids[distinct], rank_of(rank_order(P)), P))
+
+
+# ------------------------------------------------------------------------------------- driver
+USAGE = """
+Usage:
+python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train file>
+    [-e|--test=] <test file> [-k|--k=] <number of groups> [-n|--num_samples=] <restarts>
+    [-i|--num_iterations=] <EM iterations> [--seed=] <RNG seed> [--top=] <rows, default 100>
+    [--exclude=] <train,test (default) | train | test | none> [--best] [-o|--out=] <TSV file>
+"""
+
+
+def parse(argv):
+    """Arguments -> cfg; cli.ArgError on a bad one (before anything touches a GPU).  -t, -e, -k, -n
+    and -i are validated by cli.parse."""
+    from . import cli
+    cfg = dict(cli.DEFAULTS, samples=1, iterations=100, top=100, exclude=SETS, best=False, out=None,
+               seed=None)
+    try:
+        opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
+                                                        "num_iterations=", "seed=", "top=", "exclude=",
+                                                        "best", "out="])
+    except getopt.GetoptError:
+        print("Argument error. Aborting")
+        raise cli.ArgError()
+    for opt, arg in opts:
+        if opt in ("-h", "--help"):
+            print(USAGE)
+            cfg["help"] = True
+            return cfg
+        try:
+            if opt == "--top":
+                if not 1 <= int(arg) <= MAX_TOP:
+                    print("\n\nERROR: --top should be an integer number in [1, %d]" % MAX_TOP)
+                    raise cli.ArgError()
+                cfg["top"] = int(arg)
+            elif opt == "--exclude":
+                try:
+                    cfg["exclude"] = parse_exclude(arg)
+                except ValueError as e:
+                    print("\n\nERROR: " + str(e))
+                    raise cli.ArgError()
+            elif opt == "--best":
+                cfg["best"] = True
+            elif opt == "--seed":
+                cfg["seed"] = int(arg)
+            elif opt in ("-o", "--out"):
+                cfg["out"] = arg
+            else:
+                cfg = cli.parse([opt, arg], cfg)
+        except ValueError:
+            raise cli.ArgError()
+    return cfg
+
+
+def run(cfg, out=print):
+    """Fit the restarts as one batch, scan once, return the rows [rank, probability, ids, names]."""
+    from . import _lib
+    from .engine import EMEngine
+    from .model import Model
+    from .restarts import stream_states
+    model = Model()
+    model.get_traintest(cfg["train"], cfg["test"])
+    K, B = cfg["k"], cfg["samples"]
+    if cfg["seed"] is not None:
+        random.seed(cfg["seed"])
+    eng = EMEngine(K, model.P, B=B, R=model.R, eps=model.eps)
+    eng.set_links(_lib.SET_TRAIN, *model._link_arrays(0))
+    for b, (_, theta, pr) in enumerate(stream_states(model, K, range(B))):
+        eng.upload_slot(b, theta, pr)
+    eng.iterate(cfg["iterations"])
+    sample = int(np.argmax(eng.loglik(_lib.SET_TRAIN))) if cfg["best"] else None
+    out("scanning %d genes: %s" % (model.P, "sample %d" % sample if sample is not None
+                                   else "mean of %d samples" % B))
+    scores, ids = eng.scan_top(cfg["top"], known_keys(model, cfg["exclude"]), sample)
+    eng.close()
+    return [[i + 1, float(p), "_".join(str(g) for g in row), sorted(model.id_gene[int(g)] for g in row)]
+            for i, (p, row) in enumerate(zip(scores, ids))]
+
+
+def write_tsv(rows, stream):
+    stream.write("rank\tprobability\tids\tnames\n")
+    for rank, p, key, names in rows:
+        stream.write("%d\t%r\t%s\t%s\n" % (rank, p, key, "_".join(names)))
+
+
+def main(argv=None, out=print):
+    from . import cli
+    try:
+        cfg = parse(sys.argv[1:] if argv is None else argv)
+    except cli.ArgError:
+        return 2
+    if cfg.get("help"):
+        return 0
+    rows = run(cfg, out)
+    if cfg["out"]:
+        with open(cfg["out"], "w", encoding="utf-8") as f:
+            write_tsv(rows, f)
+    else:
+        write_tsv(rows, sys.stdout)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
