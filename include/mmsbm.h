@@ -153,6 +153,50 @@ int mmsbm_scan_topn(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known, 
                     int64_t ws_bytes, double *out_scores, int32_t *out_ids, int64_t *out_count,
                     void *stream);
 
+/* Partner scan: for each query gene, the exact top N of Model.do_prediction (:530-547, no eps) over
+ * the pairs of other genes it forms a triple with.  Notation as for mmsbm_scan_topn: order[P]
+ * (device) = the gene ids sorted by str(id), Th' = theta in that order, p_1 the rating-1 lattice, a
+ * triple three rank positions sorted ascending with the packed key (a P + b) P + c and the score
+ * do_prediction(order[a], order[b], order[c]).
+ * Candidates of a query at rank position q: every pair of positions b < c with b != q and c != q;
+ * the triple is {q, b, c} sorted.  Its score factors through the query's slot of p_1:
+ *   q < b < c:  S = Th'[b] T1_q Th'[c]^T,  T1_q[y][z] = sum_x Th'[q][x] p_1[x][y][z]
+ *   b < q < c:  S = Th'[b] T2_q Th'[c]^T,  T2_q[x][z] = sum_y Th'[q][y] p_1[x][y][z]
+ *   b < c < q:  S = Th'[b] T3_q Th'[c]^T,  T3_q[x][y] = sum_z Th'[q][z] p_1[x][y][z]
+ * (two triangles and a rectangle of one P x P matrix, (P - 1)(P - 2) / 2 scores, each region a GEMM
+ * of inner size K).
+ * queries_host int32[Q] (HOST) = gene ids in [0, P); they may repeat and every row is answered on
+ * its own.  An id outside [0, P) returns MMSBM_ERR_INVALID before anything is launched; Q = 0
+ * returns MMSBM_OK and writes nothing.  The ids are copied to the workspace on `stream`.
+ * Exclusion, per query in CSR form: known_off int64[Q + 1] (device) offsets into known_pairs
+ * (device), query i's slice holding the sorted, unique pair keys b P + c (rank positions of the
+ * other two genes, b < c) to skip.  Keys that name q or no pair are ignored.  known_off = NULL: none.
+ * sample >= 0 scans that slot of the active prefix; -1 the ensemble, formed as the scan forms it:
+ * each slot's tile accumulated from zero, the tiles added in slot order, divided by n_active.
+ * Result (device), row i for query i: the first out_count[i] rows of out_scores f64[Q][N] and
+ * out_ids int32[Q][N][3] hold the query's best candidates under the scan's total order (score
+ * descending; equal scores: the smaller packed key of the TRIPLE first); out_ids are the whole
+ * triple's gene ids in key order, the query included, so a row can go straight into mmsbm_predict.
+ * out_count int64[Q]; the tail of a row is NaN / -1; P < 3: count 0.
+ * Every sum has a fixed order and no score is formed by an atomic, and the exact top N under a total
+ * order is unique: a query's list and its score bits do not depend on Q, on the other queries of
+ * the call, on the grid or on the batch the sample sits in.  The scores need not equal
+ * mmsbm_scan_topn's bit for bit (the contraction runs through another slot); they agree to 1e-9
+ * relative.
+ * 1 <= N <= mmsbm_partners_max_n() (1024: a workgroup's candidate buffer stays in the LDS); above
+ * it MMSBM_ERR_UNSUPPORTED, as for an ensemble whose two W tiles of 16 rows exceed 96 KiB of LDS:
+ * n_active (4 ceil(K / 4) + 2) > 384 (scan the slots one by one).  Q <= 65535.  Needs R >= 2.
+ * ws: mmsbm_partners_workspace_bytes(ctx, Q, N) bytes of device scratch, 16-byte aligned, the
+ * caller's; its size follows the context's shape, Q and N only.  theta and pr are only read; all
+ * launches go to `stream` and nothing synchronises.  The caller guarantees that order is a
+ * permutation of [0, P).  Replaces nothing in the reference. */
+int mmsbm_partners_max_n(void);
+int mmsbm_partners_workspace_bytes(const mmsbm_ctx *ctx, int64_t Q, int32_t N, int64_t *bytes);
+int mmsbm_partners_topn(mmsbm_ctx *ctx, const int32_t *order, const int32_t *queries_host, int64_t Q,
+                        const int64_t *known_off, const int64_t *known_pairs, const double *theta,
+                        const double *pr, int32_t sample, int32_t N, void *ws, int64_t ws_bytes,
+                        double *out_scores, int32_t *out_ids, int64_t *out_count, void *stream);
+
 /* Link-sharded iteration (single sample over N ranks): each rank's context
  * holds 1/N of the train links (mmsbm_set_links) and the GLOBAL degree (mmsbm_set_degree).
  * Step 1, the accumulation half of make_iteration (:986-1012) over this rank's links:

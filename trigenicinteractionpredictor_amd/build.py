@@ -15,7 +15,8 @@ REPO = os.path.dirname(PKG)
 SRC = os.path.join(PKG, "csrc", "mmsbm.hip")           # triplet engine (include/mmsbm.h)
 SRC_PAIRS = os.path.join(PKG, "csrc", "pairs.hip")     # joint model pair lattice (mmsbm_pairs.h)
 SRC_SCAN = os.path.join(PKG, "csrc", "scan.hip")       # genome-wide top-N scan (mmsbm_scan_*)
-SRCS = [SRC, SRC_PAIRS, SRC_SCAN]
+SRC_PARTNERS = os.path.join(PKG, "csrc", "partners.hip")   # per-gene partner scan (mmsbm_partners_*)
+SRCS = [SRC, SRC_PAIRS, SRC_SCAN, SRC_PARTNERS]
 INCLUDE = os.path.join(REPO, "include")
 OUT_DIR = os.path.join(PKG, "_build")
 LIB = os.path.join(OUT_DIR, "libmmsbm.so")
@@ -26,7 +27,8 @@ DEPS = {
     SRC: [os.path.join(PKG, "csrc", "plan.h"), os.path.join(PKG, "csrc", "sk.h"),
           os.path.join(INCLUDE, "mmsbm.h")],
     SRC_PAIRS: [os.path.join(INCLUDE, "mmsbm.h"), os.path.join(INCLUDE, "mmsbm_pairs.h")],
-    SRC_SCAN: [os.path.join(INCLUDE, "mmsbm.h")],
+    SRC_SCAN: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(INCLUDE, "mmsbm.h")],
+    SRC_PARTNERS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(INCLUDE, "mmsbm.h")],
 }
 
 

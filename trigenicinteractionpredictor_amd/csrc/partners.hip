@@ -1,0 +1,533 @@
+// partners.hip — MI355X (gfx950) kernels + C ABI (include/mmsbm.h, mmsbm_partners_*) of the partner
+// scan: for each query gene, the exact top N of do_prediction (:530-547) over every pair of other
+// genes it can form a triple with.
+//
+// Notation as in scan.hip: Th' = theta in rank order (ids sorted by str(id)), p_1 the rating-1
+// lattice, a triple three rank positions sorted ascending.  For a query at position q the candidates
+// are the pairs b < c with b, c != q, and the score factors through the query's slot of p_1:
+//   q < b < c:  S = Th'[b] T1_q Th'[c]^T,  T1_q[y][z] = sum_x Th'[q][x] p_1[x][y][z]
+//   b < q < c:  S = Th'[b] T2_q Th'[c]^T,  T2_q[x][z] = sum_y Th'[q][y] p_1[x][y][z]
+//   b < c < q:  S = Th'[b] T3_q Th'[c]^T,  T3_q[x][y] = sum_z Th'[q][z] p_1[x][y][z]
+// so a query is two triangles and a rectangle of one P x P matrix, each a GEMM of inner size K:
+//   Tm_q               K^3 per query and matrix      (partners_prep_kernel)
+//   Wm[b] = Th'[b] Tm  K^2 per (q, b, m)             (partners_kernel, LDS)
+//   S[b][c] = Wm[b] . Th'[c]                         (v_mfma_f64_16x16x4)
+// A row b > q needs W1 only, a row b < q W2 (for c > q) and W3 (for c < q), so two W rows per b
+// cover the three regions: U[b] = W1[b] (b > q) or W2[b] (b < q) for every c > q, L[b] = W3[b] for
+// every c < q.
+//
+// partners_kernel: a work item is (query, a block of 16 WB rows b, a chunk of c-tiles); the row
+// block holds U and L of its rows in LDS (every sample of the ensemble).  A 16 x 16 tile runs the
+// U chain, the L chain, or both on the tiles the query's column crosses, and each lane keeps the
+// chain of its own column (c > q: U, c < q: L), so a score's bits follow from (q, b, c) alone.  Query i owns workgroups [i gpq, (i + 1) gpq): gpq follows the device size over
+// Q, so one query spreads over the device and P queries get a workgroup or two each; the c chunks
+// exist only to cut one query into enough items.  Selection is the scan's (scan_select.h), per
+// query: every workgroup keeps its best N in LDS and publishes its N-th score to the query's word
+// (a subset's N-th best is a lower bound of the query's N-th), partners_merge_kernel merges a
+// query's lists (fan-in 32, at most two levels) and writes its row.  The exact top N under a total
+// order is unique, no score is formed by an atomic and every sum has a fixed order: a query's row
+// does not depend on Q, the other queries, the grid or the batch.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstdint>
+#include <cstdlib>
+
+#include "mmsbm.h"
+#include "scan_select.h"
+
+namespace {
+
+using namespace scan_select;
+
+constexpr int PARTNERS_MAX_N = 1024;   // documented cap of N (include/mmsbm.h): the buffer stays in LDS
+constexpr int MAX_GPQ = FAN * FAN;     // workgroups per query: two merge levels at most
+constexpr int W_LDS_MAX = 96 * 1024;   // U and L of one row block, every sample
+
+// ------------------------------------------------------------------------------------------
+// Prep
+// ------------------------------------------------------------------------------------------
+// Th' k-major and zero-padded: thT[s][KP][P16].  grid (ceil(KP P16 / NT), samples).
+__global__ __launch_bounds__(NT) void partners_theta_kernel(const int* __restrict__ order,
+                                                            const double* __restrict__ theta,
+                                                            double* __restrict__ thT, int K, int KP, int P,
+                                                            int P16, int s0) {
+  const int idx = blockIdx.x * NT + threadIdx.x, s = blockIdx.y;
+  if (idx >= KP * P16) return;
+  const int k = idx / P16, a = idx % P16;
+  int g = a < P ? order[a] : -1;
+  if (g < 0 || g >= P) g = -1;  // outside the table: a zero row
+  thT[(size_t)s * KP * P16 + idx] = (g >= 0 && k < K) ? theta[((size_t)(s0 + s) * P + g) * K + k] : 0.0;
+}
+
+// T[s][Q][3][K][KP] of every query (zero-padded like the scan's T_a) and its rank position.
+// grid (Q, samples).
+__global__ __launch_bounds__(NT) void partners_prep_kernel(const int* __restrict__ order,
+                                                           const int* __restrict__ queries,
+                                                           const double* __restrict__ theta,
+                                                           const double* __restrict__ pr,
+                                                           double* __restrict__ T, int* __restrict__ qpos,
+                                                           int K, int KP, int R, int P, int Q, int s0) {
+  __shared__ double th[MMSBM_MAX_K];
+  __shared__ int pos;
+  const int qi = blockIdx.x, s = blockIdx.y;
+  const int g = queries[qi];  // in [0, P): checked on the host
+  const size_t K2 = (size_t)K * K, K3 = K2 * K;
+  if (threadIdx.x == 0) pos = -1;
+  if ((int)threadIdx.x < K) th[threadIdx.x] = theta[((size_t)(s0 + s) * P + g) * K + threadIdx.x];
+  __syncthreads();
+  if (s == 0) {
+    for (int a = threadIdx.x; a < P; a += NT)
+      if (order[a] == g) pos = a;
+    __syncthreads();
+    if (threadIdx.x == 0) qpos[qi] = pos;  // -1 (order is no permutation): the query has no candidate
+  }
+  const double* __restrict__ p1 = pr + ((size_t)(s0 + s) * R + 1) * K3;
+  double* __restrict__ Tq = T + ((size_t)s * Q + qi) * 3 * K * KP;
+  for (int idx = threadIdx.x; idx < 3 * K * KP; idx += NT) {
+    const int mm = idx / (K * KP), i = (idx / KP) % K, j = idx % KP;
+    double v = 0.0;
+    if (j < K) {
+      // the query's slot is contracted: slot 1 (T1[y][z]), slot 2 (T2[x][z]) or slot 3 (T3[x][y])
+      const double* __restrict__ p = mm == 0 ? p1 + i * K + j : mm == 1 ? p1 + i * K2 + j : p1 + i * K2 + j * K;
+      const size_t step = mm == 0 ? K2 : mm == 1 ? (size_t)K : (size_t)1;
+      for (int t = 0; t < K; ++t) v = fma(th[t], p[t * step], v);
+    }
+    Tq[idx] = v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Scan
+// ------------------------------------------------------------------------------------------
+struct PartArgs {
+  const double* thT;           // [ns][KP][P16]
+  const double* T;             // [ns][Q][3][K][KP]
+  const int* qpos;             // [Q] rank position of each query
+  const long long* known_off;  // [Q + 1] (null: no exclusion)
+  const long long* known;      // each query's sorted pair keys b P + c
+  double* list_s;              // per-workgroup results [Q gpq][N]
+  long long* list_k;
+  int* list_n;                 // [Q gpq]
+  unsigned long long* shared;  // [Q] published threshold bits
+  int K, P, P16, Q, ns, N, cap, WB, select;
+  int gpq;                     // workgroups per query
+  int ncc;                     // c chunks per row block
+};
+
+template <int KS>
+__global__ __launch_bounds__(NT) void partners_kernel(PartArgs A) {
+  constexpr int KP = 4 * KS, WS = KP + 2;  // W row stride: conflict-free A-operand reads
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  Sel* st = reinterpret_cast<Sel*>(smem);
+  double* W = reinterpret_cast<double*>(smem + sizeof(Sel));  // [2][ns][RB][WS]: U, L
+  const int RB = 16 * A.WB;
+  const int P = A.P, P16 = A.P16, K = A.K, ns = A.ns;
+  double* cs = W + (size_t)2 * ns * RB * WS;  // the candidate buffer
+  long long* ck = reinterpret_cast<long long*>(cs + A.cap);
+  const int qi = blockIdx.x / A.gpq, j = blockIdx.x % A.gpq;
+  const int q = A.qpos[qi];
+  unsigned long long* shared = A.shared + qi;
+  if (threadIdx.x == 0) {
+    sel_init(st);
+    if (A.known_off) {
+      st->klo = A.known_off[qi];
+      st->khi = A.known_off[qi + 1];
+    }
+  }
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = lane & 15, kk = lane >> 4;
+  const int wb = wave % A.WB, wc = wave / A.WB, CW = 4 / A.WB;
+  const int nct = P16 / 16;
+  const int nbq = (P + RB - 1) / RB;
+  const int CT = (nct + A.ncc - 1) / A.ncc;  // c-tiles per chunk
+  const long long PP = (long long)P;
+  const double inv_div = (double)ns;
+  const size_t Tq = (size_t)qi * 3 * K * KP, Ts = (size_t)A.Q * 3 * K * KP;
+
+  // the query's items round-robin over its workgroups
+  for (int it = (q >= 0 && q < P) ? j : INT_MAX; it < nbq * A.ncc; it += A.gpq) {
+    const int bq = it / A.ncc, cc = it % A.ncc;
+    const int ct_lo = cc * CT, ct_hi = min(nct, ct_lo + CT);
+    const int r0 = bq * RB;
+    if (ct_lo >= ct_hi || r0 >= P - 1 || ct_hi * 16 - 1 <= r0) continue;  // no b < c here
+    __syncthreads();  // the previous item's W is read
+    if (threadIdx.x == 0) {
+      const unsigned long long g = __hip_atomic_load(shared, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      st->gthr = g ? __longlong_as_double((long long)g) : neg_inf();
+    }
+    // U = W1 of the rows above q and W2 of the rows below it, L = W3 of the rows below it (zero
+    // elsewhere), every sample
+    for (int idx = threadIdx.x; idx < 2 * ns * RB * KP; idx += NT) {
+      const int z = idx % KP, r = (idx / KP) % RB, s = (idx / (KP * RB)) % ns, ul = idx / (KP * RB * ns);
+      const int rowb = r0 + r;
+      const int mm = ul ? 2 : rowb > q ? 0 : 1;
+      double v = 0.0;
+      if (rowb < P && rowb != q && (ul == 0 || rowb < q)) {
+        const double* __restrict__ Tm = A.T + (size_t)s * Ts + Tq + (size_t)mm * K * KP + z;
+        const double* __restrict__ tb = A.thT + (size_t)s * KP * P16 + rowb;
+        for (int i = 0; i < K; ++i) v = fma(tb[(size_t)i * P16], Tm[i * KP], v);
+      }
+      W[((size_t)(ul * ns + s) * RB + r) * WS + z] = v;
+    }
+    __syncthreads();
+
+    const int btile = bq * A.WB + wb, b0 = btile * 16;
+    const bool wave_on = b0 < P - 1;
+    const bool rows_hi = b0 + 15 > q, rows_lo = b0 < q;  // the tile has rows above / below q
+    int ct = ct_lo + wc;
+    if (ct < btile) ct += (btile - ct + CW - 1) / CW * CW;  // every c of those tiles is below every b
+    const long long klo = st->klo, khi = st->khi;
+    double areg[2][KS];  // single sample: the A operands live in registers for the whole item
+    if (wave_on && ns == 1) {
+#pragma unroll
+      for (int ul = 0; ul < 2; ++ul)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) areg[ul][ks] = W[((size_t)ul * RB + wb * 16 + m) * WS + 4 * ks + kk];
+    }
+    for (;;) {
+      // the thresholds change only when the workgroup sorts its buffer (behind a barrier)
+      const double thr_s = st->thr_s, gthr = st->gthr;
+      const long long thr_k = st->thr_k;
+      const double cut = fmax(thr_s, gthr);
+      if (wave_on) {
+        double bnext[KS];  // single sample: the next tile's Th' operand is in flight
+        if (ns == 1 && ct < ct_hi) {
+          const double* __restrict__ tc = A.thT + (size_t)kk * P16 + ct * 16 + m;
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) bnext[ks] = tc[(size_t)(4 * ks) * P16];
+        }
+        for (; ct < ct_hi; ct += CW) {
+          const int c0 = ct * 16, c = c0 + m;
+          // U: some c > q (rows below q) or rows above q (all their c are); L: rows and c below q
+          const bool need[2] = {rows_hi || c0 + 15 > q, rows_lo && c0 < q};
+          double bcur[KS];
+          if (ns == 1) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) bcur[ks] = bnext[ks];
+            if (ct + CW < ct_hi) {
+              const double* __restrict__ tc = A.thT + (size_t)kk * P16 + c + 16 * CW;
+#pragma unroll
+              for (int ks = 0; ks < KS; ++ks) bnext[ks] = tc[(size_t)(4 * ks) * P16];
+            }
+          }
+          d4v res = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int ul = 0; ul < 2; ++ul) {
+            if (!need[ul]) continue;  // wave-uniform
+            d4v tot = {0.0, 0.0, 0.0, 0.0};
+            if (ns == 1) {
+#pragma unroll
+              for (int ks = 0; ks < KS; ++ks)
+                tot = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ul][ks], bcur[ks], tot, 0, 0, 0);
+            } else {
+              for (int s = 0; s < ns; ++s) {
+                const double* __restrict__ tc = A.thT + ((size_t)s * KP + kk) * P16 + c;
+                const double* wr = W + ((size_t)(ul * ns + s) * RB + wb * 16 + m) * WS + kk;
+                d4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+                  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[4 * ks], tc[(size_t)(4 * ks) * P16], acc, 0, 0, 0);
+                tot = s == 0 ? acc : tot + acc;  // samples added in slot order
+              }
+              tot = tot / inv_div;
+            }
+            // lane holds S[b0 + kk + 4 i][c0 + m]: keep the chain of its own column
+            if ((c < q) == (ul == 1)) res = tot;
+          }
+          if (!A.select) {
+            asm volatile("" ::"v"(res[0]), "v"(res[1]), "v"(res[2]), "v"(res[3]));  // keep the score phase live
+            continue;
+          }
+          // first the score alone against the larger of the two bounds (equal scores stay in: the
+          // key decides below); nearly every tile ends here once the buffer holds N
+          if (!__ballot(res[0] >= cut || res[1] >= cut || res[2] >= cut || res[3] >= cut)) continue;
+          bool pass[4];
+          long long key[4];
+          unsigned long long mk[4];
+          int n = 0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int b = b0 + kk + 4 * i;
+            // the triple's packed key, q in its sorted place
+            key[i] = b > q ? ((long long)q * PP + b) * PP + c
+                   : c > q ? ((long long)b * PP + q) * PP + c
+                           : ((long long)b * PP + c) * PP + q;
+            pass[i] = b < c && c < P && b != q && c != q && !(res[i] < gthr) &&
+                      before(res[i], key[i], thr_s, thr_k);
+            if (pass[i] && khi > klo) pass[i] = !is_known(A.known, klo, khi, (long long)b * PP + c);
+            mk[i] = __ballot(pass[i]);
+            n += __popcll(mk[i]);
+          }
+          if (!n) continue;
+          int pos = wave_reserve(st, n, A.cap);
+          if (pos < 0) break;  // the tile is redone after the workgroup made room
+          const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (pass[i]) {
+              const int at = pos + __popcll(mk[i] & below);
+              cs[at] = res[i];
+              ck[at] = key[i];
+            }
+            pos += __popcll(mk[i]);
+          }
+        }
+      }
+      __syncthreads();
+      if (!st->overflow) break;
+      wg_keep_best(st, cs, ck, A.N, shared);
+    }
+  }
+  wg_keep_best(st, cs, ck, A.N, shared);
+  const int cnt = st->count;
+  for (int i = threadIdx.x; i < cnt; i += NT) {
+    A.list_s[(size_t)blockIdx.x * A.N + i] = cs[i];
+    A.list_k[(size_t)blockIdx.x * A.N + i] = ck[i];
+  }
+  if (threadIdx.x == 0) A.list_n[blockIdx.x] = cnt;
+}
+
+// ------------------------------------------------------------------------------------------
+// Merge, grid (lists out per query, Q): workgroup (w, i) keeps the best N of query i's lists
+// [FAN w, FAN (w + 1)); the last level (one workgroup per query) writes the query's row: scores,
+// gene ids in key order, count, NaN / -1 tail.
+// ------------------------------------------------------------------------------------------
+struct PMergeArgs {
+  const double* in_s;   // [Q][n_in][N]
+  const long long* in_k;
+  const int* in_n;
+  int n_in;             // lists per query
+  double* out_s;        // next level's lists [Q][gridDim.x][N] (null on the last level)
+  long long* out_k;
+  int* out_n;
+  const int* order;     // last level
+  double* scores;       // [Q][N]
+  int* ids;             // [Q][N][3]
+  long long* count;     // [Q]
+  int N, cap, P;
+};
+
+__global__ __launch_bounds__(NT) void partners_merge_kernel(PMergeArgs A) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  Sel* st = reinterpret_cast<Sel*>(smem);
+  double* cs = reinterpret_cast<double*>(smem + sizeof(Sel));
+  long long* ck = reinterpret_cast<long long*>(cs + A.cap);
+  if (threadIdx.x == 0) sel_init(st);
+  __syncthreads();
+  const int qi = blockIdx.y;
+  const int base = qi * A.n_in, l0 = base + blockIdx.x * FAN, l1 = min(l0 + FAN, base + A.n_in);
+  wg_merge_lists(st, cs, ck, A.in_s, A.in_k, A.in_n, l0, l1, A.N, A.cap);
+  wg_keep_best(st, cs, ck, A.N, nullptr);
+  const int cnt = st->count;
+  if (A.out_s) {
+    const size_t o = (size_t)qi * gridDim.x + blockIdx.x;
+    for (int i = threadIdx.x; i < cnt; i += NT) {
+      A.out_s[o * A.N + i] = cs[i];
+      A.out_k[o * A.N + i] = ck[i];
+    }
+    if (threadIdx.x == 0) A.out_n[o] = cnt;
+    return;
+  }
+  const long long PP = A.P;
+  double* scores = A.scores + (size_t)qi * A.N;
+  int* ids = A.ids + (size_t)qi * A.N * 3;
+  for (int i = threadIdx.x; i < A.N; i += NT) {
+    if (i < cnt) {
+      const long long k = ck[i];
+      scores[i] = cs[i];
+      ids[3 * i] = A.order[k / (PP * PP)];
+      ids[3 * i + 1] = A.order[(k / PP) % PP];
+      ids[3 * i + 2] = A.order[k % PP];
+    } else {
+      scores[i] = __builtin_nan("");
+      ids[3 * i] = ids[3 * i + 1] = ids[3 * i + 2] = -1;
+    }
+  }
+  if (threadIdx.x == 0) A.count[qi] = cnt;
+}
+
+// ------------------------------------------------------------------------------------------
+// Host side
+// ------------------------------------------------------------------------------------------
+struct PartPlan {
+  int device, K, KP, R, B, P, P16, nact, ncu;
+  int N, cap, gpq, n1;
+  long long Q;
+  size_t off_q, off_qpos, off_thT, off_T, off_ls[2], off_lk[2], off_ln[2], total;
+};
+
+// Everything that sizes the workspace follows the context's shape, Q and N only (not the sample
+// argument), so one workspace serves every call of that shape.
+int make_plan(const mmsbm_ctx* c, long long Q, int N, PartPlan* p) {
+  mmsbm_detail_scan_shape(c, &p->device, &p->K, &p->R, &p->B, &p->P, &p->nact, &p->ncu);
+  if (p->K < 1 || p->K > MMSBM_MAX_K)
+    return fail(MMSBM_ERR_UNSUPPORTED, "K=%d outside [1, %d]: call mmsbm_set_shape", p->K, MMSBM_MAX_K);
+  if (p->R < 2 || p->B < 1 || p->P < 0)
+    return fail(MMSBM_ERR_INVALID, "the partner scan needs R >= 2, B >= 1 (mmsbm_set_shape)");
+  if (N < 1) return fail(MMSBM_ERR_INVALID, "N=%d < 1", N);
+  if (N > PARTNERS_MAX_N)
+    return fail(MMSBM_ERR_UNSUPPORTED, "N=%d above the partner scan's cap of %d", N, PARTNERS_MAX_N);
+  if (Q < 0 || Q > 65535) return fail(MMSBM_ERR_INVALID, "Q=%lld outside [0, 65535]", Q);
+  if ((long long)p->P > 2000000) return fail(MMSBM_ERR_UNSUPPORTED, "P=%d: packed keys overflow", p->P);
+  p->KP = (p->K + 3) / 4 * 4;
+  p->P16 = std::max(16, (p->P + 15) / 16 * 16);
+  p->N = N;
+  p->Q = Q;
+  p->cap = 512;
+  while (p->cap < 2 * N) p->cap <<= 1;
+  // workgroups per query: the device's worth over Q, no more than a query has items at the
+  // narrowest row block, at most two merge levels
+  const long long Q1 = std::max<long long>(Q, 1);
+  const long long items_max = (long long)((p->P + 15) / 16) * (p->P16 / 16);
+  const long long want = (8LL * std::max(p->ncu, 1) + Q1 - 1) / Q1;
+  p->gpq = (int)std::max<long long>(1, std::min<long long>({want, items_max, (long long)MAX_GPQ}));
+  p->n1 = (p->gpq + FAN - 1) / FAN;
+  const size_t B = p->B, P = p->P, K = p->K, KP = p->KP, P16 = p->P16, q = (size_t)Q1;
+  size_t off = align256(sizeof(unsigned long long) * q);  // [0, 8 Q): the published thresholds
+  p->off_q = off, off = align256(off + sizeof(int) * q);
+  p->off_qpos = off, off = align256(off + sizeof(int) * q);
+  p->off_thT = off, off = align256(off + sizeof(double) * B * KP * P16);
+  p->off_T = off, off = align256(off + sizeof(double) * B * q * 3 * K * KP);
+  const size_t nl[2] = {q * p->gpq, q * p->n1};
+  for (int i = 0; i < 2; ++i) {
+    p->off_ls[i] = off, off = align256(off + sizeof(double) * nl[i] * N);
+    p->off_lk[i] = off, off = align256(off + sizeof(long long) * nl[i] * N);
+    p->off_ln[i] = off, off = align256(off + sizeof(int) * nl[i]);
+  }
+  (void)P;
+  p->total = off;
+  return MMSBM_OK;
+}
+
+template <int KS>
+int launch_partners(const PartArgs& a, int G, int lds, hipStream_t s) {
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&partners_kernel<KS>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  partners_kernel<KS><<<G, NT, lds, s>>>(a);
+  HIP_TRY(hipGetLastError());
+  return MMSBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmsbm_partners_max_n(void) { return PARTNERS_MAX_N; }
+
+int mmsbm_partners_workspace_bytes(const mmsbm_ctx* c, int64_t Q, int32_t N, int64_t* bytes) {
+  if (!c || !bytes) return fail(MMSBM_ERR_INVALID, "null argument");
+  PartPlan p;
+  int rc = make_plan(c, Q, N, &p);
+  if (rc) return rc;
+  *bytes = (int64_t)p.total;
+  return MMSBM_OK;
+}
+
+int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_host, int64_t Q,
+                        const int64_t* known_off, const int64_t* known_pairs, const double* theta,
+                        const double* pr, int32_t sample, int32_t N, void* ws, int64_t ws_bytes,
+                        double* out_scores, int32_t* out_ids, int64_t* out_count, void* stream) {
+  if (!c) return fail(MMSBM_ERR_INVALID, "null context");
+  PartPlan p;
+  int rc = make_plan(c, Q, N, &p);
+  if (rc) return rc;
+  if (Q == 0) return MMSBM_OK;
+  if (!order || !queries_host || !theta || !pr || !out_scores || !out_ids || !out_count)
+    return fail(MMSBM_ERR_INVALID, "null pointer");
+  if (known_off && !known_pairs) return fail(MMSBM_ERR_INVALID, "known_off without known_pairs");
+  for (int64_t i = 0; i < Q; ++i)
+    if (queries_host[i] < 0 || queries_host[i] >= p.P)
+      return fail(MMSBM_ERR_INVALID, "query %lld: gene id %d outside [0, %d)", (long long)i, queries_host[i], p.P);
+  if (sample < -1 || sample >= p.nact)
+    return fail(MMSBM_ERR_INVALID, "sample %d outside the active prefix [0, %d)", sample, p.nact);
+  if (!ws || ws_bytes < (int64_t)p.total || ((uintptr_t)ws & 15))
+    return fail(MMSBM_ERR_INVALID,
+                "partner workspace missing, misaligned or too small (mmsbm_partners_workspace_bytes)");
+  const int ns = sample >= 0 ? 1 : p.nact, s0 = sample >= 0 ? sample : 0;
+  const int WS = p.KP + 2;
+  int WB = 4;
+  while (WB > 1 && (size_t)2 * ns * 16 * WB * WS * sizeof(double) > (size_t)W_LDS_MAX) WB >>= 1;
+  const size_t w_bytes = (size_t)2 * ns * 16 * WB * WS * sizeof(double);
+  if (w_bytes > (size_t)W_LDS_MAX)
+    return fail(MMSBM_ERR_UNSUPPORTED,
+                "an ensemble of %d samples at K=%d exceeds the partner scan's LDS tile: scan the samples one by one",
+                ns, p.K);
+  const size_t cand_bytes = (size_t)p.cap * 16;
+  const int lds = (int)(sizeof(Sel) + w_bytes + cand_bytes);
+  const int merge_lds = (int)(sizeof(Sel) + cand_bytes);
+  static_assert(sizeof(Sel) + W_LDS_MAX + 2 * PARTNERS_MAX_N * 16 <= LDS_MAX, "the buffer stays in LDS");
+  bool select = true;
+  if (const char* e = getenv("MMSBM_PARTNERS_SELECT")) select = atoi(e) != 0;  // measurement: the bare score phase
+
+  DeviceGuard g(p.device);
+  hipStream_t s = (hipStream_t)stream;
+  char* w = (char*)ws;
+  const int nq = (int)Q;
+  int* ln[2] = {(int*)(w + p.off_ln[0]), (int*)(w + p.off_ln[1])};
+  double* ls[2] = {(double*)(w + p.off_ls[0]), (double*)(w + p.off_ls[1])};
+  long long* lk[2] = {(long long*)(w + p.off_lk[0]), (long long*)(w + p.off_lk[1])};
+  int n_lists = 0;  // per query
+  if (p.P >= 3) {
+    HIP_TRY(hipMemsetAsync(w, 0, sizeof(unsigned long long) * nq, s));
+    HIP_TRY(hipMemcpyAsync(w + p.off_q, queries_host, sizeof(int) * nq, hipMemcpyHostToDevice, s));
+    partners_theta_kernel<<<dim3((p.KP * p.P16 + NT - 1) / NT, ns), NT, 0, s>>>(
+        order, theta, (double*)(w + p.off_thT), p.K, p.KP, p.P, p.P16, s0);
+    HIP_TRY(hipGetLastError());
+    partners_prep_kernel<<<dim3(nq, ns), NT, 0, s>>>(order, (const int*)(w + p.off_q), theta, pr,
+                                                     (double*)(w + p.off_T), (int*)(w + p.off_qpos), p.K,
+                                                     p.KP, p.R, p.P, nq, s0);
+    HIP_TRY(hipGetLastError());
+    PartArgs a{};
+    a.thT = (const double*)(w + p.off_thT);
+    a.T = (const double*)(w + p.off_T);
+    a.qpos = (const int*)(w + p.off_qpos);
+    a.known_off = (const long long*)known_off;
+    a.known = (const long long*)known_pairs;
+    a.list_s = ls[0], a.list_k = lk[0], a.list_n = ln[0];
+    a.shared = (unsigned long long*)w;
+    a.K = p.K, a.P = p.P, a.P16 = p.P16, a.Q = nq, a.ns = ns, a.N = N, a.cap = p.cap, a.WB = WB;
+    a.select = select;
+    a.gpq = p.gpq;
+    const int nbq = (p.P + 16 * WB - 1) / (16 * WB), nct = p.P16 / 16;
+    a.ncc = std::max(1, std::min(nct, (p.gpq + nbq - 1) / nbq));  // enough items for the query's workgroups
+    n_lists = p.gpq;
+    const int G = nq * p.gpq;
+    switch (p.KP / 4) {
+      case 1: rc = launch_partners<1>(a, G, lds, s); break;
+      case 2: rc = launch_partners<2>(a, G, lds, s); break;
+      case 3: rc = launch_partners<3>(a, G, lds, s); break;
+      case 4: rc = launch_partners<4>(a, G, lds, s); break;
+      case 5: rc = launch_partners<5>(a, G, lds, s); break;
+      case 6: rc = launch_partners<6>(a, G, lds, s); break;
+      case 7: rc = launch_partners<7>(a, G, lds, s); break;
+      default: rc = launch_partners<8>(a, G, lds, s); break;
+    }
+    if (rc) return rc;
+  }
+  if (merge_lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&partners_merge_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, merge_lds));
+  int cur = 0;
+  for (;;) {
+    const bool last = n_lists <= FAN;
+    PMergeArgs ma{};
+    ma.in_s = ls[cur], ma.in_k = lk[cur], ma.in_n = ln[cur], ma.n_in = n_lists;
+    if (!last) ma.out_s = ls[cur ^ 1], ma.out_k = lk[cur ^ 1], ma.out_n = ln[cur ^ 1];
+    ma.order = order, ma.scores = out_scores, ma.ids = out_ids, ma.count = (long long*)out_count;
+    ma.N = N, ma.cap = p.cap, ma.P = std::max(p.P, 1);
+    const int n_out = last ? 1 : (n_lists + FAN - 1) / FAN;
+    partners_merge_kernel<<<dim3(n_out, nq), NT, merge_lds, s>>>(ma);
+    HIP_TRY(hipGetLastError());
+    if (last) break;
+    n_lists = n_out;
+    cur ^= 1;
+  }
+  return MMSBM_OK;
+}
+
+}  // extern "C"

@@ -31,158 +31,27 @@
 // workgroup writes its sorted best N; scan_merge_kernel (own launches, fan-in 32) merges the lists
 // with the same buffer and order.  The exact top N under a total order is unique: the result does
 // not depend on the grid, the arrival order or the batch.  Scores are never combined by atomics
-// and every sum has a fixed order.
+// and every sum has a fixed order.  The selection machinery (order, buffer, keep-best-N, merge) is
+// scan_select.h, shared with the partner scan (partners.hip).
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
 
 #include "mmsbm.h"
-
-int mmsbm_detail_fail(int code, const char* msg);  // mmsbm.hip: the library's error channel
-int mmsbm_detail_scan_shape(const mmsbm_ctx* c, int* device, int* K, int* R, int* B, int* P, int* nact,
-                            int* ncu);
+#include "scan_select.h"
 
 namespace {
 
-constexpr int NT = 256;          // threads per workgroup of every scan kernel
+using namespace scan_select;
+
 constexpr int SCAN_MAX_N = 4096; // documented cap of N (include/mmsbm.h)
-constexpr int FAN = 32;          // lists merged by one workgroup of scan_merge_kernel
 constexpr int SEED_STRIDE = 61;  // the seeding pass scans every 61st item (prime: spreads over a and b)
 constexpr int SEED_MIN_P = 200;  // below it one pass: the seeding launches would cost more than they save
-constexpr int LDS_MAX = 144 * 1024;
 constexpr int W_LDS_MAX = 64 * 1024;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return mmsbm_detail_fail(code, buf);
-}
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return fail(MMSBM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-typedef double d4v __attribute__((ext_vector_type(4)));
-
-// ------------------------------------------------------------------------------------------
-// Selection state of one workgroup (LDS) and its candidate buffer
-// ------------------------------------------------------------------------------------------
-struct Sel {
-  int count;        // entries in the buffer
-  int overflow;     // a wave's reservation did not fit: sort and keep the best N
-  double thr_s;     // the workgroup's N-th best (score, key); (-inf, max) until it has N
-  long long thr_k;
-  double gthr;      // the published bound as read at the item's start (-inf: none)
-  long long klo, khi;  // the item's first gene a: its known keys are known[klo, khi)
-  double pad[2];
-};
-static_assert(sizeof(Sel) == 64, "Sel is the first 64 bytes of the dynamic LDS");
-
-__device__ __forceinline__ double neg_inf() { return -__builtin_huge_val(); }
-
-// the total order: score descending, packed key ascending
-__device__ __forceinline__ bool before(double s1, long long k1, double s2, long long k2) {
-  return s1 > s2 || (s1 == s2 && k1 < k2);
-}
-
-__device__ __forceinline__ void sel_init(Sel* st) {
-  st->count = 0;
-  st->overflow = 0;
-  st->thr_s = neg_inf();
-  st->thr_k = LLONG_MAX;
-  st->gthr = neg_inf();
-  st->klo = st->khi = 0;
-}
-
-// Reserve n entries for this wave (lane 0, one LDS compare-exchange); -1: no room, nothing taken.
-__device__ __forceinline__ int wave_reserve(Sel* st, int n, int cap) {
-  int base = 0;
-  if ((threadIdx.x & 63) == 0) {
-    int old = __hip_atomic_load(&st->count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    for (;;) {
-      if (old + n > cap) {
-        old = -1;
-        __hip_atomic_store(&st->overflow, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        break;
-      }
-      if (__hip_atomic_compare_exchange_strong(&st->count, &old, old + n, __ATOMIC_RELAXED,
-                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-        break;
-    }
-    base = old;
-  }
-  return __shfl(base, 0, 64);
-}
-
-// Sort the buffer under the total order, keep the best N, raise the threshold.  Called by the
-// whole workgroup; begins and ends with a barrier.
-// Inlined, so that a buffer in LDS is sorted with LDS instructions (the address space is inferred).
-__device__ __forceinline__ void wg_keep_best(Sel* st, double* cs, long long* ck, int N,
-                                             unsigned long long* shared) {
-  __syncthreads();
-  const int cnt = st->count;
-  int sz = 1;
-  while (sz < cnt) sz <<= 1;
-  for (int i = cnt + threadIdx.x; i < sz; i += NT) {
-    cs[i] = neg_inf();
-    ck[i] = LLONG_MAX;
-  }
-  __syncthreads();
-  for (int k = 2; k <= sz; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < (sz >> 1); t += NT) {  // one compare-exchange per pair (i, i + j)
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), x = i | j;
-        const double si = cs[i], sx = cs[x];
-        const long long ki = ck[i], kx = ck[x];
-        const bool up = (i & k) == 0;
-        if (up ? before(sx, kx, si, ki) : before(si, ki, sx, kx)) {
-          cs[i] = sx;
-          ck[i] = kx;
-          cs[x] = si;
-          ck[x] = ki;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  if (threadIdx.x == 0) {
-    const int keep = cnt < N ? cnt : N;
-    st->count = keep;
-    st->overflow = 0;
-    if (keep == N) {
-      const double t = cs[N - 1];
-      st->thr_s = t;
-      st->thr_k = ck[N - 1];
-      if (shared && t > 0.0)
-        __hip_atomic_fetch_max(shared, (unsigned long long)__double_as_longlong(t), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  __syncthreads();
-}
 
 // ------------------------------------------------------------------------------------------
 // Prep: Th' k-major and zero-padded (thT[s][KP][P16]) and T_a (T[s][P][K][KP]) of every gene.
@@ -234,23 +103,6 @@ struct ScanArgs {
   int K, P, P16, ns, N, cap, WB, select;
   int stride;                 // 1: every item; > 1: the seeding pass over every stride-th item
 };
-
-// first index in known[lo, hi) whose key is not below `key`
-__device__ __forceinline__ long long lower_bound(const long long* __restrict__ known, long long lo,
-                                                 long long hi, long long key) {
-  while (lo < hi) {
-    const long long mid = (lo + hi) >> 1;
-    if (known[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ bool is_known(const long long* __restrict__ known, long long lo, long long hi,
-                                         long long key) {
-  const long long at = lower_bound(known, lo, hi, key);
-  return at < hi && known[at] == key;
-}
 
 template <int KS>
 __global__ __launch_bounds__(NT) void scan_kernel(ScanArgs A) {
@@ -433,43 +285,8 @@ __global__ __launch_bounds__(NT) void scan_merge_kernel(MergeArgs A) {
   long long* ck = reinterpret_cast<long long*>(cs + A.cap);
   if (threadIdx.x == 0) sel_init(st);
   __syncthreads();
-  const int lane = threadIdx.x & 63;
   const int l0 = blockIdx.x * FAN, l1 = min(l0 + FAN, A.n_in);
-  for (int l = l0; l < l1; ++l) {
-    const int cnt = min(A.in_n[l], A.N);
-    for (int base = 0; base < cnt; base += NT) {
-      const int i = base + threadIdx.x;
-      double s = 0.0;
-      long long k = 0;
-      bool pass = false;
-      if (i < cnt) {
-        s = A.in_s[(size_t)l * A.N + i];
-        k = A.in_k[(size_t)l * A.N + i];
-        pass = before(s, k, *(volatile double*)&st->thr_s, *(volatile long long*)&st->thr_k);
-      }
-      bool done = false;
-      for (;;) {
-        if (!done) {
-          const unsigned long long mk = __ballot(pass);
-          const int n = __popcll(mk);
-          int pos = n ? wave_reserve(st, n, A.cap) : 0;
-          if (pos >= 0) {
-            if (pass) {
-              pos += __popcll(mk & ((1ull << lane) - 1ull));
-              cs[pos] = s;
-              ck[pos] = k;
-            }
-            done = true;
-          }
-        }
-        __syncthreads();
-        const int full = st->overflow;
-        __syncthreads();  // everyone has read the flag before the next chunk can raise it
-        if (!full) break;
-        wg_keep_best(st, cs, ck, A.N, nullptr);
-      }
-    }
-  }
+  wg_merge_lists(st, cs, ck, A.in_s, A.in_k, A.in_n, l0, l1, A.N, A.cap);
   wg_keep_best(st, cs, ck, A.N, A.shared);  // seeding pass: publishes the subset's N-th score
   if (A.shared) return;
   const int cnt = st->count;
@@ -506,7 +323,6 @@ struct ScanPlan {
   size_t off_thT, off_T, off_cs, off_ck, off_ls[2], off_lk[2], off_ln[2], total;
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Everything that sizes the workspace follows the context's shape and N only (not the sample
 // argument), so one workspace serves every call of that shape.

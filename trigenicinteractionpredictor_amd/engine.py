@@ -63,6 +63,7 @@ class EMEngine:
         self.workspace = None
         self._scan_ws = None      # scan_top's scratch and rank order (built on first use)
         self._scan_order = None
+        self._partners_ws = None  # partners_top's scratch
         self.theta = torch.zeros((self.B, self.P, self.K), dtype=torch.float64, device=self.device)
         self.pr = torch.zeros((self.B, self.R, self.K3), dtype=torch.float64, device=self.device)
 
@@ -233,6 +234,62 @@ class EMEngine:
             stream.synchronize()
         m = int(count.cpu()[0])
         return scores[:m].cpu().numpy(), ids[:m].cpu().numpy()
+
+    def partners_top_async(self, queries, n: int, known=None, sample: int = None, stream=None):
+        """partners_top without the host copy: -> device tensors (scores f64[Q][n],
+        ids int32[Q][n][3], counts int64[Q]); row i answers queries[i], its rows from counts[i] on
+        are NaN / -1.  Nothing synchronises."""
+        from .scan import rank_order
+        n = int(n)
+        queries = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+        Q = int(queries.size)
+        off = pairs = None
+        if known is not None:
+            off = np.ascontiguousarray(known[0], dtype=np.int64).reshape(-1)
+            pairs = np.ascontiguousarray(known[1], dtype=np.int64).reshape(-1)
+            if off.size != Q + 1 or off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > pairs.size:
+                raise ValueError("known offsets must be %d non-decreasing indices into the pair keys "
+                                 "(scan.partner_known)" % (Q + 1))
+            rising = pairs[1:] > pairs[:-1]
+            starts = off[1:-1]
+            rising[starts[(starts > 0) & (starts < pairs.size)] - 1] = True   # a new query's slice
+            if not rising[int(off[0]):max(int(off[-1]) - 1, int(off[0]))].all():
+                raise ValueError("each query's known pair keys must be sorted and unique "
+                                 "(scan.partner_known)")
+        if sample is not None and not 0 <= int(sample) < self.active:
+            raise ValueError("sample %r outside the active prefix [0, %d)" % (sample, self.active))
+        nbytes = ctypes.c_int64()
+        _lib.check(self.lib.mmsbm_partners_workspace_bytes(self.ctx, Q, n, ctypes.byref(nbytes)))
+        if self._partners_ws is None or self._partners_ws.numel() < nbytes.value:
+            self._partners_ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        if self._scan_order is None:
+            self._scan_order = torch.from_numpy(rank_order(max(self.P, 1))).to(self.device)
+        off_d = pairs_d = None
+        if off is not None:
+            off_d = torch.from_numpy(off).to(self.device)
+            pairs_d = torch.from_numpy(pairs if pairs.size else np.zeros(1, np.int64)).to(self.device)
+        scores = torch.empty((Q, n), dtype=torch.float64, device=self.device)
+        ids = torch.empty((Q, n, 3), dtype=torch.int32, device=self.device)
+        counts = torch.empty(Q, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.mmsbm_partners_topn(
+            self.ctx, _ptr(self._scan_order), _host_ptr(queries), Q,
+            _ptr(off_d) if off_d is not None else None, _ptr(pairs_d) if pairs_d is not None else None,
+            _ptr(self.theta), _ptr(self.pr), -1 if sample is None else int(sample), n,
+            _ptr(self._partners_ws), self._partners_ws.numel(), _ptr(scores), _ptr(ids), _ptr(counts),
+            self._stream(stream)))
+        return scores, ids, counts
+
+    def partners_top(self, queries, n: int, known=None, sample: int = None, stream=None):
+        """For each query gene id, its n most probable partner pairs (include/mmsbm.h
+        mmsbm_partners_topn): -> one (scores f64[n'], ids int32[n'][3]) pair per query on the host,
+        best first, n' <= n; an id row is the whole triple in key order, the query included.
+        known: (known_off, known_pairs) of scan.partner_known for these queries; sample: a slot of
+        the active prefix, or None for the mean over it."""
+        scores, ids, counts = self.partners_top_async(queries, n, known, sample, stream)
+        if stream is not None:
+            stream.synchronize()
+        counts, scores, ids = counts.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
+        return [(scores[i, :int(m)].copy(), ids[i, :int(m)].copy()) for i, m in enumerate(counts)]
 
     # ---------------------------------------------------------- measurement
     def kernels(self) -> dict:

@@ -426,6 +426,55 @@ class Model:
         return [[float(p), "_".join(str(int(g)) for g in row), sorted(self.id_gene[int(g)] for g in row)]
                 for p, row in zip(scores, ids)]
 
+    def _gene_arg(self, gene):
+        """A gene id or name as do_prediction takes them -> id in [0, P) (IndexError like :537)."""
+        try:
+            g = int(gene)
+        except ValueError:
+            g = self.gene_id[gene]
+        if not -self.P <= g < self.P:
+            raise IndexError("list index out of range")
+        return g % self.P
+
+    def _rows(self, scores, ids):
+        return [[float(p), "_".join(str(int(g)) for g in row), sorted(self.id_gene[int(g)] for g in row)]
+                for p, row in zip(scores, ids)]
+
+    def predict_partners(self, gene, n, exclude=("train", "test")):
+        """The n most probable triples that contain `gene` (an id or a name) and two other, distinct
+        genes, outside the `exclude`d link tables, best first; rows shaped like predict_novel's:
+        [probability, "i_j_k", [name1, name2, name3]], the gene included in the key.  One partner
+        scan of its (P - 1)(P - 2) / 2 pairs on the GPU (engine.partners_top)."""
+        from .scan import partner_known
+        g = self._gene_arg(gene)
+        eng = self._push()
+        (scores, ids), = eng.partners_top([g], int(n), partner_known(self, [g], exclude), sample=0)
+        return self._rows(scores, ids)
+
+    def predict_third(self, gene1, gene2, n, exclude=("train", "test")):
+        """The n most probable third genes of the pair (gene1, gene2), best first, rows as
+        predict_partners gives them.  The P - 2 listed triples go through the predict kernel and a
+        host sort under the scan's order (probability descending, equal ones by packed key)."""
+        from .scan import pack_keys, parse_exclude, rank_of, rank_order
+        g1, g2 = self._gene_arg(gene1), self._gene_arg(gene2)
+        if g1 == g2:
+            raise ValueError("predict_third needs two different genes")
+        order = rank_order(self.P)
+        rank = rank_of(order)
+        third = np.array([g for g in range(self.P) if g != g1 and g != g2], dtype=np.int64)
+        pos = np.sort(np.stack([np.full(third.size, rank[g1]), np.full(third.size, rank[g2]), rank[third]],
+                               axis=1), axis=1)
+        ids = order[pos].astype(np.int32)                      # key order: slots 1, 2, 3
+        tables = [self.links if name == "train" else self.test_links for name in parse_exclude(exclude)]
+        keep = np.array([not any("_".join(str(int(g)) for g in row) in t for t in tables) for row in ids],
+                        dtype=bool)
+        ids = ids[keep]
+        if not ids.shape[0]:
+            return []
+        scores = self._push().predict(ids)[0]
+        top = np.lexsort((pack_keys(ids, rank, self.P), -scores))[:int(n)]
+        return self._rows(scores[top], ids[top])
+
     def calculate_test_set_results(self):
         tids, _ = self._link_arrays(1)
         keys = list(self.test_links.keys())

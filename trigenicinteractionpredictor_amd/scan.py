@@ -15,6 +15,11 @@ fits the -n restarts as one batch for -i iterations (the initial states come fro
 `random` stream as `Model.initialize_parameters`, seeded once), scans once (the ensemble mean, or
 with --best the restart of the highest train likelihood) and writes a TSV with the columns
 rank, probability, ids, names.
+
+With --gene NAME_OR_ID (repeatable, or a comma list; a name or an id as `do_prediction` takes them)
+or --all-genes the driver asks the per-gene question instead (`EMEngine.partners_top`,
+mmsbm_partners_topn): for each query gene its --top most probable partner pairs, as a TSV with the
+columns query, rank, probability, ids, names, in query order and then by rank.
 """
 from __future__ import annotations
 
@@ -26,6 +31,7 @@ import numpy as np
 
 SETS = ("train", "test")
 MAX_TOP = 4096   # mmsbm_scan_max_n() (include/mmsbm.h): the largest N one scan returns
+MAX_PARTNER_TOP = 1024   # mmsbm_partners_max_n(): the largest N per query gene
 
 
 def rank_order(P: int) -> np.ndarray:
@@ -83,6 +89,51 @@ def known_keys(source, exclude=SETS) -> np.ndarray:
     return np.unique(pack_keys(ids[distinct], rank_of(rank_order(P)), P))
 
 
+def partner_known(source, queries, exclude=SETS):
+    """The measured partner pairs of each query gene, as mmsbm_partners_topn takes them:
+    -> (known_off int64[Q + 1], known_pairs int64[known_off[Q]]), query i's slice holding the
+    sorted, unique keys b P + c (rank positions b < c of the other two genes) of the measured
+    triples of distinct genes that contain queries[i].  `source` is a Model or
+    (P, train_ids, test_ids); `queries` are gene ids in [0, P) (IndexError otherwise)."""
+    exclude = parse_exclude(exclude)
+    P, tables = _id_tables(source, exclude)
+    queries = np.asarray(queries, dtype=np.int64).reshape(-1)
+    if queries.size and (queries.min() < 0 or queries.max() >= P):
+        raise IndexError("query gene id outside [0, %d)" % P)
+    off = np.zeros(queries.size + 1, dtype=np.int64)
+    if not tables or not queries.size:
+        return off, np.zeros(0, dtype=np.int64)
+    ids = np.concatenate(tables, axis=0)
+    distinct = (ids[:, 0] != ids[:, 1]) & (ids[:, 1] != ids[:, 2]) & (ids[:, 0] != ids[:, 2])
+    rank = rank_of(rank_order(P))
+    pos = np.sort(rank[ids[distinct]], axis=1)
+    a, b, c = pos[:, 0], pos[:, 1], pos[:, 2]
+    # one (gene, pair of the other two) entry per slot of every triple, sorted by gene then pair
+    both = np.unique(np.concatenate([a, b, c]) * (P * P) + np.concatenate([b * P + c, a * P + c, a * P + b]))
+    who, pair = both // (P * P), both % (P * P)
+    start = np.searchsorted(who, np.arange(P + 1))
+    qpos = rank[queries]
+    off[1:] = np.cumsum(start[qpos + 1] - start[qpos])
+    pairs = np.concatenate([pair[start[q]:start[q + 1]] for q in qpos])
+    return off, pairs.astype(np.int64)
+
+
+def resolve_genes(model, names):
+    """Gene names or ids, as Model.do_prediction takes them, -> gene ids in [0, P): a token that
+    reads as an integer is an id, anything else a name of the fold.  KeyError on an unknown name,
+    IndexError on an id outside the table."""
+    out = []
+    for name in names:
+        try:
+            g = int(name)
+        except ValueError:
+            g = model.gene_id[name]
+        if not 0 <= g < model.P:
+            raise IndexError("gene id %d outside [0, %d)" % (g, model.P))
+        out.append(g)
+    return out
+
+
 # ------------------------------------------------------------------------------------- driver
 USAGE = """
 Usage:
@@ -90,6 +141,8 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [-e|--test=] <test file> [-k|--k=] <number of groups> [-n|--num_samples=] <restarts>
     [-i|--num_iterations=] <EM iterations> [--seed=] <RNG seed> [--top=] <rows, default 100>
     [--exclude=] <train,test (default) | train | test | none> [--best] [-o|--out=] <TSV file>
+    [--gene=] <gene name or id: its best partner pairs instead; repeatable, or a comma list>
+    [--all-genes] <the best partner pairs of every gene>
 """
 
 
@@ -98,11 +151,11 @@ def parse(argv):
     and -i are validated by cli.parse."""
     from . import cli
     cfg = dict(cli.DEFAULTS, samples=1, iterations=100, top=100, exclude=SETS, best=False, out=None,
-               seed=None)
+               seed=None, genes=[], all_genes=False)
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
-                                                        "best", "out="])
+                                                        "best", "out=", "gene=", "all-genes"])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -125,6 +178,14 @@ def parse(argv):
                     raise cli.ArgError()
             elif opt == "--best":
                 cfg["best"] = True
+            elif opt == "--gene":
+                names = [t.strip() for t in arg.split(",")]
+                if not all(names):
+                    print("\n\nERROR: --gene needs a gene name or id")
+                    raise cli.ArgError()
+                cfg["genes"] = cfg["genes"] + names
+            elif opt == "--all-genes":
+                cfg["all_genes"] = True
             elif opt == "--seed":
                 cfg["seed"] = int(arg)
             elif opt in ("-o", "--out"):
@@ -133,17 +194,39 @@ def parse(argv):
                 cfg = cli.parse([opt, arg], cfg)
         except ValueError:
             raise cli.ArgError()
+    if cfg["genes"] and cfg["all_genes"]:
+        print("\n\nERROR: --gene and --all-genes exclude each other")
+        raise cli.ArgError()
+    if (cfg["genes"] or cfg["all_genes"]) and cfg["top"] > MAX_PARTNER_TOP:
+        print("\n\nERROR: with --gene / --all-genes --top should be in [1, %d]" % MAX_PARTNER_TOP)
+        raise cli.ArgError()
     return cfg
 
 
+def partner_queries(model, cfg):
+    """The driver's query gene ids (None: the genome-wide scan); cli.ArgError on a bad gene."""
+    from . import cli
+    if cfg.get("all_genes"):
+        return list(range(model.P))
+    if not cfg.get("genes"):
+        return None
+    try:
+        return resolve_genes(model, cfg["genes"])
+    except (KeyError, IndexError) as e:
+        print("\n\nERROR: --gene: unknown gene %s" % (e,))
+        raise cli.ArgError()
+
+
 def run(cfg, out=print):
-    """Fit the restarts as one batch, scan once, return the rows [rank, probability, ids, names]."""
-    from . import _lib
-    from .engine import EMEngine
+    """Fit the restarts as one batch, scan once, return the rows [rank, probability, ids, names]
+    (with --gene / --all-genes: [query, rank, probability, ids, names], by query then rank)."""
     from .model import Model
-    from .restarts import stream_states
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
+    queries = partner_queries(model, cfg)     # before anything touches a GPU
+    from . import _lib
+    from .engine import EMEngine
+    from .restarts import stream_states
     K, B = cfg["k"], cfg["samples"]
     if cfg["seed"] is not None:
         random.seed(cfg["seed"])
@@ -153,6 +236,14 @@ def run(cfg, out=print):
         eng.upload_slot(b, theta, pr)
     eng.iterate(cfg["iterations"])
     sample = int(np.argmax(eng.loglik(_lib.SET_TRAIN))) if cfg["best"] else None
+    if queries is not None:
+        out("partner pairs of %d genes: %s" % (len(queries), "sample %d" % sample if sample is not None
+                                               else "mean of %d samples" % B))
+        lists = eng.partners_top(queries, cfg["top"], partner_known(model, queries, cfg["exclude"]), sample)
+        eng.close()
+        return [[model.id_gene[g], i + 1, float(p), "_".join(str(x) for x in row),
+                 sorted(model.id_gene[int(x)] for x in row)]
+                for g, (scores, ids) in zip(queries, lists) for i, (p, row) in enumerate(zip(scores, ids))]
     out("scanning %d genes: %s" % (model.P, "sample %d" % sample if sample is not None
                                    else "mean of %d samples" % B))
     scores, ids = eng.scan_top(cfg["top"], known_keys(model, cfg["exclude"]), sample)
@@ -161,7 +252,12 @@ def run(cfg, out=print):
             for i, (p, row) in enumerate(zip(scores, ids))]
 
 
-def write_tsv(rows, stream):
+def write_tsv(rows, stream, partners=False):
+    if partners:
+        stream.write("query\trank\tprobability\tids\tnames\n")
+        for query, rank, p, key, names in rows:
+            stream.write("%s\t%d\t%r\t%s\t%s\n" % (query, rank, p, key, "_".join(names)))
+        return
     stream.write("rank\tprobability\tids\tnames\n")
     for rank, p, key, names in rows:
         stream.write("%d\t%r\t%s\t%s\n" % (rank, p, key, "_".join(names)))
@@ -175,12 +271,16 @@ def main(argv=None, out=print):
         return 2
     if cfg.get("help"):
         return 0
-    rows = run(cfg, out)
+    try:
+        rows = run(cfg, out)
+    except cli.ArgError:
+        return 2
+    partners = bool(cfg["genes"] or cfg["all_genes"])
     if cfg["out"]:
         with open(cfg["out"], "w", encoding="utf-8") as f:
-            write_tsv(rows, f)
+            write_tsv(rows, f, partners)
     else:
-        write_tsv(rows, sys.stdout)
+        write_tsv(rows, sys.stdout, partners)
     return 0
 
 
