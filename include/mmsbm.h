@@ -197,6 +197,34 @@ int mmsbm_partners_topn(mmsbm_ctx *ctx, const int32_t *order, const int32_t *que
                         const double *pr, int32_t sample, int32_t N, void *ws, int64_t ws_bytes,
                         double *out_scores, int32_t *out_ids, int64_t *out_count, void *stream);
 
+/* Score census: for M thresholds, the exact number of the scan's eligible triples whose score is at
+ * or above each, and the number of eligible triples.  order, known, n_known, theta, pr, sample
+ * (-1: the mean over the active prefix), ws and stream mean what they mean for mmsbm_scan_topn, and
+ * a triple is eligible exactly as there: rank positions a < b < c < P whose packed key is not among
+ * `known`.  A score carries the same bits as in mmsbm_scan_topn (one score phase serves both), so
+ * a census at the scores of a scan list returns each entry's position in that list.
+ * thresholds f64[M] (device): finite and non-decreasing (the caller guarantees both; duplicates are
+ * fine), 0 <= M <= mmsbm_census_max_m() (1024); above it MMSBM_ERR_UNSUPPORTED, as for K outside
+ * [1, MMSBM_MAX_K] and for an ensemble whose W tile exceeds the LDS (as for the scan).  Null
+ * pointers, a bad sample or a small workspace: MMSBM_ERR_INVALID.
+ * Result (device) out_counts int64[M + 1]: out_counts[m], m < M = the eligible triples with
+ * score >= thresholds[m]; out_counts[M] = the eligible triples in all (counted by the kernel; P < 3:
+ * every count is 0).  The counts are integers combined by integer adds only (LDS and 64-bit global
+ * atomics, then suffix sums); no floating-point value is summed across lanes or workgroups, so they
+ * do not depend on the grid, the batch the sample sits in or the arrival order.  A count is at most
+ * C(P, 3) < 2^63.
+ * ws: mmsbm_census_workspace_bytes(ctx, M) bytes of device scratch, 16-byte aligned, the caller's;
+ * its size follows the context's shape and M only (a workspace for M serves every smaller M).
+ * theta, pr and thresholds are only read; all launches go to `stream` and nothing synchronises.
+ * The environment variable MMSBM_CENSUS_GRID=<workgroups> overrides the grid (measurement; the
+ * counts do not depend on it).  Needs R >= 2.  Replaces nothing in the reference. */
+int mmsbm_census_max_m(void);
+int mmsbm_census_workspace_bytes(const mmsbm_ctx *ctx, int32_t M, int64_t *bytes);
+int mmsbm_scan_census(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known, int64_t n_known,
+                      const double *theta, const double *pr, int32_t sample,
+                      const double *thresholds, int32_t M, void *ws, int64_t ws_bytes,
+                      int64_t *out_counts, void *stream);
+
 /* Link-sharded iteration (single sample over N ranks): each rank's context
  * holds 1/N of the train links (mmsbm_set_links) and the GLOBAL degree (mmsbm_set_degree).
  * Step 1, the accumulation half of make_iteration (:986-1012) over this rank's links:

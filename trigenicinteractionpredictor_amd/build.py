@@ -16,7 +16,8 @@ SRC = os.path.join(PKG, "csrc", "mmsbm.hip")           # triplet engine (include
 SRC_PAIRS = os.path.join(PKG, "csrc", "pairs.hip")     # joint model pair lattice (mmsbm_pairs.h)
 SRC_SCAN = os.path.join(PKG, "csrc", "scan.hip")       # genome-wide top-N scan (mmsbm_scan_*)
 SRC_PARTNERS = os.path.join(PKG, "csrc", "partners.hip")   # per-gene partner scan (mmsbm_partners_*)
-SRCS = [SRC, SRC_PAIRS, SRC_SCAN, SRC_PARTNERS]
+SRC_CENSUS = os.path.join(PKG, "csrc", "census.hip")   # score census (mmsbm_census_*, mmsbm_scan_census)
+SRCS = [SRC, SRC_PAIRS, SRC_SCAN, SRC_PARTNERS, SRC_CENSUS]
 INCLUDE = os.path.join(REPO, "include")
 OUT_DIR = os.path.join(PKG, "_build")
 LIB = os.path.join(OUT_DIR, "libmmsbm.so")
@@ -27,8 +28,11 @@ DEPS = {
     SRC: [os.path.join(PKG, "csrc", "plan.h"), os.path.join(PKG, "csrc", "sk.h"),
           os.path.join(INCLUDE, "mmsbm.h")],
     SRC_PAIRS: [os.path.join(INCLUDE, "mmsbm.h"), os.path.join(INCLUDE, "mmsbm_pairs.h")],
-    SRC_SCAN: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(INCLUDE, "mmsbm.h")],
+    SRC_SCAN: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
+               os.path.join(INCLUDE, "mmsbm.h")],
     SRC_PARTNERS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(INCLUDE, "mmsbm.h")],
+    SRC_CENSUS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
+                 os.path.join(INCLUDE, "mmsbm.h")],
 }
 
 

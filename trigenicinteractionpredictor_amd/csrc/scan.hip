@@ -32,7 +32,9 @@
 // with the same buffer and order.  The exact top N under a total order is unique: the result does
 // not depend on the grid, the arrival order or the batch.  Scores are never combined by atomics
 // and every sum has a fixed order.  The selection machinery (order, buffer, keep-best-N, merge) is
-// scan_select.h, shared with the partner scan (partners.hip).
+// scan_select.h, shared with the partner scan (partners.hip); the score phase (prep, W rows, the
+// MFMA chain of a tile, the ensemble's sum and division) is scan_score.h, shared with the score
+// census (census.hip), whose scores therefore carry this kernel's bits.
 
 #include <hip/hip_runtime.h>
 
@@ -42,49 +44,20 @@
 #include <cstdlib>
 
 #include "mmsbm.h"
+#include "scan_score.h"
 #include "scan_select.h"
 
 namespace {
 
 using namespace scan_select;
+using scan_score::pick_wb;
+using scan_score::scan_prep_kernel;
+using scan_score::Score;
+using scan_score::W_LDS_MAX;
 
 constexpr int SCAN_MAX_N = 4096; // documented cap of N (include/mmsbm.h)
 constexpr int SEED_STRIDE = 61;  // the seeding pass scans every 61st item (prime: spreads over a and b)
 constexpr int SEED_MIN_P = 200;  // below it one pass: the seeding launches would cost more than they save
-constexpr int W_LDS_MAX = 64 * 1024;
-
-// ------------------------------------------------------------------------------------------
-// Prep: Th' k-major and zero-padded (thT[s][KP][P16]) and T_a (T[s][P][K][KP]) of every gene.
-// grid (P16, samples).
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT) void scan_prep_kernel(const int* __restrict__ order,
-                                                       const double* __restrict__ theta,
-                                                       const double* __restrict__ pr,
-                                                       double* __restrict__ thT, double* __restrict__ T,
-                                                       int K, int KP, int R, int P, int P16, int s0) {
-  __shared__ double th[MMSBM_MAX_K];
-  const int a = blockIdx.x, s = blockIdx.y;
-  const size_t K2 = (size_t)K * K, K3 = K2 * K;
-  int g = a < P ? order[a] : -1;
-  if (g < 0 || g >= P) g = -1;  // outside the table: a zero row (the binding checks the permutation)
-  const double* __restrict__ row = theta + ((size_t)(s0 + s) * P + (g < 0 ? 0 : g)) * K;
-  if (threadIdx.x < KP) {
-    const double v = (g >= 0 && (int)threadIdx.x < K) ? row[threadIdx.x] : 0.0;
-    if ((int)threadIdx.x < K) th[threadIdx.x] = v;
-    thT[((size_t)s * KP + threadIdx.x) * P16 + a] = v;
-  }
-  __syncthreads();
-  if (a >= P) return;
-  const double* __restrict__ p1 = pr + ((size_t)(s0 + s) * R + 1) * K3;
-  double* __restrict__ Ta = T + ((size_t)s * P + a) * K * KP;
-  for (int idx = threadIdx.x; idx < K * KP; idx += NT) {
-    const int y = idx / KP, z = idx % KP;
-    double v = 0.0;
-    if (z < K)
-      for (int x = 0; x < K; ++x) v = fma(th[x], p1[x * K2 + y * K + z], v);
-    Ta[idx] = v;
-  }
-}
 
 // ------------------------------------------------------------------------------------------
 // Scan
@@ -106,7 +79,8 @@ struct ScanArgs {
 
 template <int KS>
 __global__ __launch_bounds__(NT) void scan_kernel(ScanArgs A) {
-  constexpr int KP = 4 * KS, WS = KP + 2;  // W row stride: conflict-free A-operand reads
+  using Sc = Score<KS>;  // the score phase (scan_score.h)
+  constexpr int WS = Sc::WS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Sel* st = reinterpret_cast<Sel*>(smem);
   double* W = reinterpret_cast<double*>(smem + sizeof(Sel));
@@ -148,27 +122,13 @@ __global__ __launch_bounds__(NT) void scan_kernel(ScanArgs A) {
       st->klo = lower_bound(A.known, 0, A.n_known, (long long)a * PP * PP);
       st->khi = lower_bound(A.known, st->klo, A.n_known, (long long)(a + 1) * PP * PP);
     }
-    // W_a of the item's rows, every sample
-    for (int idx = threadIdx.x; idx < ns * RB * KP; idx += NT) {
-      const int z = idx % KP, r = (idx / KP) % RB, s = idx / (KP * RB);
-      const int rowb = bq * RB + r;
-      double v = 0.0;
-      if (rowb < P) {
-        const double* __restrict__ Ta = A.T + ((size_t)s * P + a) * K * KP + z;
-        const double* __restrict__ tb = A.thT + (size_t)s * KP * P16 + rowb;
-        for (int y = 0; y < K; ++y) v = fma(tb[(size_t)y * P16], Ta[y * KP], v);
-      }
-      W[((size_t)s * RB + r) * WS + z] = v;
-    }
+    Sc::fill_w(W, A.T, A.thT, a, bq, RB, ns, K, P, P16);  // W_a of the item's rows, every sample
     __syncthreads();
 
     const int btile = bq * A.WB + wb, b0 = btile * 16;
     const bool wave_on = b0 < P - 1 && b0 + 15 > a;
     double areg[KS];
-    if (wave_on && ns == 1) {
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) areg[ks] = W[(size_t)(wb * 16 + m) * WS + 4 * ks + kk];
-    }
+    if (wave_on && ns == 1) Sc::load_a(areg, W, wb, m, kk);
     int ct = bq * A.WB + wc;
     while (ct < btile) ct += CW;  // every c of those tiles is below every b
     const long long klo = st->klo, khi = st->khi;
@@ -179,37 +139,18 @@ __global__ __launch_bounds__(NT) void scan_kernel(ScanArgs A) {
       const double cut = fmax(thr_s, gthr);
       if (wave_on) {
         double bnext[KS];  // single sample: the next tile's Th' operand is in flight
-        if (ns == 1 && ct < nct) {
-          const double* __restrict__ tc = A.thT + (size_t)kk * P16 + ct * 16 + m;
-#pragma unroll
-          for (int ks = 0; ks < KS; ++ks) bnext[ks] = tc[(size_t)(4 * ks) * P16];
-        }
+        if (ns == 1 && ct < nct) Sc::load_b(bnext, A.thT, P16, ct * 16, m, kk);
         for (; ct < nct; ct += CW) {
           const int c0 = ct * 16;
-          d4v tot = {0.0, 0.0, 0.0, 0.0};
+          d4v tot;
           if (ns == 1) {
             double bcur[KS];
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) bcur[ks] = bnext[ks];
-            if (ct + CW < nct) {
-              const double* __restrict__ tc = A.thT + (size_t)kk * P16 + c0 + 16 * CW + m;
-#pragma unroll
-              for (int ks = 0; ks < KS; ++ks) bnext[ks] = tc[(size_t)(4 * ks) * P16];
-            }
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-              tot = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ks], bcur[ks], tot, 0, 0, 0);
+            if (ct + CW < nct) Sc::load_b(bnext, A.thT, P16, c0 + 16 * CW, m, kk);
+            tot = Sc::tile_one(areg, bcur);
           } else {
-            for (int s = 0; s < ns; ++s) {
-              const double* __restrict__ tc = A.thT + ((size_t)s * KP + kk) * P16 + c0 + m;
-              const double* wr = W + ((size_t)s * RB + wb * 16 + m) * WS + kk;
-              d4v acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-              for (int ks = 0; ks < KS; ++ks)
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[4 * ks], tc[(size_t)(4 * ks) * P16], acc, 0, 0, 0);
-              tot = s == 0 ? acc : tot + acc;  // samples added in slot order
-            }
-            tot = tot / inv_div;
+            tot = Sc::tile_mean(W, A.thT, ns, RB, P16, wb, c0, m, kk, inv_div);
           }
           if (!A.select) continue;
           // lane holds S[b0 + kk + 4 i][c0 + m].  First the score alone against the larger of the
@@ -400,10 +341,8 @@ int mmsbm_scan_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, in
   if (!ws || ws_bytes < (int64_t)p.total || ((uintptr_t)ws & 15))
     return fail(MMSBM_ERR_INVALID, "scan workspace missing, misaligned or too small (mmsbm_scan_workspace_bytes)");
   const int ns = sample >= 0 ? 1 : p.nact, s0 = sample >= 0 ? sample : 0;
-  const int WS = p.KP + 2;
-  int WB = 4;
-  while (WB > 1 && (size_t)ns * 16 * WB * WS * sizeof(double) > (size_t)W_LDS_MAX) WB >>= 1;
-  const size_t w_bytes = (size_t)ns * 16 * WB * WS * sizeof(double);
+  size_t w_bytes = 0;
+  const int WB = pick_wb(ns, p.KP, &w_bytes);
   if (w_bytes > (size_t)W_LDS_MAX)
     return fail(MMSBM_ERR_UNSUPPORTED, "an ensemble of %d samples at K=%d exceeds the scan's LDS tile: scan the samples one by one",
                 ns, p.K);

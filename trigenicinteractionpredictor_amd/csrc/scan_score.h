@@ -1,0 +1,128 @@
+// scan_score.h — the score phase shared by the genome-wide scan (scan.hip) and the score census
+// (census.hip): the prep kernel (Th' k-major, T_a of every gene), a work item's W rows in LDS, the
+// MFMA chain of one 16 x 16 tile and the ensemble's slot-order sum and division.  Both kernels form
+// a score through these functions and nothing else, so a triple's score carries the same bits in
+// either: the census at the scores of a scan list returns each entry's position in that list.
+//
+// Notation (scan.hip): Th' = theta in rank order, T_a[y][z] = sum_x Th'[a][x] p_1[x][y][z],
+// W_a[b][z] = sum_y Th'[b][y] T_a[y][z], S_a[b][c] = sum_z W_a[b][z] Th'[c][z].  A work item is
+// (a, a block of 16 WB rows b); wave w of the 4 holds b-tile w % WB and the c-tiles w / WB + i 4 / WB.
+#ifndef MMSBM_SCAN_SCORE_H
+#define MMSBM_SCAN_SCORE_H
+
+#include "scan_select.h"
+
+namespace scan_score {
+
+using scan_select::d4v;
+using scan_select::NT;
+
+constexpr int W_LDS_MAX = 64 * 1024;  // the W rows of one item, every sample
+
+// ------------------------------------------------------------------------------------------
+// Prep: Th' k-major and zero-padded (thT[s][KP][P16]) and T_a (T[s][P][K][KP]) of every gene.
+// grid (P16, samples).
+// ------------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(NT) void scan_prep_kernel(const int* __restrict__ order,
+                                                              const double* __restrict__ theta,
+                                                              const double* __restrict__ pr,
+                                                              double* __restrict__ thT, double* __restrict__ T,
+                                                              int K, int KP, int R, int P, int P16, int s0) {
+  __shared__ double th[MMSBM_MAX_K];
+  const int a = blockIdx.x, s = blockIdx.y;
+  const size_t K2 = (size_t)K * K, K3 = K2 * K;
+  int g = a < P ? order[a] : -1;
+  if (g < 0 || g >= P) g = -1;  // outside the table: a zero row (the binding checks the permutation)
+  const double* __restrict__ row = theta + ((size_t)(s0 + s) * P + (g < 0 ? 0 : g)) * K;
+  if (threadIdx.x < KP) {
+    const double v = (g >= 0 && (int)threadIdx.x < K) ? row[threadIdx.x] : 0.0;
+    if ((int)threadIdx.x < K) th[threadIdx.x] = v;
+    thT[((size_t)s * KP + threadIdx.x) * P16 + a] = v;
+  }
+  __syncthreads();
+  if (a >= P) return;
+  const double* __restrict__ p1 = pr + ((size_t)(s0 + s) * R + 1) * K3;
+  double* __restrict__ Ta = T + ((size_t)s * P + a) * K * KP;
+  for (int idx = threadIdx.x; idx < K * KP; idx += NT) {
+    const int y = idx / KP, z = idx % KP;
+    double v = 0.0;
+    if (z < K)
+      for (int x = 0; x < K; ++x) v = fma(th[x], p1[x * K2 + y * K + z], v);
+    Ta[idx] = v;
+  }
+}
+
+// The widest row block (WB b-tiles of 16 rows, a power of two <= 4) whose W rows of `ns` samples fit
+// W_LDS_MAX; *w_bytes may still exceed it at WB = 1 (the caller reports the ensemble as unsupported).
+inline int pick_wb(int ns, int KP, size_t* w_bytes) {
+  const int WS = KP + 2;
+  int WB = 4;
+  while (WB > 1 && (size_t)ns * 16 * WB * WS * sizeof(double) > (size_t)W_LDS_MAX) WB >>= 1;
+  *w_bytes = (size_t)ns * 16 * WB * WS * sizeof(double);
+  return WB;
+}
+
+template <int KS>
+struct Score {
+  static constexpr int KP = 4 * KS, WS = KP + 2;  // W row stride: conflict-free A-operand reads
+
+  // W_a of the item's RB rows from bq RB on, every sample (the whole workgroup; barriers are the caller's)
+  static __device__ __forceinline__ void fill_w(double* W, const double* __restrict__ Tall,
+                                                const double* __restrict__ thT, int a, int bq, int RB,
+                                                int ns, int K, int P, int P16) {
+    for (int idx = threadIdx.x; idx < ns * RB * KP; idx += NT) {
+      const int z = idx % KP, r = (idx / KP) % RB, s = idx / (KP * RB);
+      const int rowb = bq * RB + r;
+      double v = 0.0;
+      if (rowb < P) {
+        const double* __restrict__ Ta = Tall + ((size_t)s * P + a) * K * KP + z;
+        const double* __restrict__ tb = thT + (size_t)s * KP * P16 + rowb;
+        for (int y = 0; y < K; ++y) v = fma(tb[(size_t)y * P16], Ta[y * KP], v);
+      }
+      W[((size_t)s * RB + r) * WS + z] = v;
+    }
+  }
+
+  // single sample: the wave's A operand (rows of b-tile wb) stays in registers for the whole item
+  static __device__ __forceinline__ void load_a(double (&areg)[KS], const double* W, int wb, int m, int kk) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) areg[ks] = W[(size_t)(wb * 16 + m) * WS + 4 * ks + kk];
+  }
+
+  // single sample: the Th' operand of the c-tile whose first column is c0
+  static __device__ __forceinline__ void load_b(double (&b)[KS], const double* __restrict__ thT, int P16,
+                                                int c0, int m, int kk) {
+    const double* __restrict__ tc = thT + (size_t)kk * P16 + c0 + m;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) b[ks] = tc[(size_t)(4 * ks) * P16];
+  }
+
+  // lane holds S[b0 + kk + 4 i][c0 + m] in element i
+  static __device__ __forceinline__ d4v tile_one(const double (&areg)[KS], const double (&b)[KS]) {
+    d4v tot = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) tot = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ks], b[ks], tot, 0, 0, 0);
+    return tot;
+  }
+
+  // the ensemble: each sample's tile accumulated from zero, the tiles added in slot order, then
+  // divided by the sample count
+  static __device__ __forceinline__ d4v tile_mean(const double* W, const double* __restrict__ thT, int ns,
+                                                  int RB, int P16, int wb, int c0, int m, int kk, double div) {
+    d4v tot = {0.0, 0.0, 0.0, 0.0};
+    for (int s = 0; s < ns; ++s) {
+      const double* __restrict__ tc = thT + ((size_t)s * KP + kk) * P16 + c0 + m;
+      const double* wr = W + ((size_t)s * RB + wb * 16 + m) * WS + kk;
+      d4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[4 * ks], tc[(size_t)(4 * ks) * P16], acc, 0, 0, 0);
+      tot = s == 0 ? acc : tot + acc;  // samples added in slot order
+    }
+    return tot / div;
+  }
+};
+
+}  // namespace scan_score
+
+#endif  // MMSBM_SCAN_SCORE_H

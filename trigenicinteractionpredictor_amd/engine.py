@@ -64,6 +64,7 @@ class EMEngine:
         self._scan_ws = None      # scan_top's scratch and rank order (built on first use)
         self._scan_order = None
         self._partners_ws = None  # partners_top's scratch
+        self._census_ws = None    # census's scratch
         self.theta = torch.zeros((self.B, self.P, self.K), dtype=torch.float64, device=self.device)
         self.pr = torch.zeros((self.B, self.R, self.K3), dtype=torch.float64, device=self.device)
 
@@ -290,6 +291,56 @@ class EMEngine:
             stream.synchronize()
         counts, scores, ids = counts.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
         return [(scores[i, :int(m)].copy(), ids[i, :int(m)].copy()) for i, m in enumerate(counts)]
+
+    def census_async(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None):
+        """census without the host copy: -> device tensors (counts int64[len(thresholds)] in the
+        caller's order, total int64[1]).  Nothing synchronises."""
+        from .scan import census_chunks, rank_order
+        max_m = int(self.lib.mmsbm_census_max_m())
+        chunks, perm = census_chunks(thresholds, max_m)      # ValueError on a NaN or infinite one
+        known = np.zeros(0, np.int64) if known is None else np.ascontiguousarray(known, dtype=np.int64)
+        if known.size > 1 and not (known[1:] > known[:-1]).all():
+            raise ValueError("known keys must be sorted and unique (scan.known_keys)")
+        if sample is not None and not 0 <= int(sample) < self.active:
+            raise ValueError("sample %r outside the active prefix [0, %d)" % (sample, self.active))
+        nbytes = ctypes.c_int64()
+        _lib.check(self.lib.mmsbm_census_workspace_bytes(self.ctx, max(c.size for c in chunks),
+                                                         ctypes.byref(nbytes)))
+        if self._census_ws is None or self._census_ws.numel() < nbytes.value:
+            self._census_ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        if self._scan_order is None:
+            self._scan_order = torch.from_numpy(rank_order(max(self.P, 1))).to(self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(s):      # the tensors below belong to the stream the kernels run on
+            known_d = torch.from_numpy(known).to(self.device)
+            outs = []
+            for chunk in chunks:
+                thr_d = torch.from_numpy(chunk if chunk.size else np.zeros(1)).to(self.device)
+                out = torch.empty(chunk.size + 1, dtype=torch.int64, device=self.device)
+                _lib.check(self.lib.mmsbm_scan_census(
+                    self.ctx, _ptr(self._scan_order), _ptr(known_d) if known.size else None, int(known.size),
+                    _ptr(self.theta), _ptr(self.pr), -1 if sample is None else int(sample), _ptr(thr_d),
+                    int(chunk.size), _ptr(self._census_ws), self._census_ws.numel(), _ptr(out), s.cuda_stream))
+                outs.append(out)
+            total = outs[-1][-1:]
+            if len(outs) == 1 and (perm == np.arange(perm.size)).all():
+                counts = outs[0][:-1]      # one call, thresholds already ascending: nothing to put back
+            else:            # sorted position i answers the caller's thresholds[perm[i]]
+                counts = torch.empty(perm.size, dtype=torch.int64, device=self.device)
+                counts[torch.from_numpy(perm).to(self.device)] = torch.cat([o[:-1] for o in outs])
+        return counts, total
+
+    def census(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None):
+        """The score census (include/mmsbm.h mmsbm_scan_census): -> (counts int64[len(thresholds)],
+        total int) on the host; counts[i] = the eligible triples (those scan_top ranks: distinct
+        genes, key not in `known`) whose score is >= thresholds[i], total = the eligible triples.
+        The thresholds may come in any order, with duplicates, in any number or none; a NaN or an
+        infinite one raises ValueError.  known, sample: as for scan_top.  The scores are scan_top's
+        bit for bit, so census(scan_top(n)[0]) numbers that list's entries."""
+        counts, total = self.census_async(thresholds, known, sample, stream)
+        if stream is not None:
+            stream.synchronize()
+        return counts.cpu().numpy(), int(total.cpu()[0])
 
     # ---------------------------------------------------------- measurement
     def kernels(self) -> dict:

@@ -475,6 +475,47 @@ class Model:
         top = np.lexsort((pack_keys(ids, rank, self.P), -scores))[:int(n)]
         return self._rows(scores[top], ids[top])
 
+    # ---------------------------------------------------------- score census
+    # Exactness: the counts are exact for the scan's score bits; a listed triple's probability comes
+    # from the predict kernel, which sums in another order, so a triple within rounding distance
+    # (about 1e-12 relative) of another triple's score may be placed on either side of it.
+    def novel_census(self, thresholds, exclude=("train", "test")):
+        """-> (counts int64[len(thresholds)], total): counts[i] = the triples of distinct genes
+        outside the `exclude`d link tables with P(r = 1) >= thresholds[i], total = all of them.
+        Stands to engine.census as predict_novel stands to scan_top: one pass over all C(P, 3)
+        triples on the GPU per 1024 thresholds."""
+        from .scan import known_keys
+        return self._push().census(thresholds, known_keys(self, exclude), sample=0)
+
+    def _ranked(self, ids, exclude):
+        from .scan import known_keys, ranks_of
+        return ranks_of(self._push(), ids, known_keys(self, exclude), sample=0)
+
+    def novel_rank(self, triples, exclude=("train", "test")):
+        """Where listed triples stand genome-wide: one row [rank, probability, "i_j_k"] per triple
+        (three gene ids or names each, as do_prediction takes them).  probability is
+        do_prediction's of the triple in key order, rank 1 + the number of triples of distinct genes outside the `exclude`d
+        tables that score strictly above it (a listed triple that is itself excluded gets the rank
+        it would have had), the key as `links` spells it (:349-358)."""
+        from .scan import rank_of, rank_order
+        order = rank_order(self.P)
+        rank = rank_of(order)
+        genes = np.array([[self._gene_arg(g) for g in t] for t in triples], dtype=np.int64).reshape(-1, 3)
+        ids = order[np.sort(rank[genes], axis=1)].astype(np.int32).reshape(-1, 3)   # key order
+        probs, ranks = self._ranked(ids, exclude)
+        return [[int(r), float(p), "_".join(str(int(g)) for g in row)] for r, p, row in zip(ranks, probs, ids)]
+
+    def heldout_ranks(self):
+        """The genome-wide rank of every test link among everything not trained on: one row
+        [rank, probability, key, real] per test link (real as in `results`), ordered by rank, equal
+        ranks by key.  Only the train links are excluded."""
+        from .scan import heldout_rows
+        ids, counts = self._link_arrays(1)
+        if not ids.shape[0]:
+            return []
+        probs, ranks = self._ranked(ids, ("train",))
+        return heldout_rows(ids, counts, probs, ranks)
+
     def calculate_test_set_results(self):
         tids, _ = self._link_arrays(1)
         keys = list(self.test_links.keys())

@@ -20,6 +20,23 @@ With --gene NAME_OR_ID (repeatable, or a comma list; a name or an id as `do_pred
 or --all-genes the driver asks the per-gene question instead (`EMEngine.partners_top`,
 mmsbm_partners_topn): for each query gene its --top most probable partner pairs, as a TSV with the
 columns query, rank, probability, ids, names, in query order and then by rank.
+
+Two more tables come from the score census (`EMEngine.census`, mmsbm_scan_census), each written
+next to the table above:
+    --census FILE          threshold, count, fraction rows: how many eligible triples (those the scan
+                           ranks under --exclude, scored by --best or the ensemble mean) have
+                           P(r = 1) >= threshold; fraction = count / total, the total in a header
+                           comment.  --thresholds LIST: a comma list of floats in (0, 1]; the default
+                           is DEFAULT_THRESHOLDS: 0.99 0.95 0.9 0.8 0.7 0.6 0.5 0.4 0.3 0.2 0.1 0.05
+                           0.02 0.01 0.005 0.002 0.001.  Rows go from the highest threshold down.
+    --heldout-ranks FILE   (needs -e) one rank, probability, ids, real row per test link: its
+                           genome-wide rank among every triple not trained on (1 + the number of
+                           those scoring strictly above it), ordered by rank, equal ranks by key.
+
+Exactness: the counts are exact for the scan's score bits.  A listed triple's probability comes from
+the predict kernel, which sums in another order, so a triple within rounding distance (about 1e-12
+relative) of another triple's score may be placed on either side of it.  (Listed triples are
+compared with each other by their probabilities and never with their own scan score.)
 """
 from __future__ import annotations
 
@@ -32,6 +49,9 @@ import numpy as np
 SETS = ("train", "test")
 MAX_TOP = 4096   # mmsbm_scan_max_n() (include/mmsbm.h): the largest N one scan returns
 MAX_PARTNER_TOP = 1024   # mmsbm_partners_max_n(): the largest N per query gene
+MAX_CENSUS_M = 1024      # mmsbm_census_max_m(): the most thresholds one census call takes
+DEFAULT_THRESHOLDS = (0.99, 0.95, 0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3, 0.2, 0.1, 0.05, 0.02, 0.01, 0.005,
+                      0.002, 0.001)   # --census without --thresholds
 
 
 def rank_order(P: int) -> np.ndarray:
@@ -118,6 +138,94 @@ def partner_known(source, queries, exclude=SETS):
     return off, pairs.astype(np.int64)
 
 
+# ------------------------------------------------------------------------------------- census
+def strict_thresholds(scores) -> np.ndarray:
+    """The next double above each score: a census at them counts the triples scoring STRICTLY
+    above each score (the census itself counts "at or above")."""
+    return np.nextafter(np.asarray(scores, dtype=np.float64), np.inf)
+
+
+def log_thresholds(lo: float, hi: float, n: int) -> np.ndarray:
+    """n log-spaced thresholds from hi down to lo, both included (n = 1: hi alone); ValueError
+    unless 0 < lo <= hi, both finite, and n >= 1."""
+    lo, hi, n = float(lo), float(hi), int(n)
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo <= hi) or n < 1:
+        raise ValueError("log_thresholds needs 0 < lo <= hi and n >= 1")
+    if n == 1:
+        return np.array([hi])
+    grid = np.geomspace(hi, lo, n)
+    grid[0], grid[-1] = hi, lo      # the ends exactly
+    return grid
+
+
+def census_chunks(thresholds, max_m: int = MAX_CENSUS_M):
+    """The binding's plan for any list of thresholds -> (chunks, perm): the thresholds sorted
+    ascending (stable) and cut into float64 arrays of at most max_m, one census call each (no
+    threshold: one empty chunk, the call that returns the total), and perm with
+    sorted[i] = thresholds[perm[i]].  ValueError on a NaN or infinite threshold."""
+    t = np.array(thresholds, dtype=np.float64).reshape(-1)
+    if not np.isfinite(t).all():
+        raise ValueError("census thresholds must be finite numbers")
+    perm = np.argsort(t, kind="stable")
+    ordered = np.ascontiguousarray(t[perm])
+    step = max(int(max_m), 1)
+    chunks = [ordered[i:i + step] for i in range(0, ordered.size, step)] or [ordered]
+    return chunks, perm
+
+
+def census_unsort(parts, perm) -> np.ndarray:
+    """The chunks' counts (each int64[len(chunk)], in chunk order) -> int64 counts in the caller's
+    order: out[perm[i]] = sorted count i."""
+    perm = np.asarray(perm, dtype=np.int64)
+    out = np.empty(perm.size, dtype=np.int64)
+    if perm.size:
+        out[perm] = np.concatenate([np.asarray(p, dtype=np.int64).reshape(-1) for p in parts])
+    return out
+
+
+def parse_thresholds(text):
+    """'0.5,0.1' -> [0.5, 0.1]; ValueError when a token does not parse, the list is empty or a
+    value lies outside (0, 1]."""
+    values = [float(t) for t in text.split(",")]     # '' -> ValueError
+    if not all(0.0 < v <= 1.0 for v in values):      # NaN fails the comparison
+        raise ValueError("threshold outside (0, 1]")
+    return values
+
+
+def ranks_of(eng, ids, known, sample=None):
+    """Listed triples ids int32[n][3] -> (probabilities f64[n] of the predict kernel for `sample`,
+    or the mean over the active prefix added in slot order; ranks int64[n]): rank = 1 + the number
+    of eligible triples (engine.census under `known`) scoring strictly above the probability.
+    The listed triples that are eligible themselves are taken out of the census and compared with
+    each other by their probabilities, so no triple is ever compared with its own scan score (whose
+    last bits may differ from the predict kernel's)."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1, 3)
+    known = np.zeros(0, np.int64) if known is None else np.asarray(known, dtype=np.int64)
+    probs = eng.predict(ids)
+    if sample is not None:
+        p = probs[int(sample)]
+    else:
+        p = probs[0]
+        for b in range(1, eng.active):
+            p = p + probs[b]
+        p = p / eng.active
+    keys = pack_keys(ids, rank_of(rank_order(eng.P)), eng.P)
+    own = (ids[:, 0] != ids[:, 1]) & (ids[:, 1] != ids[:, 2]) & (ids[:, 0] != ids[:, 2]) & ~np.isin(keys, known)
+    own_keys, first = np.unique(keys[own], return_index=True)      # a triple listed twice counts once
+    counts, _ = eng.census(strict_thresholds(p), np.union1d(known, own_keys), sample)
+    own_p = np.sort(p[own][first])
+    return p, counts + (own_p.size - np.searchsorted(own_p, p, side="right")) + 1
+
+
+def heldout_rows(ids, counts, probs, ranks):
+    """Test-link arrays and their ranks -> rows [rank, probability, "i_j_k", real] ordered by rank,
+    equal ranks by key; real as Model.results has it (0 when the link has a rating-0 count)."""
+    rows = [[int(r), float(p), "_".join(str(int(g)) for g in row), 0 if int(c[0]) else 1]
+            for r, p, row, c in zip(ranks, probs, ids, counts)]
+    rows.sort(key=lambda row: (row[0], row[2]))
+    return rows
+
+
 def resolve_genes(model, names):
     """Gene names or ids, as Model.do_prediction takes them, -> gene ids in [0, P): a token that
     reads as an integer is an id, anything else a name of the fold.  KeyError on an unknown name,
@@ -143,6 +251,9 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [--exclude=] <train,test (default) | train | test | none> [--best] [-o|--out=] <TSV file>
     [--gene=] <gene name or id: its best partner pairs instead; repeatable, or a comma list>
     [--all-genes] <the best partner pairs of every gene>
+    [--census=] <TSV file: counts of eligible triples at or above each threshold>
+    [--thresholds=] <comma list of floats in (0, 1]; default 0.99 ... 0.001>
+    [--heldout-ranks=] <TSV file: the genome-wide rank of every test link (needs -e)>
 """
 
 
@@ -151,11 +262,12 @@ def parse(argv):
     and -i are validated by cli.parse."""
     from . import cli
     cfg = dict(cli.DEFAULTS, samples=1, iterations=100, top=100, exclude=SETS, best=False, out=None,
-               seed=None, genes=[], all_genes=False)
+               seed=None, genes=[], all_genes=False, census=None, thresholds=None, heldout_ranks=None)
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
-                                                        "best", "out=", "gene=", "all-genes"])
+                                                        "best", "out=", "gene=", "all-genes", "census=",
+                                                        "thresholds=", "heldout-ranks="])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -186,6 +298,16 @@ def parse(argv):
                 cfg["genes"] = cfg["genes"] + names
             elif opt == "--all-genes":
                 cfg["all_genes"] = True
+            elif opt == "--census":
+                cfg["census"] = arg
+            elif opt == "--heldout-ranks":
+                cfg["heldout_ranks"] = arg
+            elif opt == "--thresholds":
+                try:
+                    cfg["thresholds"] = parse_thresholds(arg)
+                except ValueError:
+                    print("\n\nERROR: --thresholds should be a comma list of numbers in (0, 1]")
+                    raise cli.ArgError()
             elif opt == "--seed":
                 cfg["seed"] = int(arg)
             elif opt in ("-o", "--out"):
@@ -199,6 +321,9 @@ def parse(argv):
         raise cli.ArgError()
     if (cfg["genes"] or cfg["all_genes"]) and cfg["top"] > MAX_PARTNER_TOP:
         print("\n\nERROR: with --gene / --all-genes --top should be in [1, %d]" % MAX_PARTNER_TOP)
+        raise cli.ArgError()
+    if cfg["heldout_ranks"] and "-e" not in [o for o, _ in opts] and "--test" not in [o for o, _ in opts]:
+        print("\n\nERROR: --heldout-ranks needs a test file (-e)")
         raise cli.ArgError()
     return cfg
 
@@ -217,9 +342,23 @@ def partner_queries(model, cfg):
         raise cli.ArgError()
 
 
-def run(cfg, out=print):
+def census_tables(eng, model, cfg, sample, extras):
+    """The driver's --census and --heldout-ranks tables into `extras` (see run)."""
+    if cfg.get("census"):
+        thresholds = sorted(cfg.get("thresholds") or DEFAULT_THRESHOLDS, reverse=True)
+        counts, total = eng.census(thresholds, known_keys(model, cfg["exclude"]), sample)
+        extras["census"] = (thresholds, [int(c) for c in counts], total)
+    if cfg.get("heldout_ranks"):
+        ids, link_counts = model._link_arrays(1)
+        probs, ranks = ranks_of(eng, ids, known_keys(model, ("train",)), sample)
+        extras["heldout_ranks"] = heldout_rows(ids, link_counts, probs, ranks)
+
+
+def run(cfg, out=print, extras=None):
     """Fit the restarts as one batch, scan once, return the rows [rank, probability, ids, names]
-    (with --gene / --all-genes: [query, rank, probability, ids, names], by query then rank)."""
+    (with --gene / --all-genes: [query, rank, probability, ids, names], by query then rank).
+    extras: a dict that receives "census" = (thresholds, counts, total) and "heldout_ranks" = rows
+    when cfg asks for them (--census, --heldout-ranks)."""
     from .model import Model
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
@@ -236,6 +375,8 @@ def run(cfg, out=print):
         eng.upload_slot(b, theta, pr)
     eng.iterate(cfg["iterations"])
     sample = int(np.argmax(eng.loglik(_lib.SET_TRAIN))) if cfg["best"] else None
+    if extras is not None:
+        census_tables(eng, model, cfg, sample, extras)
     if queries is not None:
         out("partner pairs of %d genes: %s" % (len(queries), "sample %d" % sample if sample is not None
                                                else "mean of %d samples" % B))
@@ -263,6 +404,19 @@ def write_tsv(rows, stream, partners=False):
         stream.write("%d\t%r\t%s\t%s\n" % (rank, p, key, "_".join(names)))
 
 
+def write_census_tsv(thresholds, counts, total, stream):
+    stream.write("# total\t%d\n" % total)
+    stream.write("threshold\tcount\tfraction\n")
+    for t, c in zip(thresholds, counts):
+        stream.write("%r\t%d\t%r\n" % (float(t), int(c), (int(c) / total) if total else 0.0))
+
+
+def write_heldout_tsv(rows, stream):
+    stream.write("rank\tprobability\tids\treal\n")
+    for rank, p, key, real in rows:
+        stream.write("%d\t%r\t%s\t%d\n" % (rank, p, key, real))
+
+
 def main(argv=None, out=print):
     from . import cli
     try:
@@ -271,10 +425,17 @@ def main(argv=None, out=print):
         return 2
     if cfg.get("help"):
         return 0
+    extras = {}
     try:
-        rows = run(cfg, out)
+        rows = run(cfg, out, extras)
     except cli.ArgError:
         return 2
+    if "census" in extras:
+        with open(cfg["census"], "w", encoding="utf-8") as f:
+            write_census_tsv(*extras["census"], f)
+    if "heldout_ranks" in extras:
+        with open(cfg["heldout_ranks"], "w", encoding="utf-8") as f:
+            write_heldout_tsv(extras["heldout_ranks"], f)
     partners = bool(cfg["genes"] or cfg["all_genes"])
     if cfg["out"]:
         with open(cfg["out"], "w", encoding="utf-8") as f:
