@@ -65,7 +65,12 @@ int mmsbm_destroy(mmsbm_ctx *ctx);
 /* K groups, R ratings (2 in the reference, :79), B batched samples
  * (independent restarts, :1253), P genes (:413), eps (:88).  Changing K, R or P
  * drops the link sets, the degree and the workspace (call mmsbm_set_links and
- * mmsbm_set_workspace again); changing B drops the workspace. */
+ * mmsbm_set_workspace again); changing B drops the workspace.
+ * Accepted: 1 <= K <= MMSBM_MAX_K and 2 <= R <= 8 (MMSBM_ERR_UNSUPPORTED outside either
+ * range; the context keeps its previous shape), eps >= 0.  A rating no train link
+ * observes (counts_host[e][r] == 0 for every e) is valid: its slice pr[b][r] becomes
+ * exactly 0 at the first iteration and stays 0.  Every kernel takes eps from here; none
+ * assumes the reference's 1e-10. */
 int mmsbm_set_shape(mmsbm_ctx *ctx, int32_t K, int32_t R, int32_t B, int32_t P, double eps);
 
 /* One link set (MMSBM_SET_TRAIN = `links`, MMSBM_SET_TEST = `test_links`) as the

@@ -46,6 +46,10 @@ typedef struct mmsbm_pairs_ctx mmsbm_pairs_ctx;
 /* Context = one GPU + one shape; replaces the pair half of the `_23` Model state (:43-105). */
 int mmsbm_pairs_create(int device, mmsbm_pairs_ctx **out);
 int mmsbm_pairs_destroy(mmsbm_pairs_ctx *ctx);
+/* The shape of the triplet context it is used with (mmsbm_set_shape): 1 <= K <= MMSBM_MAX_K,
+ * 2 <= R <= 8 (MMSBM_ERR_UNSUPPORTED outside either range; the context keeps its previous
+ * shape), eps >= 0.  A rating no train pair observes is valid: its slice qr[b][r] becomes
+ * exactly 0 at the first iteration and stays 0. */
 int mmsbm_pairs_set_shape(mmsbm_pairs_ctx *ctx, int32_t K, int32_t R, int32_t B, int32_t P, double eps);
 
 /* One pair-link set (MMSBM_SET_TRAIN = `dlinks`, MMSBM_SET_TEST = `dtest_links`) as

@@ -39,7 +39,7 @@ def _links(P, E, seed, R=2, hub=0.0, multi=0.05, both=0.03):
         r = int(rng.integers(R))
         c[r] = int(rng.integers(2, 5)) if rng.random() < multi else 1
         if rng.random() < both:
-            c[1 - r] = 1
+            c[(r + 1) % R] = 1      # (1 - r at R = 2)
         rows.append(list(t) + c)
     return np.array(rows, dtype=np.int64)
 
@@ -72,9 +72,12 @@ def test_plan_invariants(plan_check, P, E, units, gcap, sp_rows, hub):
     _check(plan_check, P, E, units, gcap, sp_rows, hub)
 
 
-def _check(plan_check, P, E, units, gcap, sp_rows, hub, env=None):
-    links = _links(P, E, seed=P + E, hub=hub)
-    head = "%d 2 %d %d %d %d %d\n" % (len(links), P, units[0], units[1], gcap, sp_rows)
+def _check(plan_check, P, E, units, gcap, sp_rows, hub, env=None, R=2, links=None):
+    """`links`: rows of (i, j, k, n_0 .. n_{R-1}); by default the synthetic table of _links."""
+    if links is None:
+        links = _links(P, E, seed=P + E, R=R, hub=hub)
+    assert links.shape[1] == 3 + R
+    head = "%d %d %d %d %d %d %d\n" % (len(links), R, P, units[0], units[1], gcap, sp_rows)
     body = "\n".join(" ".join(str(v) for v in row) for row in links)
     res = subprocess.run([plan_check], input=head + body + "\n", capture_output=True, text=True,
                          env=None if env is None else {**os.environ, **env})
