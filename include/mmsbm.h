@@ -230,6 +230,40 @@ int mmsbm_scan_census(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known
                       const double *thresholds, int32_t M, void *ws, int64_t ws_bytes,
                       int64_t *out_counts, void *stream);
 
+/* Pair census: the census's counts binned by pair.  For M thresholds and every pair of rank
+ * positions x < y, the exact number of the scan's eligible triples that contain both x and y and
+ * whose score is at or above each threshold: the number of predicted, unmeasured interactions a
+ * double-mutant query (x, y) would have.  order, known, n_known, theta, pr, sample (-1: the mean over
+ * the active prefix), thresholds, ws and stream mean what they mean for mmsbm_scan_census; a triple
+ * is eligible exactly as there, and its score carries the same bits (one score phase serves the
+ * scan, the census and this call), so for every m the sum of the result over x < y is exactly three
+ * times mmsbm_scan_census's count at thresholds[m].
+ * thresholds f64[M] (device): finite and non-decreasing (the caller guarantees both; duplicates are
+ * fine), 0 <= M <= mmsbm_pair_census_max_m() (8: a tile with hits walks the thresholds one
+ * by one); above it MMSBM_ERR_UNSUPPORTED, as for K outside [1, MMSBM_MAX_K], for an ensemble
+ * whose W tile exceeds the LDS (as for the census) and for P > 16384 (a pair index x P + y stays
+ * below 2^28 and the result below 8 GiB).  Null pointers, a bad sample or a small workspace:
+ * MMSBM_ERR_INVALID.  Every argument is checked before any device call.
+ * Result (device) out_counts int32[P][P][M], zeroed by the call: out_counts[x][y][m], x < y = the
+ * eligible triples that contain the genes at rank positions x and y with score >= thresholds[m];
+ * entries with x >= y stay 0.  A count is at most P - 2.  M = 0 writes nothing; P < 3: all 0.  The
+ * call does not count a pair's eligible triples (P - 2 minus the known keys that contain the pair:
+ * host arithmetic on `known`).
+ * The counts are integers combined by integer adds only (registers, integer cross-lane moves and
+ * 32-bit global atomics); no floating-point value crosses a lane, so they do not depend on the grid,
+ * the batch the sample sits in or the arrival order.
+ * ws: mmsbm_pair_census_workspace_bytes(ctx, M) bytes of device scratch, 16-byte aligned, the
+ * caller's; its size follows the context's shape only.  theta, pr and thresholds are only read; all
+ * launches go to `stream` and nothing synchronises.  The environment variable
+ * MMSBM_PAIR_CENSUS_GRID=<workgroups> overrides the grid (measurement; the counts do not depend on
+ * it).  Needs R >= 2.  Replaces nothing in the reference. */
+int mmsbm_pair_census_max_m(void);
+int mmsbm_pair_census_workspace_bytes(const mmsbm_ctx *ctx, int32_t M, int64_t *bytes);
+int mmsbm_pair_census(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known, int64_t n_known,
+                      const double *theta, const double *pr, int32_t sample,
+                      const double *thresholds, int32_t M, void *ws, int64_t ws_bytes,
+                      int32_t *out_counts, void *stream);
+
 /* Link-sharded iteration (single sample over N ranks): each rank's context
  * holds 1/N of the train links (mmsbm_set_links) and the GLOBAL degree (mmsbm_set_degree).
  * Step 1, the accumulation half of make_iteration (:986-1012) over this rank's links:

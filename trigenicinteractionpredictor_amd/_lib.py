@@ -65,6 +65,9 @@ SIGNATURES = {
     "mmsbm_census_max_m": (_c_int, []),
     "mmsbm_census_workspace_bytes": (_c_int, [_vp, _c_i32, ctypes.POINTER(_c_i64)]),
     "mmsbm_scan_census": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_i32, _vp, _c_i32, _vp, _c_i64, _vp, _vp]),
+    "mmsbm_pair_census_max_m": (_c_int, []),
+    "mmsbm_pair_census_workspace_bytes": (_c_int, [_vp, _c_i32, ctypes.POINTER(_c_i64)]),
+    "mmsbm_pair_census": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_i32, _vp, _c_i32, _vp, _c_i64, _vp, _vp]),
     # include/mmsbm_pairs.h — the joint model's pair lattice
     "mmsbm_pairs_create": (_c_int, [_c_int, ctypes.POINTER(_vp)]),
     "mmsbm_pairs_destroy": (_c_int, [_vp]),

@@ -17,7 +17,8 @@ SRC_PAIRS = os.path.join(PKG, "csrc", "pairs.hip")     # joint model pair lattic
 SRC_SCAN = os.path.join(PKG, "csrc", "scan.hip")       # genome-wide top-N scan (mmsbm_scan_*)
 SRC_PARTNERS = os.path.join(PKG, "csrc", "partners.hip")   # per-gene partner scan (mmsbm_partners_*)
 SRC_CENSUS = os.path.join(PKG, "csrc", "census.hip")   # score census (mmsbm_census_*, mmsbm_scan_census)
-SRCS = [SRC, SRC_PAIRS, SRC_SCAN, SRC_PARTNERS, SRC_CENSUS]
+SRC_PAIR_CENSUS = os.path.join(PKG, "csrc", "pair_census.hip")   # pair census (mmsbm_pair_census_*)
+SRCS = [SRC, SRC_PAIRS, SRC_SCAN, SRC_PARTNERS, SRC_CENSUS, SRC_PAIR_CENSUS]
 INCLUDE = os.path.join(REPO, "include")
 OUT_DIR = os.path.join(PKG, "_build")
 LIB = os.path.join(OUT_DIR, "libmmsbm.so")
@@ -33,6 +34,8 @@ DEPS = {
     SRC_PARTNERS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(INCLUDE, "mmsbm.h")],
     SRC_CENSUS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
                  os.path.join(INCLUDE, "mmsbm.h")],
+    SRC_PAIR_CENSUS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
+                      os.path.join(INCLUDE, "mmsbm.h")],
 }
 
 

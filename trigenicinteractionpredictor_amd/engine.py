@@ -65,6 +65,7 @@ class EMEngine:
         self._scan_order = None
         self._partners_ws = None  # partners_top's scratch
         self._census_ws = None    # census's scratch
+        self._pair_census_ws = None   # pair_census's scratch
         self.theta = torch.zeros((self.B, self.P, self.K), dtype=torch.float64, device=self.device)
         self.pr = torch.zeros((self.B, self.R, self.K3), dtype=torch.float64, device=self.device)
 
@@ -341,6 +342,101 @@ class EMEngine:
         if stream is not None:
             stream.synchronize()
         return counts.cpu().numpy(), int(total.cpu()[0])
+
+    # ----------------------------------------------------------- pair census
+    def _pair_census_rank(self, thresholds, known, sample, stream):
+        """The pair census in rank positions: -> (device int32 [P][P][len(thresholds)], filled for
+        x < y only, thresholds in the caller's order; the launch stream).  One call of
+        mmsbm_pair_census per mmsbm_pair_census_max_m() thresholds."""
+        from .scan import census_chunks, rank_order
+        max_m = int(self.lib.mmsbm_pair_census_max_m())
+        chunks, perm = census_chunks(thresholds, max_m)      # ValueError on a NaN or infinite one
+        known = np.zeros(0, np.int64) if known is None else np.ascontiguousarray(known, dtype=np.int64)
+        if known.size > 1 and not (known[1:] > known[:-1]).all():
+            raise ValueError("known keys must be sorted and unique (scan.known_keys)")
+        if sample is not None and not 0 <= int(sample) < self.active:
+            raise ValueError("sample %r outside the active prefix [0, %d)" % (sample, self.active))
+        nbytes = ctypes.c_int64()
+        _lib.check(self.lib.mmsbm_pair_census_workspace_bytes(self.ctx, max(c.size for c in chunks),
+                                                              ctypes.byref(nbytes)))
+        if self._pair_census_ws is None or self._pair_census_ws.numel() < nbytes.value:
+            self._pair_census_ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        if self._scan_order is None:
+            self._scan_order = torch.from_numpy(rank_order(max(self.P, 1))).to(self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(s):      # the tensors below belong to the stream the kernels run on
+            known_d = torch.from_numpy(known).to(self.device)
+            outs = []
+            for chunk in chunks:
+                thr_d = torch.from_numpy(chunk if chunk.size else np.zeros(1)).to(self.device)
+                out = torch.empty((self.P, self.P, chunk.size), dtype=torch.int32, device=self.device)
+                _lib.check(self.lib.mmsbm_pair_census(
+                    self.ctx, _ptr(self._scan_order), _ptr(known_d) if known.size else None, int(known.size),
+                    _ptr(self.theta), _ptr(self.pr), -1 if sample is None else int(sample), _ptr(thr_d),
+                    int(chunk.size), _ptr(self._pair_census_ws), self._pair_census_ws.numel(),
+                    _ptr(out) if chunk.size else None, s.cuda_stream))
+                outs.append(out)
+            if len(outs) == 1 and (perm == np.arange(perm.size)).all():
+                mat = outs[0]           # one call, thresholds already ascending: nothing to put back
+            else:            # sorted position i answers the caller's thresholds[perm[i]]
+                mat = torch.empty((self.P, self.P, perm.size), dtype=torch.int32, device=self.device)
+                mat[:, :, torch.from_numpy(perm).to(self.device)] = torch.cat(outs, dim=2)
+        return mat, s
+
+    def pair_census_async(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None):
+        """pair_census without the host copy: -> a device tensor int32 [P][P][len(thresholds)] in
+        gene ids, symmetric with a zero diagonal, thresholds in the caller's order.  Nothing
+        synchronises."""
+        from .scan import rank_of, rank_order
+        mat, s = self._pair_census_rank(thresholds, known, sample, stream)
+        with torch.cuda.stream(s):
+            rank = torch.from_numpy(rank_of(rank_order(self.P))).to(self.device)
+            mat = mat + mat.transpose(0, 1)             # x < y was filled, the rest is zero
+            return mat[rank][:, rank].contiguous()      # [g1][g2] = [rank[g1]][rank[g2]]
+
+    def pair_census(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None):
+        """The pair census (include/mmsbm.h mmsbm_pair_census): -> int32 [P][P][len(thresholds)] on
+        the host; [g1][g2][i] = the eligible triples (those scan_top ranks: distinct genes, key not
+        in `known`) that contain the genes g1 and g2 and score >= thresholds[i]: the predicted,
+        unmeasured interactions of the double-mutant query (g1, g2).  Symmetric, zero diagonal.
+        The thresholds may come in any order, with duplicates, in any number or none; a NaN or an
+        infinite one raises ValueError.  known, sample: as for census; the scores are the census's
+        bit for bit, so the sum over g1 < g2 is three times census(thresholds)."""
+        mat = self.pair_census_async(thresholds, known, sample, stream)
+        if stream is not None:
+            stream.synchronize()
+        return mat.cpu().numpy()
+
+    def pairs_top(self, n: int, threshold: float, known: np.ndarray = None, sample: int = None):
+        """The n pairs with the most eligible triples scoring >= threshold: -> (counts int64[n'],
+        eligible int64[n'] = the pair's eligible triples in all (scan.pair_eligible), ids
+        int32[n'][2] in key order) on the host, n' = min(n, C(P, 2)).  Ordered by count descending,
+        equal counts by the pair's rank-position key x P + y ascending.  The selection is one
+        torch.topk on the device over count * P^2 + (P^2 - 1 - key)."""
+        from .scan import pair_eligible, rank_order
+        mat, s = self._pair_census_rank([float(threshold)], known, sample, None)
+        P = self.P
+        n = max(0, min(int(n), P * (P - 1) // 2))
+        with torch.cuda.stream(s):
+            key = torch.arange(P * P, dtype=torch.int64, device=self.device)
+            upper = (key // P) < (key % P)
+            combined = torch.where(upper, mat[:, :, 0].reshape(-1).to(torch.int64) * (P * P) + (P * P - 1 - key),
+                                   torch.full_like(key, -1))
+            best, _ = torch.topk(combined, n)
+        best = best.cpu().numpy()
+        counts = best // (P * P)
+        key = P * P - 1 - best % (P * P)
+        order = rank_order(max(P, 1))
+        ids = np.stack([order[key // P], order[key % P]], axis=1).astype(np.int32).reshape(-1, 2)
+        eligible = pair_eligible(P, known)[ids[:, 0], ids[:, 1]].astype(np.int64)
+        return counts.astype(np.int64), eligible, ids
+
+    def gene_census(self, thresholds, known: np.ndarray = None, sample: int = None):
+        """-> int64 [P][len(thresholds)] on the host: the eligible triples that contain each gene
+        and score >= each threshold.  The row sums of the pair matrix halved: every triple of a gene
+        sits in two of the gene's pairs."""
+        mat = self.pair_census_async(thresholds, known, sample)
+        return (mat.sum(dim=1, dtype=torch.int64) // 2).cpu().numpy()
 
     # ---------------------------------------------------------- measurement
     def kernels(self) -> dict:

@@ -33,6 +33,18 @@ next to the table above:
                            genome-wide rank among every triple not trained on (1 + the number of
                            those scoring strictly above it), ordered by rank, equal ranks by key.
 
+Two more come from the pair census (`EMEngine.pair_census`, mmsbm_pair_census), the census's counts
+binned by pair: the question of a trigenic screen, whose unit of work is a double-mutant query crossed
+against the whole array, is which pair to build next.
+    --pairs FILE           the --top pairs of genes with the most eligible triples (under --exclude,
+                           scored by --best or the ensemble mean) at or above --pair-threshold T
+                           (default 0.5, in (0, 1]): rank, count, eligible, ids, names rows, best
+                           first, equal counts by the pair's key; eligible = the pair's eligible
+                           triples in all (P - 2 minus its measured ones).
+    --gene-census FILE     one row per gene, in id order: gene, name and its count of eligible triples
+                           at or above each of --thresholds (default DEFAULT_THRESHOLDS), from the
+                           highest threshold down.
+
 Exactness: the counts are exact for the scan's score bits.  A listed triple's probability comes from
 the predict kernel, which sums in another order, so a triple within rounding distance (about 1e-12
 relative) of another triple's score may be placed on either side of it.  (Listed triples are
@@ -50,6 +62,8 @@ SETS = ("train", "test")
 MAX_TOP = 4096   # mmsbm_scan_max_n() (include/mmsbm.h): the largest N one scan returns
 MAX_PARTNER_TOP = 1024   # mmsbm_partners_max_n(): the largest N per query gene
 MAX_CENSUS_M = 1024      # mmsbm_census_max_m(): the most thresholds one census call takes
+MAX_PAIR_CENSUS_M = 8    # mmsbm_pair_census_max_m(): the most thresholds one pair census call takes
+DEFAULT_PAIR_THRESHOLD = 0.5   # --pairs without --pair-threshold
 DEFAULT_THRESHOLDS = (0.99, 0.95, 0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3, 0.2, 0.1, 0.05, 0.02, 0.01, 0.005,
                       0.002, 0.001)   # --census without --thresholds
 
@@ -183,6 +197,46 @@ def census_unsort(parts, perm) -> np.ndarray:
     return out
 
 
+def pair_eligible(P: int, known=None) -> np.ndarray:
+    """int32 [P][P] in gene ids: the eligible triples of every pair of genes, P - 2 minus the number
+    of `known` keys (sorted packed keys of rank positions, scan.known_keys) that contain the pair;
+    the diagonal is zero.  Keys that pack no triple a < b < c < P are ignored, as the kernels ignore
+    them.  Pure numpy: the pair census never counts eligibility (an add per triple)."""
+    P = int(P)
+    pos = np.full((P, P), max(P - 2, 0), dtype=np.int64)       # in rank positions
+    if known is not None and len(known) and P >= 3:
+        k = np.unique(np.asarray(known, dtype=np.int64).reshape(-1))
+        k = k[(k >= 0) & (k < P ** 3)]
+        a, b, c = k // (P * P), (k // P) % P, k % P
+        ok = (a < b) & (b < c)
+        a, b, c = a[ok], b[ok], c[ok]
+        for x, y in ((a, b), (a, c), (b, c)):
+            np.subtract.at(pos, (x, y), 1)
+            np.subtract.at(pos, (y, x), 1)
+    np.fill_diagonal(pos, 0)
+    rank = rank_of(rank_order(P))
+    return pos[rank][:, rank].astype(np.int32)
+
+
+def pair_key(i: int, j: int) -> str:
+    """The pair's key as `links` spells keys: the ids in string order, joined by '_'."""
+    return "_".join(sorted((str(int(i)), str(int(j)))))
+
+
+def pair_rows(id_gene, counts, eligible, ids):
+    """pairs_top's arrays -> rows [count, eligible, "i_j", [name1, name2]], names sorted."""
+    return [[int(n), int(e), pair_key(i, j), sorted((id_gene[int(i)], id_gene[int(j)]))]
+            for n, e, (i, j) in zip(counts, eligible, ids)]
+
+
+def parse_pair_threshold(text) -> float:
+    """'0.5' -> 0.5; ValueError unless it is one number in (0, 1]."""
+    v = float(text)
+    if not 0.0 < v <= 1.0:      # NaN fails the comparison
+        raise ValueError("pair threshold outside (0, 1]")
+    return v
+
+
 def parse_thresholds(text):
     """'0.5,0.1' -> [0.5, 0.1]; ValueError when a token does not parse, the list is empty or a
     value lies outside (0, 1]."""
@@ -254,6 +308,9 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [--census=] <TSV file: counts of eligible triples at or above each threshold>
     [--thresholds=] <comma list of floats in (0, 1]; default 0.99 ... 0.001>
     [--heldout-ranks=] <TSV file: the genome-wide rank of every test link (needs -e)>
+    [--pairs=] <TSV file: the --top gene pairs with the most eligible triples at or above T>
+    [--pair-threshold=] <T, a float in (0, 1]; default 0.5>
+    [--gene-census=] <TSV file: per gene, its eligible triples at or above each of --thresholds>
 """
 
 
@@ -262,12 +319,14 @@ def parse(argv):
     and -i are validated by cli.parse."""
     from . import cli
     cfg = dict(cli.DEFAULTS, samples=1, iterations=100, top=100, exclude=SETS, best=False, out=None,
-               seed=None, genes=[], all_genes=False, census=None, thresholds=None, heldout_ranks=None)
+               seed=None, genes=[], all_genes=False, census=None, thresholds=None, heldout_ranks=None,
+               pairs=None, pair_threshold=DEFAULT_PAIR_THRESHOLD, gene_census=None)
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
                                                         "best", "out=", "gene=", "all-genes", "census=",
-                                                        "thresholds=", "heldout-ranks="])
+                                                        "thresholds=", "heldout-ranks=", "pairs=",
+                                                        "pair-threshold=", "gene-census="])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -302,6 +361,16 @@ def parse(argv):
                 cfg["census"] = arg
             elif opt == "--heldout-ranks":
                 cfg["heldout_ranks"] = arg
+            elif opt == "--pairs":
+                cfg["pairs"] = arg
+            elif opt == "--gene-census":
+                cfg["gene_census"] = arg
+            elif opt == "--pair-threshold":
+                try:
+                    cfg["pair_threshold"] = parse_pair_threshold(arg)
+                except ValueError:
+                    print("\n\nERROR: --pair-threshold should be a number in (0, 1]")
+                    raise cli.ArgError()
             elif opt == "--thresholds":
                 try:
                     cfg["thresholds"] = parse_thresholds(arg)
@@ -354,11 +423,24 @@ def census_tables(eng, model, cfg, sample, extras):
         extras["heldout_ranks"] = heldout_rows(ids, link_counts, probs, ranks)
 
 
+def pair_tables(eng, model, cfg, sample, extras):
+    """The driver's --pairs and --gene-census tables into `extras` (see run)."""
+    if cfg.get("pairs"):
+        counts, eligible, ids = eng.pairs_top(cfg["top"], cfg["pair_threshold"],
+                                              known_keys(model, cfg["exclude"]), sample)
+        extras["pairs"] = pair_rows(model.id_gene, counts, eligible, ids)
+    if cfg.get("gene_census"):
+        thresholds = sorted(cfg.get("thresholds") or DEFAULT_THRESHOLDS, reverse=True)
+        counts = eng.gene_census(thresholds, known_keys(model, cfg["exclude"]), sample)
+        extras["gene_census"] = (thresholds, [model.id_gene[g] for g in range(model.P)], counts)
+
+
 def run(cfg, out=print, extras=None):
     """Fit the restarts as one batch, scan once, return the rows [rank, probability, ids, names]
     (with --gene / --all-genes: [query, rank, probability, ids, names], by query then rank).
     extras: a dict that receives "census" = (thresholds, counts, total) and "heldout_ranks" = rows
-    when cfg asks for them (--census, --heldout-ranks)."""
+    when cfg asks for them (--census, --heldout-ranks), and "pairs" = rows [count, eligible, ids,
+    names] and "gene_census" = (thresholds, names, counts int64[P][M]) for --pairs, --gene-census."""
     from .model import Model
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
@@ -377,6 +459,7 @@ def run(cfg, out=print, extras=None):
     sample = int(np.argmax(eng.loglik(_lib.SET_TRAIN))) if cfg["best"] else None
     if extras is not None:
         census_tables(eng, model, cfg, sample, extras)
+        pair_tables(eng, model, cfg, sample, extras)
     if queries is not None:
         out("partner pairs of %d genes: %s" % (len(queries), "sample %d" % sample if sample is not None
                                                else "mean of %d samples" % B))
@@ -411,6 +494,18 @@ def write_census_tsv(thresholds, counts, total, stream):
         stream.write("%r\t%d\t%r\n" % (float(t), int(c), (int(c) / total) if total else 0.0))
 
 
+def write_pairs_tsv(rows, stream):
+    stream.write("rank\tcount\teligible\tids\tnames\n")
+    for i, (count, eligible, key, names) in enumerate(rows):
+        stream.write("%d\t%d\t%d\t%s\t%s\n" % (i + 1, count, eligible, key, "_".join(names)))
+
+
+def write_gene_census_tsv(thresholds, names, counts, stream):
+    stream.write("gene\tname\t" + "\t".join("%r" % float(t) for t in thresholds) + "\n")
+    for g, (name, row) in enumerate(zip(names, counts)):
+        stream.write("%d\t%s\t%s\n" % (g, name, "\t".join("%d" % int(c) for c in row)))
+
+
 def write_heldout_tsv(rows, stream):
     stream.write("rank\tprobability\tids\treal\n")
     for rank, p, key, real in rows:
@@ -436,6 +531,12 @@ def main(argv=None, out=print):
     if "heldout_ranks" in extras:
         with open(cfg["heldout_ranks"], "w", encoding="utf-8") as f:
             write_heldout_tsv(extras["heldout_ranks"], f)
+    if "pairs" in extras:
+        with open(cfg["pairs"], "w", encoding="utf-8") as f:
+            write_pairs_tsv(extras["pairs"], f)
+    if "gene_census" in extras:
+        with open(cfg["gene_census"], "w", encoding="utf-8") as f:
+            write_gene_census_tsv(*extras["gene_census"], f)
     partners = bool(cfg["genes"] or cfg["all_genes"])
     if cfg["out"]:
         with open(cfg["out"], "w", encoding="utf-8") as f:
