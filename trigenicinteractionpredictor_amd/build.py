@@ -30,11 +30,14 @@ DEPS = {
           os.path.join(INCLUDE, "mmsbm.h")],
     SRC_PAIRS: [os.path.join(INCLUDE, "mmsbm.h"), os.path.join(INCLUDE, "mmsbm_pairs.h")],
     SRC_SCAN: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
-               os.path.join(INCLUDE, "mmsbm.h")],
-    SRC_PARTNERS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(INCLUDE, "mmsbm.h")],
+               os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(INCLUDE, "mmsbm.h")],
+    SRC_PARTNERS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_host.h"),
+                   os.path.join(INCLUDE, "mmsbm.h")],
     SRC_CENSUS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
+                 os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(PKG, "csrc", "scan_sweep.h"),
                  os.path.join(INCLUDE, "mmsbm.h")],
     SRC_PAIR_CENSUS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
+                      os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(PKG, "csrc", "scan_sweep.h"),
                       os.path.join(INCLUDE, "mmsbm.h")],
 }
 

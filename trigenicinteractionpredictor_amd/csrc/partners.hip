@@ -33,13 +33,14 @@
 #include <algorithm>
 #include <climits>
 #include <cstdint>
-#include <cstdlib>
 
 #include "mmsbm.h"
+#include "scan_host.h"
 #include "scan_select.h"
 
 namespace {
 
+using namespace scan_host;
 using namespace scan_select;
 
 constexpr int PARTNERS_MAX_N = 1024;   // documented cap of N (include/mmsbm.h): the buffer stays in LDS
@@ -354,7 +355,7 @@ __global__ __launch_bounds__(NT) void partners_merge_kernel(PMergeArgs A) {
 // Host side
 // ------------------------------------------------------------------------------------------
 struct PartPlan {
-  int device, K, KP, R, B, P, P16, nact, ncu;
+  ScanShape sh;
   int N, cap, gpq, n1;
   long long Q;
   size_t off_q, off_qpos, off_thT, off_T, off_ls[2], off_lk[2], off_ln[2], total;
@@ -363,18 +364,13 @@ struct PartPlan {
 // Everything that sizes the workspace follows the context's shape, Q and N only (not the sample
 // argument), so one workspace serves every call of that shape.
 int make_plan(const mmsbm_ctx* c, long long Q, int N, PartPlan* p) {
-  mmsbm_detail_scan_shape(c, &p->device, &p->K, &p->R, &p->B, &p->P, &p->nact, &p->ncu);
-  if (p->K < 1 || p->K > MMSBM_MAX_K)
-    return fail(MMSBM_ERR_UNSUPPORTED, "K=%d outside [1, %d]: call mmsbm_set_shape", p->K, MMSBM_MAX_K);
-  if (p->R < 2 || p->B < 1 || p->P < 0)
-    return fail(MMSBM_ERR_INVALID, "the partner scan needs R >= 2, B >= 1 (mmsbm_set_shape)");
+  ScanShape& sh = p->sh;
+  if (int rc = scan_shape(c, "the partner scan", &sh)) return rc;
   if (N < 1) return fail(MMSBM_ERR_INVALID, "N=%d < 1", N);
   if (N > PARTNERS_MAX_N)
     return fail(MMSBM_ERR_UNSUPPORTED, "N=%d above the partner scan's cap of %d", N, PARTNERS_MAX_N);
   if (Q < 0 || Q > 65535) return fail(MMSBM_ERR_INVALID, "Q=%lld outside [0, 65535]", Q);
-  if ((long long)p->P > 2000000) return fail(MMSBM_ERR_UNSUPPORTED, "P=%d: packed keys overflow", p->P);
-  p->KP = (p->K + 3) / 4 * 4;
-  p->P16 = std::max(16, (p->P + 15) / 16 * 16);
+  if (int rc = packed_keys_fit(sh)) return rc;
   p->N = N;
   p->Q = Q;
   p->cap = 512;
@@ -382,11 +378,11 @@ int make_plan(const mmsbm_ctx* c, long long Q, int N, PartPlan* p) {
   // workgroups per query: the device's worth over Q, no more than a query has items at the
   // narrowest row block, at most two merge levels
   const long long Q1 = std::max<long long>(Q, 1);
-  const long long items_max = (long long)((p->P + 15) / 16) * (p->P16 / 16);
-  const long long want = (8LL * std::max(p->ncu, 1) + Q1 - 1) / Q1;
+  const long long items_max = (long long)((sh.P + 15) / 16) * (sh.P16 / 16);
+  const long long want = (8LL * std::max(sh.ncu, 1) + Q1 - 1) / Q1;
   p->gpq = (int)std::max<long long>(1, std::min<long long>({want, items_max, (long long)MAX_GPQ}));
   p->n1 = (p->gpq + FAN - 1) / FAN;
-  const size_t B = p->B, P = p->P, K = p->K, KP = p->KP, P16 = p->P16, q = (size_t)Q1;
+  const size_t B = sh.B, K = sh.K, KP = sh.KP, P16 = sh.P16, q = (size_t)Q1;
   size_t off = align256(sizeof(unsigned long long) * q);  // [0, 8 Q): the published thresholds
   p->off_q = off, off = align256(off + sizeof(int) * q);
   p->off_qpos = off, off = align256(off + sizeof(int) * q);
@@ -398,18 +394,7 @@ int make_plan(const mmsbm_ctx* c, long long Q, int N, PartPlan* p) {
     p->off_lk[i] = off, off = align256(off + sizeof(long long) * nl[i] * N);
     p->off_ln[i] = off, off = align256(off + sizeof(int) * nl[i]);
   }
-  (void)P;
   p->total = off;
-  return MMSBM_OK;
-}
-
-template <int KS>
-int launch_partners(const PartArgs& a, int G, int lds, hipStream_t s) {
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&partners_kernel<KS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  partners_kernel<KS><<<G, NT, lds, s>>>(a);
-  HIP_TRY(hipGetLastError());
   return MMSBM_OK;
 }
 
@@ -437,34 +422,26 @@ int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queri
   int rc = make_plan(c, Q, N, &p);
   if (rc) return rc;
   if (Q == 0) return MMSBM_OK;
+  const ScanShape& sh = p.sh;
   if (!order || !queries_host || !theta || !pr || !out_scores || !out_ids || !out_count)
     return fail(MMSBM_ERR_INVALID, "null pointer");
   if (known_off && !known_pairs) return fail(MMSBM_ERR_INVALID, "known_off without known_pairs");
   for (int64_t i = 0; i < Q; ++i)
-    if (queries_host[i] < 0 || queries_host[i] >= p.P)
-      return fail(MMSBM_ERR_INVALID, "query %lld: gene id %d outside [0, %d)", (long long)i, queries_host[i], p.P);
-  if (sample < -1 || sample >= p.nact)
-    return fail(MMSBM_ERR_INVALID, "sample %d outside the active prefix [0, %d)", sample, p.nact);
-  if (!ws || ws_bytes < (int64_t)p.total || ((uintptr_t)ws & 15))
-    return fail(MMSBM_ERR_INVALID,
-                "partner workspace missing, misaligned or too small (mmsbm_partners_workspace_bytes)");
-  const int ns = sample >= 0 ? 1 : p.nact, s0 = sample >= 0 ? sample : 0;
-  const int WS = p.KP + 2;
-  int WB = 4;
-  while (WB > 1 && (size_t)2 * ns * 16 * WB * WS * sizeof(double) > (size_t)W_LDS_MAX) WB >>= 1;
-  const size_t w_bytes = (size_t)2 * ns * 16 * WB * WS * sizeof(double);
-  if (w_bytes > (size_t)W_LDS_MAX)
-    return fail(MMSBM_ERR_UNSUPPORTED,
-                "an ensemble of %d samples at K=%d exceeds the partner scan's LDS tile: scan the samples one by one",
-                ns, p.K);
+    if (queries_host[i] < 0 || queries_host[i] >= sh.P)
+      return fail(MMSBM_ERR_INVALID, "query %lld: gene id %d outside [0, %d)", (long long)i, queries_host[i], sh.P);
+  int ns, s0, WB;
+  size_t w_bytes;  // U and L: two W rows per row b; the known pairs are per query (checked above)
+  if ((rc = check_call(sh, "the partner scan", "mmsbm_partners_workspace_bytes", nullptr, 0, sample, ws, ws_bytes,
+                       p.total, &ns, &s0)))
+    return rc;
+  if ((rc = pick_wb(sh, "the partner scan", 2, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
   const size_t cand_bytes = (size_t)p.cap * 16;
   const int lds = (int)(sizeof(Sel) + w_bytes + cand_bytes);
   const int merge_lds = (int)(sizeof(Sel) + cand_bytes);
   static_assert(sizeof(Sel) + W_LDS_MAX + 2 * PARTNERS_MAX_N * 16 <= LDS_MAX, "the buffer stays in LDS");
-  bool select = true;
-  if (const char* e = getenv("MMSBM_PARTNERS_SELECT")) select = atoi(e) != 0;  // measurement: the bare score phase
+  const bool select = env_override("MMSBM_PARTNERS_SELECT", 1) != 0;  // measurement: the bare score phase
 
-  DeviceGuard g(p.device);
+  DeviceGuard g(sh.device);
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)ws;
   const int nq = (int)Q;
@@ -472,15 +449,15 @@ int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queri
   double* ls[2] = {(double*)(w + p.off_ls[0]), (double*)(w + p.off_ls[1])};
   long long* lk[2] = {(long long*)(w + p.off_lk[0]), (long long*)(w + p.off_lk[1])};
   int n_lists = 0;  // per query
-  if (p.P >= 3) {
+  if (sh.P >= 3) {
     HIP_TRY(hipMemsetAsync(w, 0, sizeof(unsigned long long) * nq, s));
     HIP_TRY(hipMemcpyAsync(w + p.off_q, queries_host, sizeof(int) * nq, hipMemcpyHostToDevice, s));
-    partners_theta_kernel<<<dim3((p.KP * p.P16 + NT - 1) / NT, ns), NT, 0, s>>>(
-        order, theta, (double*)(w + p.off_thT), p.K, p.KP, p.P, p.P16, s0);
+    partners_theta_kernel<<<dim3((sh.KP * sh.P16 + NT - 1) / NT, ns), NT, 0, s>>>(
+        order, theta, (double*)(w + p.off_thT), sh.K, sh.KP, sh.P, sh.P16, s0);
     HIP_TRY(hipGetLastError());
     partners_prep_kernel<<<dim3(nq, ns), NT, 0, s>>>(order, (const int*)(w + p.off_q), theta, pr,
-                                                     (double*)(w + p.off_T), (int*)(w + p.off_qpos), p.K,
-                                                     p.KP, p.R, p.P, nq, s0);
+                                                     (double*)(w + p.off_T), (int*)(w + p.off_qpos), sh.K,
+                                                     sh.KP, sh.R, sh.P, nq, s0);
     HIP_TRY(hipGetLastError());
     PartArgs a{};
     a.thT = (const double*)(w + p.off_thT);
@@ -490,28 +467,18 @@ int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queri
     a.known = (const long long*)known_pairs;
     a.list_s = ls[0], a.list_k = lk[0], a.list_n = ln[0];
     a.shared = (unsigned long long*)w;
-    a.K = p.K, a.P = p.P, a.P16 = p.P16, a.Q = nq, a.ns = ns, a.N = N, a.cap = p.cap, a.WB = WB;
+    a.K = sh.K, a.P = sh.P, a.P16 = sh.P16, a.Q = nq, a.ns = ns, a.N = N, a.cap = p.cap, a.WB = WB;
     a.select = select;
     a.gpq = p.gpq;
-    const int nbq = (p.P + 16 * WB - 1) / (16 * WB), nct = p.P16 / 16;
+    const int nbq = (sh.P + 16 * WB - 1) / (16 * WB), nct = sh.P16 / 16;
     a.ncc = std::max(1, std::min(nct, (p.gpq + nbq - 1) / nbq));  // enough items for the query's workgroups
     n_lists = p.gpq;
     const int G = nq * p.gpq;
-    switch (p.KP / 4) {
-      case 1: rc = launch_partners<1>(a, G, lds, s); break;
-      case 2: rc = launch_partners<2>(a, G, lds, s); break;
-      case 3: rc = launch_partners<3>(a, G, lds, s); break;
-      case 4: rc = launch_partners<4>(a, G, lds, s); break;
-      case 5: rc = launch_partners<5>(a, G, lds, s); break;
-      case 6: rc = launch_partners<6>(a, G, lds, s); break;
-      case 7: rc = launch_partners<7>(a, G, lds, s); break;
-      default: rc = launch_partners<8>(a, G, lds, s); break;
-    }
+    rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
+      return launch_lds(partners_kernel<decltype(ks)::value>, G, lds, s, a);
+    });
     if (rc) return rc;
   }
-  if (merge_lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&partners_merge_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, merge_lds));
   int cur = 0;
   for (;;) {
     const bool last = n_lists <= FAN;
@@ -519,10 +486,9 @@ int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queri
     ma.in_s = ls[cur], ma.in_k = lk[cur], ma.in_n = ln[cur], ma.n_in = n_lists;
     if (!last) ma.out_s = ls[cur ^ 1], ma.out_k = lk[cur ^ 1], ma.out_n = ln[cur ^ 1];
     ma.order = order, ma.scores = out_scores, ma.ids = out_ids, ma.count = (long long*)out_count;
-    ma.N = N, ma.cap = p.cap, ma.P = std::max(p.P, 1);
+    ma.N = N, ma.cap = p.cap, ma.P = std::max(sh.P, 1);
     const int n_out = last ? 1 : (n_lists + FAN - 1) / FAN;
-    partners_merge_kernel<<<dim3(n_out, nq), NT, merge_lds, s>>>(ma);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch_lds(partners_merge_kernel, dim3(n_out, nq), merge_lds, s, ma))) return rc;
     if (last) break;
     n_lists = n_out;
     cur ^= 1;

@@ -33,24 +33,25 @@
 // not depend on the grid, the arrival order or the batch.  Scores are never combined by atomics
 // and every sum has a fixed order.  The selection machinery (order, buffer, keep-best-N, merge) is
 // scan_select.h, shared with the partner scan (partners.hip); the score phase (prep, W rows, the
-// MFMA chain of a tile, the ensemble's sum and division) is scan_score.h, shared with the score
-// census (census.hip), whose scores therefore carry this kernel's bits.
+// MFMA chain of a tile, the ensemble's sum and division) is scan_score.h, shared with the sweep of
+// the score census and the pair census (scan_sweep.h), whose scores therefore carry this kernel's
+// bits; the host prologue (shape, checks, launch, dispatch on K) is scan_host.h, shared by all four.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
 #include <cstdint>
-#include <cstdlib>
 
 #include "mmsbm.h"
+#include "scan_host.h"
 #include "scan_score.h"
 #include "scan_select.h"
 
 namespace {
 
+using namespace scan_host;
 using namespace scan_select;
-using scan_score::pick_wb;
 using scan_score::scan_prep_kernel;
 using scan_score::Score;
 using scan_score::W_LDS_MAX;
@@ -259,35 +260,29 @@ __global__ __launch_bounds__(NT) void scan_merge_kernel(MergeArgs A) {
 // Host side
 // ------------------------------------------------------------------------------------------
 struct ScanPlan {
-  int device, K, KP, R, B, P, P16, nact, ncu;
+  ScanShape sh;
   int N, cap, G, G2;
   size_t off_thT, off_T, off_cs, off_ck, off_ls[2], off_lk[2], off_ln[2], total;
 };
 
-
 // Everything that sizes the workspace follows the context's shape and N only (not the sample
 // argument), so one workspace serves every call of that shape.
 int make_plan(const mmsbm_ctx* c, int N, ScanPlan* p) {
-  mmsbm_detail_scan_shape(c, &p->device, &p->K, &p->R, &p->B, &p->P, &p->nact, &p->ncu);
-  if (p->K < 1 || p->K > MMSBM_MAX_K)
-    return fail(MMSBM_ERR_UNSUPPORTED, "K=%d outside [1, %d]: call mmsbm_set_shape", p->K, MMSBM_MAX_K);
-  if (p->R < 2 || p->B < 1 || p->P < 0) return fail(MMSBM_ERR_INVALID, "scan needs R >= 2, B >= 1 (mmsbm_set_shape)");
+  ScanShape& sh = p->sh;
+  if (int rc = scan_shape(c, "scan", &sh)) return rc;
   if (N < 1) return fail(MMSBM_ERR_INVALID, "N=%d < 1", N);
   if (N > SCAN_MAX_N) return fail(MMSBM_ERR_UNSUPPORTED, "N=%d above the scan's cap of %d", N, SCAN_MAX_N);
-  if ((long long)p->P > 2000000) return fail(MMSBM_ERR_UNSUPPORTED, "P=%d: packed keys overflow", p->P);
-  p->KP = (p->K + 3) / 4 * 4;
-  p->P16 = std::max(16, (p->P + 15) / 16 * 16);
+  if (int rc = packed_keys_fit(sh)) return rc;
   p->N = N;
   p->cap = 512;
   while (p->cap < 2 * N) p->cap <<= 1;
   const long long per_cu = N <= 1024 ? 4 : N <= 2048 ? 2 : 1;
-  const long long items = std::max<long long>(1, (long long)p->P * (p->P16 / 16));
-  p->G = (int)std::min<long long>(per_cu * p->ncu, items);
+  const long long items = std::max<long long>(1, (long long)sh.P * (sh.P16 / 16));
+  p->G = (int)std::min<long long>(per_cu * sh.ncu, items);
   p->G2 = (p->G + FAN - 1) / FAN;
-  const size_t B = p->B, P = p->P, K = p->K, KP = p->KP, P16 = p->P16, G = p->G, cap = p->cap;
+  const size_t G = p->G, cap = p->cap;
   size_t off = 256;  // [0, 256): the published threshold
-  p->off_thT = off, off = align256(off + sizeof(double) * B * KP * P16);
-  p->off_T = off, off = align256(off + sizeof(double) * B * P * K * KP);
+  score_workspace(sh, off, &p->off_thT, &p->off_T);
   p->off_cs = off, off = align256(off + sizeof(double) * G * cap);
   p->off_ck = off, off = align256(off + sizeof(long long) * G * cap);
   const size_t nl[2] = {G, (size_t)p->G2};
@@ -297,16 +292,6 @@ int make_plan(const mmsbm_ctx* c, int N, ScanPlan* p) {
     p->off_ln[i] = off, off = align256(off + sizeof(int) * nl[i]);
   }
   p->total = off;
-  return MMSBM_OK;
-}
-
-template <int KS>
-int launch_scan(const ScanArgs& a, int G, int lds, hipStream_t s) {
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_kernel<KS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  scan_kernel<KS><<<G, NT, lds, s>>>(a);
-  HIP_TRY(hipGetLastError());
   return MMSBM_OK;
 }
 
@@ -335,37 +320,29 @@ int mmsbm_scan_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, in
   if (rc) return rc;
   if (!order || !theta || !pr || !out_scores || !out_ids || !out_count)
     return fail(MMSBM_ERR_INVALID, "null pointer");
-  if (n_known < 0 || (n_known > 0 && !known)) return fail(MMSBM_ERR_INVALID, "bad known-key table");
-  if (sample < -1 || sample >= p.nact)
-    return fail(MMSBM_ERR_INVALID, "sample %d outside the active prefix [0, %d)", sample, p.nact);
-  if (!ws || ws_bytes < (int64_t)p.total || ((uintptr_t)ws & 15))
-    return fail(MMSBM_ERR_INVALID, "scan workspace missing, misaligned or too small (mmsbm_scan_workspace_bytes)");
-  const int ns = sample >= 0 ? 1 : p.nact, s0 = sample >= 0 ? sample : 0;
-  size_t w_bytes = 0;
-  const int WB = pick_wb(ns, p.KP, &w_bytes);
-  if (w_bytes > (size_t)W_LDS_MAX)
-    return fail(MMSBM_ERR_UNSUPPORTED, "an ensemble of %d samples at K=%d exceeds the scan's LDS tile: scan the samples one by one",
-                ns, p.K);
+  const ScanShape& sh = p.sh;
+  int ns, s0, WB;
+  size_t w_bytes;
+  if ((rc = check_call(sh, "scan", "mmsbm_scan_workspace_bytes", known, n_known, sample, ws, ws_bytes, p.total, &ns,
+                       &s0)))
+    return rc;
+  if ((rc = pick_wb(sh, "scan", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
   const size_t cand_bytes = (size_t)p.cap * 16;
   const bool cand_lds = sizeof(Sel) + w_bytes + cand_bytes <= (size_t)LDS_MAX;
   const int lds = (int)(sizeof(Sel) + w_bytes + (cand_lds ? cand_bytes : 0));
   const int merge_lds = (int)(sizeof(Sel) + cand_bytes);
-  bool select = true;
-  if (const char* e = getenv("MMSBM_SCAN_SELECT")) select = atoi(e) != 0;  // measurement: the bare score phase
+  const bool select = env_override("MMSBM_SCAN_SELECT", 1) != 0;  // measurement: the bare score phase
 
-  DeviceGuard g(p.device);
+  DeviceGuard g(sh.device);
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)ws;
   HIP_TRY(hipMemsetAsync(w, 0, 256, s));
   int* ln[2] = {(int*)(w + p.off_ln[0]), (int*)(w + p.off_ln[1])};
   double* ls[2] = {(double*)(w + p.off_ls[0]), (double*)(w + p.off_ls[1])};
   long long* lk[2] = {(long long*)(w + p.off_lk[0]), (long long*)(w + p.off_lk[1])};
-  if (merge_lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_merge_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, merge_lds));
-  if (p.P >= 3) {
-    scan_prep_kernel<<<dim3(p.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
-                                                    (double*)(w + p.off_T), p.K, p.KP, p.R, p.P, p.P16, s0);
+  if (sh.P >= 3) {
+    scan_prep_kernel<<<dim3(sh.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
+                                                     (double*)(w + p.off_T), sh.K, sh.KP, sh.R, sh.P, sh.P16, s0);
     HIP_TRY(hipGetLastError());
   }
   // Pass 0 (large P only) seeds the bound: the same scan and merge over every SEED_STRIDE-th item,
@@ -373,10 +350,10 @@ int mmsbm_scan_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, in
   // instead of written out.  Pass 1 scans every item and starts from that bound, so it appends
   // about N SEED_STRIDE candidates in all instead of filling every workgroup's buffer from nothing.
   // The bound only prunes: the result does not depend on it.
-  for (int pass = (select && p.P >= SEED_MIN_P) ? 0 : 1; pass < 2; ++pass) {
+  for (int pass = (select && sh.P >= SEED_MIN_P) ? 0 : 1; pass < 2; ++pass) {
     const bool seeding = pass == 0;
     int n_lists = 0;
-    if (p.P >= 3) {
+    if (sh.P >= 3) {
       ScanArgs a{};
       a.thT = (const double*)(w + p.off_thT);
       a.T = (const double*)(w + p.off_T);
@@ -388,19 +365,12 @@ int mmsbm_scan_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, in
       a.list_k = lk[0];
       a.list_n = ln[0];
       a.shared = (unsigned long long*)w;
-      a.K = p.K, a.P = p.P, a.P16 = p.P16, a.ns = ns, a.N = N, a.cap = p.cap, a.WB = WB, a.select = select;
+      a.K = sh.K, a.P = sh.P, a.P16 = sh.P16, a.ns = ns, a.N = N, a.cap = p.cap, a.WB = WB, a.select = select;
       a.stride = seeding ? SEED_STRIDE : 1;
-      n_lists = seeding ? std::min(p.G, p.ncu) : p.G;
-      switch (p.KP / 4) {
-        case 1: rc = launch_scan<1>(a, n_lists, lds, s); break;
-        case 2: rc = launch_scan<2>(a, n_lists, lds, s); break;
-        case 3: rc = launch_scan<3>(a, n_lists, lds, s); break;
-        case 4: rc = launch_scan<4>(a, n_lists, lds, s); break;
-        case 5: rc = launch_scan<5>(a, n_lists, lds, s); break;
-        case 6: rc = launch_scan<6>(a, n_lists, lds, s); break;
-        case 7: rc = launch_scan<7>(a, n_lists, lds, s); break;
-        default: rc = launch_scan<8>(a, n_lists, lds, s); break;
-      }
+      n_lists = seeding ? std::min(p.G, sh.ncu) : p.G;
+      rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
+        return launch_lds(scan_kernel<decltype(ks)::value>, n_lists, lds, s, a);
+      });
       if (rc) return rc;
     }
     int cur = 0;
@@ -411,10 +381,9 @@ int mmsbm_scan_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, in
       if (!last) ma.out_s = ls[cur ^ 1], ma.out_k = lk[cur ^ 1], ma.out_n = ln[cur ^ 1];
       ma.order = order, ma.scores = out_scores, ma.ids = out_ids, ma.count = (long long*)out_count;
       ma.shared = (seeding && last) ? (unsigned long long*)w : nullptr;
-      ma.N = N, ma.cap = p.cap, ma.P = std::max(p.P, 1);
+      ma.N = N, ma.cap = p.cap, ma.P = std::max(sh.P, 1);
       const int n_out = last ? 1 : (n_lists + FAN - 1) / FAN;
-      scan_merge_kernel<<<n_out, NT, merge_lds, s>>>(ma);
-      HIP_TRY(hipGetLastError());
+      if ((rc = launch_lds(scan_merge_kernel, n_out, merge_lds, s, ma))) return rc;
       if (last) break;
       n_lists = n_out;
       cur ^= 1;

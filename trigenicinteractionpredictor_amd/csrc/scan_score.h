@@ -1,8 +1,9 @@
-// scan_score.h — the score phase shared by the genome-wide scan (scan.hip) and the score census
-// (census.hip): the prep kernel (Th' k-major, T_a of every gene), a work item's W rows in LDS, the
-// MFMA chain of one 16 x 16 tile and the ensemble's slot-order sum and division.  Both kernels form
-// a score through these functions and nothing else, so a triple's score carries the same bits in
-// either: the census at the scores of a scan list returns each entry's position in that list.
+// scan_score.h — the score phase shared by the genome-wide scan (scan.hip) and the triangle sweep
+// of the score census and the pair census (scan_sweep.h): the prep kernel (Th' k-major, T_a of every
+// gene), a work item's W rows in LDS, the MFMA chain of one 16 x 16 tile and the ensemble's
+// slot-order sum and division.  Every kernel forms a score through these functions and nothing
+// else, so a triple's score carries the same bits in each: the census at the scores of a scan list
+// returns each entry's position in that list.
 //
 // Notation (scan.hip): Th' = theta in rank order, T_a[y][z] = sum_x Th'[a][x] p_1[x][y][z],
 // W_a[b][z] = sum_y Th'[b][y] T_a[y][z], S_a[b][c] = sum_z W_a[b][z] Th'[c][z].  A work item is
@@ -10,6 +11,7 @@
 #ifndef MMSBM_SCAN_SCORE_H
 #define MMSBM_SCAN_SCORE_H
 
+#include "mmsbm.h"
 #include "scan_select.h"
 
 namespace scan_score {
@@ -17,7 +19,7 @@ namespace scan_score {
 using scan_select::d4v;
 using scan_select::NT;
 
-constexpr int W_LDS_MAX = 64 * 1024;  // the W rows of one item, every sample
+constexpr int W_LDS_MAX = 64 * 1024;  // the W rows of one item, every sample (scan_host::pick_wb)
 
 // ------------------------------------------------------------------------------------------
 // Prep: Th' k-major and zero-padded (thT[s][KP][P16]) and T_a (T[s][P][K][KP]) of every gene.
@@ -50,16 +52,6 @@ static __global__ __launch_bounds__(NT) void scan_prep_kernel(const int* __restr
       for (int x = 0; x < K; ++x) v = fma(th[x], p1[x * K2 + y * K + z], v);
     Ta[idx] = v;
   }
-}
-
-// The widest row block (WB b-tiles of 16 rows, a power of two <= 4) whose W rows of `ns` samples fit
-// W_LDS_MAX; *w_bytes may still exceed it at WB = 1 (the caller reports the ensemble as unsupported).
-inline int pick_wb(int ns, int KP, size_t* w_bytes) {
-  const int WS = KP + 2;
-  int WB = 4;
-  while (WB > 1 && (size_t)ns * 16 * WB * WS * sizeof(double) > (size_t)W_LDS_MAX) WB >>= 1;
-  *w_bytes = (size_t)ns * 16 * WB * WS * sizeof(double);
-  return WB;
 }
 
 template <int KS>

@@ -1,6 +1,8 @@
 // scan_select.h — the selection machinery shared by the genome-wide scan (scan.hip) and the partner
 // scan (partners.hip): the total order, a workgroup's candidate buffer with ballot-compacted
-// appends, keep-best-N by a bitonic sort, the list merge, and the sorted known-key search.
+// appends, keep-best-N by a bitonic sort and the list merge; and the sorted known-key search
+// (lower_bound, is_known), which the census sweep (scan_sweep.h) uses too.  Device code only: the
+// host side of every family is scan_host.h.
 //
 // Every entry of a buffer is (score, key); the total order is score descending, key ascending, so
 // the best N of any set is unique and does not depend on who appended what when.  Everything is
@@ -11,50 +13,12 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-
-#include "mmsbm.h"
-
-int mmsbm_detail_fail(int code, const char* msg);  // mmsbm.hip: the library's error channel
-int mmsbm_detail_scan_shape(const mmsbm_ctx* c, int* device, int* K, int* R, int* B, int* P, int* nact,
-                            int* ncu);
 
 namespace scan_select {
 
 constexpr int NT = 256;  // threads per workgroup of every scan kernel
 constexpr int FAN = 32;  // lists merged by one workgroup of a merge kernel
 constexpr int LDS_MAX = 144 * 1024;
-
-inline int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return mmsbm_detail_fail(code, buf);
-}
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return fail(MMSBM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 typedef double d4v __attribute__((ext_vector_type(4)));
 
