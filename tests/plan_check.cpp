@@ -242,7 +242,8 @@ int main() {
   // PLAN_MERGE=1: one partial row per (workgroup, gene) (the K >= 25 pass kernel merges its waves' parts)
   const bool merge = getenv("PLAN_MERGE") != nullptr;
   const int gu = (gcap == 0 || gcap == -2) ? 4 : 8;
-  // PLAN_NW=n: n units per large-K workgroup (the K >= 25 pass kernel runs 4-wave workgroups)
+  // PLAN_NW=n: n units per large-K workgroup (Plan::nw; the pass kernel itself runs NW-wave
+  // workgroups at every K)
   const int nw_env = getenv("PLAN_NW") ? atoi(getenv("PLAN_NW")) : NW;
   // PLAN_SP_CAP=n: at most n S-partial parts per rating (the large-K product plans take 1,024)
   const int sp_cap = getenv("PLAN_SP_CAP") ? atoi(getenv("PLAN_SP_CAP")) : 256;

@@ -118,8 +118,8 @@ def test_balanced_plan_fewer_workgroups(plan_check):
     assert int(bal[3]) < int(old[3])
 
 
-# 4-unit workgroups (the K >= 25 pass kernel: 4-wave workgroups, three per CU, gene cap 4), merged
-# and plain partial rows, balanced and round-3 packing
+# 4-unit workgroups (the planner's nw parameter; the pass kernel runs 8-wave workgroups at every K,
+# so no product plan is built this way), merged and plain partial rows, balanced and round-3 packing
 @pytest.mark.parametrize("P,E,units,gcap,sp_rows,hub", [
     (500, 40000, (64, 64), 4, 128, 0.0),
     (300, 5000, (1536, 3072), 4, 128, 30.0),

@@ -80,102 +80,43 @@ int fail(int code, const char* fmt, ...) {
 // ------------------------------------------------------------------------------------------
 // Compile-time shape of one K.
 // ------------------------------------------------------------------------------------------
-// Pass-A LDS budget (V tables of GMAX genes + the wave images): two workgroups per CU at every K.
-// Measured (tools/gpu_r02c_gcap.sh): a 150 KB budget (one workgroup per CU, GMAX 22 at K = 20,
-// 13 at K = 30) ran pass A at 156 us (K = 20 x 8) and 2088 us (K = 30, 10M links); 78 KB
+// Pass-A LDS budget (V tables of GMAX genes + the wave images): two workgroups per CU below
+// K = BIG_K.  Measured (tools/gpu_r02c_gcap.sh): a 150 KB budget (one workgroup per CU, GMAX 22
+// at K = 20, 13 at K = 30) ran pass A at 156 us (K = 20 x 8) and 2088 us (K = 30, 10M links); 78 KB
 // (GMAX 9 / 4) at 125 us and 1794 us.
-// From K = MMSBM_LDS_BIG up the pass kernel takes more than 128 VGPRs (130-140 at K = 25-32), so it
-// runs one workgroup per CU whatever its LDS: there the budget is 150 KB (GMAX 13 at K = 30 instead
-// of 5; pass A 2,761 -> 2,531 us at K=30 on 10M links, profiles/r04s_large_ab.txt)
-#ifndef MMSBM_LDS_BIG
-#define MMSBM_LDS_BIG 25
-#endif
-// Waves per pass workgroup from K = MMSBM_LDS_BIG (MMSBM_PNW; below LDS_BIG always NW = 8) and
-// the V operands in registers (MMSBM_VREG, pass_kernel).  Measured at K=30 on 10M links, one box
-// (profiles/r05_vreg_ab.txt): 8-wave workgroups with V in registers (~245 VGPRs, one workgroup per
-// CU) are fastest; 4-wave workgroups (MMSBM_PNW=4: 52 KB, three per CU at <= 168 VGPRs with U=4 /
-// DT=1, profiles/r05_pnw4_ab.txt) beat 8-wave ones only while V is read from LDS, and with V in
-// registers (two per CU) they lose.
-#ifndef MMSBM_PNW
-#define MMSBM_PNW 8
-#endif
-#ifndef MMSBM_VREG
-#define MMSBM_VREG 1
-#endif
-#ifndef MMSBM_ZSPLIT
-#define MMSBM_ZSPLIT 1
-#endif
-#ifndef MMSBM_VREG_MIN
-#define MMSBM_VREG_MIN MMSBM_LDS_BIG
-#endif
-#ifndef MMSBM_PNW_U
-#define MMSBM_PNW_U 4
-#endif
-#ifndef MMSBM_PNW_DT
-#define MMSBM_PNW_DT 1
-#endif
-#ifndef MMSBM_PNW_WPE
-#define MMSBM_PNW_WPE 3
-#endif
-#ifndef MMSBM_LDS_BIGKB
-#define MMSBM_LDS_BIGKB (MMSBM_PNW == 8 ? 150 : 52)
-#endif
-constexpr int pnw_for(int K) { return K >= MMSBM_LDS_BIG ? MMSBM_PNW : NW; }
-constexpr int lds_target(int K) {
-  return K >= MMSBM_LDS_BIG ? MMSBM_LDS_BIGKB * 1024 : K <= 16 ? 76 * 1024 : 78 * 1024;
-}
+// From K = BIG_K up the pass kernel takes more than 128 VGPRs (130-140 at K = 25-32), so it runs
+// one workgroup per CU whatever its LDS: there the budget is 150 KB (GMAX 13 at K = 30 instead of
+// 5; pass A 2,761 -> 2,531 us at K=30 on 10M links, profiles/r04s_large_ab.txt), its partial rows
+// are merged per (workgroup, gene) (MG) and the V operands stay in registers (VREG, pass_kernel).
+// Measured at K=30 on 10M links, one box (profiles/r05_vreg_ab.txt): 8-wave workgroups with V in
+// registers (~245 VGPRs, one workgroup per CU) are fastest; 4-wave workgroups (52 KB, three per CU
+// at <= 168 VGPRs with a shorter pipeline, profiles/r05_pnw4_ab.txt) beat 8-wave ones only while V
+// is read from LDS, and with V in registers (two per CU) they lose.  So the pass workgroup is NW
+// waves at every K.
+constexpr int BIG_K = 25;
+constexpr int lds_target(int K) { return K >= BIG_K ? 150 * 1024 : K <= 16 ? 76 * 1024 : 78 * 1024; }
 
-// Pass-A ablations for measurement builds only (results invalid): 1 = no Y stores, 2 = theta
-// gathers from 64 hot rows (L2 hits), 4 = no partial-row stores
-#ifndef MMSBM_ABL
-#define MMSBM_ABL 0
-#endif
-
-// Large-K Y entries: row stride K rounded up to MMSBM_YALIGN doubles (4 = one 32-B sector), so no
+// Large-K Y entries: row stride K rounded up to YALIGN doubles (4 = one 32-B sector), so no
 // entry starts inside a sector another entry also writes (the pad words hold zeros or never-read
 // values).  K=30 on 10M links: pass A 3,695 us at stride 30, 3,402 at 32; K=20 x 8 (already
 // sector-aligned at 20): 139.8 us at 20, 152.5 at 24 and 197.0 at 32, the pad being pure extra
 // bytes there (profiles/r04p_large_ab.txt).
-#ifndef MMSBM_YALIGN
-#define MMSBM_YALIGN 4
-#endif
-constexpr int y_stride(int K) { return (K + MMSBM_YALIGN - 1) / MMSBM_YALIGN * MMSBM_YALIGN; }
-// Y entry stores (pass A) and loads (upd) plain or non-temporal: bit 1 stores, bit 2 loads.
-// Non-temporal loads in upd: K=30 on 10M links upd 895 -> 807 us (the 5.1 GB stream no longer
-// displaces the L2's theta / X-row lines); non-temporal stores in pass A within noise, and
-// non-temporal loads of the small-K SK_Y entries (92 MB, just written, on die) slower (fin 19.5 ->
-// 21.8 us at K=10 x 8): profiles/r06p_fin_ynt_ab.txt, r06q_fin_butterfly_ab.txt
-#ifndef MMSBM_YNT
-#define MMSBM_YNT 2
-#endif
-__device__ __forceinline__ void y_st(double* p, double v) {
-  if constexpr (MMSBM_YNT & 1) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
+constexpr int YALIGN = 4;
+static_assert(YALIGN % 2 == 0, "upd_kernel reads the Y entries as 16-byte pairs");
+constexpr int y_stride(int K) { return (K + YALIGN - 1) / YALIGN * YALIGN; }
+// Y entry stores (pass A) are plain, the loads (upd) non-temporal: K=30 on 10M links upd 895 ->
+// 807 us (the 5.1 GB stream no longer displaces the L2's theta / X-row lines); non-temporal stores
+// in pass A were within noise, and non-temporal loads of the small-K SK_Y entries (92 MB, just
+// written, on die) slower (fin 19.5 -> 21.8 us at K=10 x 8): profiles/r06p_fin_ynt_ab.txt,
+// r06q_fin_butterfly_ab.txt
 typedef double yd2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ yd2 y_ld2(const yd2* p) {
-  if constexpr (MMSBM_YNT & 2) return __builtin_nontemporal_load(p);
-  else return *p;
-}
+__device__ __forceinline__ yd2 y_ld2(const yd2* p) { return __builtin_nontemporal_load(p); }
 
-// Pass-kernel occupancy hint: 1 leaves the compiler free (K = 25-32 take 132-134 VGPRs, so one
-// 8-wave workgroup per CU although the LDS would fit two); 4 caps it at 128 VGPRs (4 waves per
-// SIMD) at the price of 3-21 spilled VGPRs: K=30 pass A 3,402 us capped vs 3,306 free
-// (profiles/r04p_large_ab.txt), so the default stays free.
-#ifndef MMSBM_PASS_WPE
-#define MMSBM_PASS_WPE 1
-#endif
-constexpr int PASS_WPE = MMSBM_PASS_WPE;
-
-// Row strides of pass A's V tables and of their genes' theta rows: odd (1) or the round-3 even
-// strides (0, measurement).  The compiler pairs the chunk loop's V reads into ds_read2_b64, whose
-// 16-lane groups bank on (a/4) mod 32: an odd stride puts the 16 rows of a Z read (b = 4 blk + lo)
-// on distinct banks, and the 4 theta rows of a V-prologue read (4 t + lo) likewise; the Z' reads
-// walk one row and stay conflict-free at any stride.
-#ifndef MMSBM_VR_ODD
-#define MMSBM_VR_ODD 1
-#endif
-
+// Row strides of pass A's V tables and of their genes' theta rows are odd.  The compiler pairs the
+// chunk loop's V reads into ds_read2_b64, whose 16-lane groups bank on (a/4) mod 32: an odd stride
+// puts the 16 rows of a Z read (b = 4 blk + lo) on distinct banks, and the 4 theta rows of a
+// V-prologue read (4 t + lo) likewise; the Z' reads walk one row and stay conflict-free at any
+// stride (round 3's even strides, KP + 2 and KP: profiles/r04m_vstride_ab.txt).
 template <int K>
 struct KT {
   static constexpr int NG = (K + 3) / 4;          // 4-wide tiles of one K axis
@@ -183,9 +124,9 @@ struct KT {
   static constexpr int K2 = K * K, K3 = K * K * K;
   static constexpr int NBG = (NG + 3) / 4;        // Z phase: groups of 4 b-tiles (one per block)
   static constexpr int VROWS = 16 * NBG;          // V image rows (b); zero from K on
-  static constexpr int VR = MMSBM_VR_ODD ? KP + 1 : KP + 2;  // V row stride (above)
+  static constexpr int VR = KP + 1;               // V row stride (above)
   static constexpr int VDBL = VROWS * VR;         // one gene's V image
-  static constexpr int TGR = MMSBM_VR_ODD ? KP + 1 : KP;     // theta row stride of the V genes
+  static constexpr int TGR = KP + 1;              // theta row stride of the V genes
   // doubles of g genes' theta rows, even so the wave images after them stay 16-byte aligned
   static constexpr int tg_dbl(int g) { return (g * TGR + 1) & ~1; }
   static constexpr int TR = KP + 2;               // theta image row stride
@@ -193,10 +134,7 @@ struct KT {
   static constexpr int SW = (K % 2 == 0) ? 2 : 1;  // staging width: double2 pieces when K is even
   static constexpr int NPC = (8 * KP / SW + 63) / 64;  // staged pieces per lane per chunk
   static constexpr int IMGW = 2 * IMG + 2;        // per wave: double buffer + a dummy piece slot
-  static constexpr int NWK = pnw_for(K), NTK = 64 * NWK;  // pass_kernel's waves / threads
-  // occupancy hint: 4-wave workgroups three per CU (<= 168 VGPRs), else PASS_WPE
-  static constexpr int WPE = NWK == 4 ? MMSBM_PNW_WPE : PASS_WPE;
-  static constexpr int IMG_BYTES = NWK * IMGW * 8;
+  static constexpr int IMG_BYTES = NW * IMGW * 8;
   static constexpr int GMAX_RAW = (lds_target(K) - IMG_BYTES - 64 - 8) / ((VDBL + TGR) * 8);
   static constexpr int GMAX = GMAX_RAW > 64 ? 64 : (GMAX_RAW < 4 ? 4 : GMAX_RAW);
   static constexpr int LDS_A = GMAX * VDBL * 8 + tg_dbl(GMAX) * 8 + IMG_BYTES + 64;
@@ -209,7 +147,6 @@ struct KT {
 };
 
 int gmax_for(int K);  // host view of KT<K>::GMAX (table below)
-int pnw_host(int K) { return pnw_for(K); }
 
 __device__ __forceinline__ double mfma4(double a, double b, double c) {
   return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
@@ -222,20 +159,17 @@ __device__ __forceinline__ d4v mfma16(double a, double b, d4v c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
-// Stores of the large-K intermediates (partial rows, S partials): plain (0), or written through
-// the XCD L2 (1: agent-scope relaxed atomic store = global_store sc1, so their bytes leave L2
-// while the kernel runs instead of at the kernel boundary).  Write-through won 2-3 % at fold0 in
-// round 2, when the large-K kernels ran the headline with c and the S partials among these
-// stores; since round 4 (stream 0 + Y entries) it costs: pass A 3,402 -> 2,776 us at K=30 on 10M
-// links and 152.5 -> 128.3 us at K=20 x 8 with plain stores (profiles/r04p_large_ab.txt), a
-// partial row's K x K words being written as scattered 4 x 16-word pieces.
-#ifndef MMSBM_WT
-#define MMSBM_WT 0
-#endif
-__device__ __forceinline__ void st_wt(double* p, double v) {
-  if constexpr (MMSBM_WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *p = v;
-}
+// The large-K intermediates (partial rows, S partials) are written with plain stores, not through
+// the XCD L2 (agent-scope relaxed atomic store = global_store sc1, whose bytes leave L2 while the
+// kernel runs instead of at the kernel boundary).  Write-through won 2-3 % at fold0 in round 2,
+// when the large-K kernels ran the headline with c and the S partials among these stores; since
+// round 4 (stream 0 + Y entries) it costs: pass A 3,402 -> 2,776 us at K=30 on 10M links and
+// 152.5 -> 128.3 us at K=20 x 8 with plain stores (profiles/r04p_large_ab.txt), a partial row's
+// K x K words being written as scattered 4 x 16-word pieces.  The Y entries are plain stores too
+// (above).  A function, not `*p = v` in place: a call forms the address before the value, an
+// assignment the value first, and pass A's schedule (the code every measurement here was taken
+// with) follows that order.
+__device__ __forceinline__ void st_plain(double* p, double v) { *p = v; }
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -291,8 +225,8 @@ __device__ __forceinline__ double dpp(double v) {
 // that is symmetric under the step's permutation).
 // n / d by v_rcp_f64 and two Newton steps plus a residual correction (within an ulp or two of the
 // IEEE quotient; d > 0 here): 8 FP64 instructions instead of the IEEE division's 11 (scale / fixup
-// sequence), in the chunk loops of sk.h and (MMSBM_PDIV, round 5) pass_kernel.  Deterministic, so
-// results stay bitwise reproducible.
+// sequence), in the chunk loops of sk.h and (round 5: pass A -0.6 % at K=30, -1 % at K=20 x 8,
+// profiles/r05_pdiv_ab.txt) pass_kernel.  Deterministic, so results stay bitwise reproducible.
 __device__ __forceinline__ double sk_div(double n, double d) {
   double r = __builtin_amdgcn_rcp(d);
   r = fma(fma(-d, r, 1.0), r, r);
@@ -300,10 +234,6 @@ __device__ __forceinline__ double sk_div(double n, double d) {
   const double q = n * r;
   return fma(fma(-d, q, n), r, q);
 }
-
-#ifndef MMSBM_PDIV
-#define MMSBM_PDIV 1
-#endif
 
 __device__ __forceinline__ double row16_sum(double v) {
   v += dpp<0xB1>(v);
@@ -327,8 +257,11 @@ enum { PASS_A = 0, PASS_LL = 1, PASS_B = 2 };  // (PASS_B: the small-K family's 
 //   d = eps + th_j . Z,  c = n / d,  Y[entry j] = c Z  (= ntheta_j / th_j),  Y[entry k] = c Z'
 // and per gene stretch the M^0 partial row (K^2) for X^0 and S (gene_kernel).
 // ------------------------------------------------------------------------------------------
+// Occupancy hint 1: the compiler stays free (K = 25-32 take 132-134 VGPRs, so one 8-wave workgroup
+// per CU although the LDS would fit two).  A cap at 128 VGPRs (4 waves per SIMD) costs 3-21
+// spilled VGPRs: K=30 pass A 3,402 us capped vs 3,306 free (profiles/r04p_large_ab.txt).
 template <int K, int MODE>
-__global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K>::WPE))) void pass_kernel(
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1))) void pass_kernel(
     const int4* __restrict__ rows, const int* __restrict__ chunk_prow,
     const int* __restrict__ chunk_vslot, const int* __restrict__ row_y, const int* __restrict__ wg_units,
     const int* __restrict__ wg_code, const int* __restrict__ wg_gene, const int* __restrict__ vgenes,
@@ -345,7 +278,7 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
   const double* __restrict__ th = theta + (size_t)b * P * K;
   Stamp st_{};
   st_.mark(0);
-  const long long wave_id = ((long long)b * gridDim.x + w) * T::NWK + wv;
+  const long long wave_id = ((long long)b * gridDim.x + w) * NW + wv;
 
   const int code = wg_code[w];
   const int r = code & 15;
@@ -362,10 +295,10 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
   // the other lanes read them by readlane / shuffle, so no register array is indexed at run time.
   // Ring of U record registers: the loop below is unrolled U times so each ring slot keeps a
   // fixed register (a rotation by register moves would wait for every load in flight).
-  constexpr int U = T::NWK == 4 ? MMSBM_PNW_U : 6;  // records U - 1 chunks ahead
-  constexpr int DT = T::NWK == 4 ? MMSBM_PNW_DT : 2;  // theta values DT chunks ahead (ring of U slots, DT + 1 live)
+  constexpr int U = 6;   // records U - 1 chunks ahead
+  constexpr int DT = 2;  // theta values DT chunks ahead (ring of U slots, DT + 1 live)
   constexpr bool EM = MODE == PASS_A;
-  const int c0 = wg_units[w * (T::NWK + 1) + wv], c1 = wg_units[w * (T::NWK + 1) + wv + 1];
+  const int c0 = wg_units[w * (NW + 1) + wv], c1 = wg_units[w * (NW + 1) + wv + 1];
   const int* __restrict__ rows_i = reinterpret_cast<const int*>(rows);
   // Every load in the chunk loop is issued by every lane on every path (addresses clamped, values
   // selected afterwards): an exec-masked load behind a branch would make the compiler's vmcnt
@@ -378,15 +311,15 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
   auto ld_rec = [&](int q) -> int { return rbase[(size_t)q * rstride]; };
   auto clampq = [&](int q) { return q < c1 ? q : c1 - 1; };
   const bool any = c0 < c1;
-  // Merged partial rows (Plan::merge, K >= MMSBM_LDS_BIG, where one workgroup runs per CU and the
+  // Merged partial rows (Plan::merge, K >= BIG_K, where one workgroup runs per CU and the
   // registers are there): one row per (workgroup, gene).  A wave's first stretch may continue the
   // previous wave's run (first_cont: its M goes to the workgroup's LDS after the chunk loops) and
   // its last may be continued by the next waves (last_cont: it adds their parts, in wave order,
   // before the one store).
-  constexpr bool MG = EM && K >= MMSBM_LDS_BIG;
+  constexpr bool MG = EM && K >= BIG_K;
   bool first_cont = false, last_cont = false;
   if (MG && merge && any) {
-    const int wc0 = wg_units[w * (T::NWK + 1)], wc1 = wg_units[w * (T::NWK + 1) + T::NWK];
+    const int wc0 = wg_units[w * (NW + 1)], wc1 = wg_units[w * (NW + 1) + NW];
     first_cont = c0 > wc0 && __builtin_amdgcn_readfirstlane(chunk_prow[c0 - 1]) ==
                                  __builtin_amdgcn_readfirstlane(chunk_prow[c0]);
     last_cont = c1 < wc1 && __builtin_amdgcn_readfirstlane(chunk_prow[c1]) ==
@@ -403,33 +336,33 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
     // wg_gene; p_r is staged in the image region when it fits.  All loads go out together.
     const int ng = wg_gene[w + 1] - wg_gene[w];
     const int* __restrict__ vgw = vgenes + (size_t)w * gcap;
-    constexpr bool PV = T::K3 <= T::NWK * T::IMGW;
+    constexpr bool PV = T::K3 <= NW * T::IMGW;
     double* Ps = smem + gcap * T::VDBL + T::tg_dbl(gcap);
-    constexpr int NTG = (T::GMAX * T::KP + T::NTK - 1) / T::NTK, NPV = PV ? (T::K3 + T::NTK - 1) / T::NTK : 1;
+    constexpr int NTG = (T::GMAX * T::KP + NT - 1) / NT, NPV = PV ? (T::K3 + NT - 1) / NT : 1;
     double tg[NTG], pv[NPV];
 #pragma unroll
     for (int i = 0; i < NTG; ++i) {
-      const int idx = tid + T::NTK * i, gl = idx / T::KP, a = idx % T::KP;
+      const int idx = tid + NT * i, gl = idx / T::KP, a = idx % T::KP;
       const int g = vgw[gl < gcap ? gl : 0];
       tg[i] = th[(size_t)g * K + (a < K ? a : 0)];
     }
     if constexpr (PV) {
 #pragma unroll
-      for (int i = 0; i < NPV; ++i) pv[i] = p[tid + T::NTK * i < T::K3 ? tid + T::NTK * i : 0];
+      for (int i = 0; i < NPV; ++i) pv[i] = p[tid + NT * i < T::K3 ? tid + NT * i : 0];
     }
     constexpr int ZR = (T::VROWS - K) * VR;  // rows b >= K read as zero
     if constexpr (ZR > 0)
-      for (int idx = tid; idx < ng * ZR; idx += T::NTK)
+      for (int idx = tid; idx < ng * ZR; idx += NT)
         Vt[(idx / ZR) * T::VDBL + K * VR + idx % ZR] = 0.0;
 #pragma unroll
     for (int i = 0; i < NTG; ++i) {  // theta rows, zero padded
-      const int idx = tid + T::NTK * i, gl = idx / T::KP, a = idx % T::KP;
+      const int idx = tid + NT * i, gl = idx / T::KP, a = idx % T::KP;
       if (idx < gcap * T::KP) Tg[gl * T::TGR + a] = (gl < ng && a < K) ? tg[i] : 0.0;
     }
     if constexpr (PV) {
 #pragma unroll
       for (int i = 0; i < NPV; ++i)
-        if (tid + T::NTK * i < T::K3) Ps[tid + T::NTK * i] = pv[i];
+        if (tid + NT * i < T::K3) Ps[tid + NT * i] = pv[i];
     }
     const double* __restrict__ pv_src = PV ? Ps : p;
     __syncthreads();
@@ -438,7 +371,7 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
     constexpr int CG = (CT + 3) / 4;
     const int GT = (ng + 3) / 4;
     constexpr int GTM = (T::GMAX + 3) / 4;
-    // wave wv owns cell groups (4 cell tiles) cg = wv, wv + T::NWK, ..., CPR per round, for every
+    // wave wv owns cell groups (4 cell tiles) cg = wv, wv + NW, ..., CPR per round, for every
     // gene tile: each p value is loaded once and feeds GT MFMAs (A = the tile's theta rows)
     constexpr int CPR = K <= 12 ? 1 : 2;
     // software pipeline over the rounds: the next round's p values (from L2 when K > 12) are in
@@ -447,8 +380,8 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
     auto v_load = [&](int cr, double (&bv)[CPR][NG], int (&ctv)[CPR]) {
 #pragma unroll
       for (int u = 0; u < CPR; ++u) {
-        const int ct = 4 * (cr + u * T::NWK) + blk;
-        const bool cv = cr + u * T::NWK < CG && ct < CT;
+        const int ct = 4 * (cr + u * NW) + blk;
+        const bool cv = cr + u * NW < CG && ct < CT;
         const int bb = cv ? ct / NG : 0, hh = cv ? 4 * (ct % NG) + lo : 0;
         ctv[u] = cv ? ct : -1;
 #pragma unroll
@@ -479,7 +412,7 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
         }
       }
     };
-    constexpr int CST = CPR * T::NWK;  // cell groups per round (all waves)
+    constexpr int CST = CPR * NW;  // cell groups per round (all waves)
     double bvA[CPR][NG], bvB[CPR][NG];
     int ctA[CPR], ctB[CPR];
     v_load(wv, bvA, ctA);
@@ -517,8 +450,7 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
     for (int t = 0; t < T::NPC; ++t) {
       const int pc = 64 * t + lane;
       const int row8 = pc < 8 * PR ? pc / PR : 0, col = T::SW * (pc % PR);
-      int g = __shfl(rv, (row8 & 3) * 4 + ((row8 >> 2) ? 2 : 1), 64);
-      if constexpr (MMSBM_ABL & 2) g &= 63;
+      const int g = __shfl(rv, (row8 & 3) * 4 + ((row8 >> 2) ? 2 : 1), 64);
       v[t] = *reinterpret_cast<const SV*>(th + (size_t)g * K + (col < K ? col : K - T::SW));
     }
   };
@@ -544,10 +476,10 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
 
   // w of observation hi (its count n_r) of a record register
   auto rec_w = [&](int rr) { return __shfl(rr, hi * 4 + 3, 64); };
-  // VREG (MMSBM_VREG, K >= MMSBM_VREG_MIN = MMSBM_LDS_BIG): the pivot gene's Z / Z' operands of the V table kept in
-  // registers for the whole stretch (reloaded at a gene change) instead of read from LDS per chunk
-  constexpr bool VREG = MMSBM_VREG && K >= MMSBM_VREG_MIN && EM;
-  constexpr bool ZSPLIT = MMSBM_ZSPLIT && K >= MMSBM_VREG_MIN;  // (K = 20: -7 %, r05_zsplit_ab.txt)
+  // VREG (K >= BIG_K): the pivot gene's Z / Z' operands of the V table kept in registers for the
+  // whole stretch (reloaded at a gene change) instead of read from LDS per chunk
+  constexpr bool VREG = K >= BIG_K && EM;
+  constexpr bool ZSPLIT = K >= BIG_K;  // (K = 20: -7 %, r05_zsplit_ab.txt)
   double vz[VREG ? T::NBG : 1][VREG ? NG : 1], vzp[VREG ? T::NBG : 1][VREG ? NG : 1];
   int cur_vs = -1;
   if (any) {
@@ -595,7 +527,7 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
         double dp = 0.0;
 #pragma unroll
         for (int bg = 0; bg < T::NBG; ++bg) {
-          // MMSBM_ZSPLIT: even and odd h steps in two accumulators (shorter dependent MFMA chains)
+          // ZSPLIT: even and odd h steps in two accumulators (shorter dependent MFMA chains)
           double z = 0.0, zo = 0.0;
 #pragma unroll
           for (int hs = 0; hs < NG; ++hs) {
@@ -611,7 +543,7 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
         if constexpr (MODE == PASS_LL) {
           if ((lane & 15) == 0) ll += (double)nw * log(d);
         } else {
-          const double c = MMSBM_PDIV ? sk_div((double)nw, d) : (double)nw / d;
+          const double c = sk_div((double)nw, d);
           // ---- the j- and k-slot sums of this observation (:1009-1011): Y[entry j][b] = c Z[b]
           // and Y[entry k][h] = c Z'[h], Z'[h] = sum_b th_j[b] V[b][h]; 16 lanes of row hi write
           // 16 consecutive words of observation hi's entry
@@ -622,7 +554,7 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
 #pragma unroll
           for (int bg = 0; bg < T::NBG; ++bg) {
             const int bb = 16 * bg + 4 * blk + lo;
-            if (bb < YS && !(MMSBM_ABL & 1)) y_st(yb + (size_t)e1 * YS + bb, c * zb[bg]);
+            if (bb < YS) st_plain(yb + (size_t)e1 * YS + bb, c * zb[bg]);
           }
 #pragma unroll
           for (int hg = 0; hg < T::NBG; ++hg) {
@@ -637,8 +569,7 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
             }
             if (ZSPLIT) z2 += z2o;
             const int hh = 16 * hg + 4 * blk + lo;
-            if (hh < YS && !(MMSBM_ABL & 1)) y_st(yb + (size_t)e2 * YS + hh, c * z2);
-            else if (MMSBM_ABL & 1) ll += z2;  // (keep Z' live)
+            if (hh < YS) st_plain(yb + (size_t)e2 * YS + hh, c * z2);
           }
           // ---- M += c th_u (x) th_v over the chunk's 4 observations: one v_mfma_f64_16x16x4 per
           // 16 x 16 tile of M, k = the 4 observations.  Lane l holds A[x = l & 15][o = l >> 4] =
@@ -681,8 +612,7 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
 #pragma unroll
                   for (int i = 0; i < 4; ++i) {
                     const int x = 16 * tx + hi + 4 * i, y = 16 * ty + col;
-                    if (x < K && y < K && !(MMSBM_ABL & 4)) st_wt(out + x * K + y, m16[tx * NX16 + ty][i]);
-                    else if (MMSBM_ABL & 4) ll += m16[tx * NX16 + ty][i];
+                    if (x < K && y < K) st_plain(out + x * K + y, m16[tx * NX16 + ty][i]);
                     m16[tx * NX16 + ty][i] = 0.0;
                   }
             }
@@ -696,8 +626,8 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
   }
   st_.mark(2);
   if constexpr (MG) {
-    if (merge) {  // (workgroup-uniform) the V tables and images are dead: T::NWK slots of K^2 words
-      static_assert((4 * T::VDBL + T::tg_dbl(4)) * 8 + T::IMG_BYTES >= T::NWK * T::K2 * 8,
+    if (merge) {  // (workgroup-uniform) the V tables and images are dead: NW slots of K^2 words
+      static_assert((4 * T::VDBL + T::tg_dbl(4)) * 8 + T::IMG_BYTES >= NW * T::K2 * 8,
                     "merge slots within the smallest gene cap's LDS");
       const int col = lane & 15;
       __syncthreads();
@@ -715,8 +645,8 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
       __syncthreads();
       if (kept) {
         const int mypr = __builtin_amdgcn_readfirstlane(chunk_prow[c1 - 1]);
-        for (int nx = wv + 1; nx < T::NWK; ++nx) {  // the continuing waves, in order
-          const int n0 = wg_units[w * (T::NWK + 1) + nx], n1 = wg_units[w * (T::NWK + 1) + nx + 1];
+        for (int nx = wv + 1; nx < NW; ++nx) {  // the continuing waves, in order
+          const int n0 = wg_units[w * (NW + 1) + nx], n1 = wg_units[w * (NW + 1) + nx + 1];
           if (n0 == n1) continue;  // (an empty unit)
           if (__builtin_amdgcn_readfirstlane(chunk_prow[n0]) != mypr) break;
 #pragma unroll
@@ -738,25 +668,23 @@ __global__ __launch_bounds__(KT<K>::NTK) __attribute__((amdgpu_waves_per_eu(KT<K
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const int x = 16 * tx + hi + 4 * i, y = 16 * ty + col;
-              if (x < K && y < K) st_wt(out + x * K + y, m16[tx * NX16 + ty][i]);
+              if (x < K && y < K) st_plain(out + x * K + y, m16[tx * NX16 + ty][i]);
             }
       }
     }
   }
-  if constexpr (MMSBM_ABL != 0 && EM)  // ablation builds: keep the skipped stores' values live
-    if (ll == -1.2345e300) partL[0] = ll;
   st_.t[5] = (unsigned long long)(c1 - c0);
   st_.t[4] = (unsigned long long)(wg_gene[w + 1] - wg_gene[w]);
   if constexpr (MODE == PASS_LL) {
     // fixed-order workgroup sum of the log-likelihood terms
-    __shared__ double red[T::NWK];
+    __shared__ double red[NW];
     ll = wave_sum(ll);
     __syncthreads();
     if (lane == 0) red[wv] = ll;
     __syncthreads();
     if (tid == 0) {
       double t = 0.0;
-      for (int q = 0; q < T::NWK; ++q) t += red[q];
+      for (int q = 0; q < NW; ++q) t += red[q];
       partL[(size_t)b * n_wg + w] = t;
     }
   }
@@ -807,17 +735,17 @@ struct GM {
   // in order).  Up to four groups at K = 17-24 (one wave forms a whole X tile, written at the
   // group's last chunk); two at K <= 16, where two waves split each tile's k-steps and add their
   // parts through LDS after the row tile's chunks (two groups' parts fit the freed M tile), and at
-  // K >= MMSBM_LDS_BIG (XPOST below)
+  // K >= BIG_K (XPOST below)
   // X rows written after a row tile's chunks (two groups) where two waves split an X tile's k-steps
-  // (K <= 16) or where one workgroup's S accumulators fill the registers (K >= MMSBM_LDS_BIG: a group
+  // (K <= 16) or where one workgroup's S accumulators fill the registers (K >= BIG_K: a group
   // written at its last chunk cost K = 30 eight spilled VGPRs, 0.7 %); else at each group's last chunk
-  static constexpr bool XPOST = 8 / (4 * NA) == 2 || K >= MMSBM_LDS_BIG;
+  static constexpr bool XPOST = 8 / (4 * NA) == 2 || K >= BIG_K;
   static constexpr int QC = XPOST ? (NCH + 1) / 2 : (NCH + 3) / 4;  // chunks per X group
   static constexpr int NQ = (NCH + QC - 1) / QC;          // X groups (all non-empty)
-  // Q4 (K >= MMSBM_LDS_BIG, plans with fewer parts than CUs, SetDev::gm_q4): the four-group layout
+  // Q4 (K >= BIG_K, plans with fewer parts than CUs, SetDev::gm_q4): the four-group layout
   // of K = 17-24 there too (written at each group's last chunk; its CS = 2 form spills, but such
   // plans run four workgroups per part)
-  static constexpr bool Q4OK = K >= MMSBM_LDS_BIG && 8 / (4 * NA) == 1;
+  static constexpr bool Q4OK = K >= BIG_K && 8 / (4 * NA) == 1;
   static constexpr int QC4 = (NCH + 3) / 4, NQ4 = (NCH + QC4 - 1) / QC4;
   static constexpr int qc(bool q4) { return q4 && Q4OK ? QC4 : QC; }
   static constexpr int nq(bool q4) { return q4 && Q4OK ? NQ4 : NQ; }
@@ -1359,7 +1287,7 @@ struct SetDev {  // device copy of one link set's plan
   int* skrow12 = nullptr;               // slot-major row12 of group 0
   int ncu = 0;                          // CUs the fused plan's unit target came from (0: none)
   int unit_target = 0;
-  bool gm_q4 = false;                   // K >= MMSBM_LDS_BIG: gm_kernel's four-group X layout (GM<K>::Q4OK)
+  bool gm_q4 = false;                   // K >= BIG_K: gm_kernel's four-group X layout (GM<K>::Q4OK)
   void release() {
     void* ps[] = {rows, chunk_prow, chunk_vslot, wg_units, wg_code, wg_gene, vgenes, prow_ptr, prow_gene, sp_desc,
                   row_y, yptr, gptr, sku[0], sku[1], skr[0], skr[1], skrow12};
@@ -1572,13 +1500,13 @@ int launch_pass(mmsbm_ctx* c, int mode, int which, const double* theta, const do
     const int lds = (c->gcap * T::VDBL + T::tg_dbl(c->gcap)) * 8 + T::IMG_BYTES + 64;
     if (mode == PASS_A) {
       if ((rc = lds_opt_in(c, 0, &pass_kernel<K, PASS_A>, T::LDS_A))) return rc;
-      pass_kernel<K, PASS_A><<<dim3(h.n_wg_a, nb_of(c)), T::NTK, lds, s>>>(
+      pass_kernel<K, PASS_A><<<dim3(h.n_wg_a, nb_of(c)), NT, lds, s>>>(
           sd.rows, sd.chunk_prow, sd.chunk_vslot, sd.row_y, sd.wg_units, sd.wg_code, sd.wg_gene, sd.vgenes,
           theta, pr, c->cbuf, c->prows, c->partL, c->P, c->R, h.n_y, h.n_prows, h.n_wg_a, c->eps, c->gcap,
           h.merge ? 1 : 0);
     } else {
       if ((rc = lds_opt_in(c, 1, &pass_kernel<K, PASS_LL>, T::LDS_A))) return rc;
-      pass_kernel<K, PASS_LL><<<dim3(h.n_wg_a, nb_of(c)), T::NTK, lds, s>>>(
+      pass_kernel<K, PASS_LL><<<dim3(h.n_wg_a, nb_of(c)), NT, lds, s>>>(
           sd.rows, sd.chunk_prow, sd.chunk_vslot, nullptr, sd.wg_units, sd.wg_code, sd.wg_gene, sd.vgenes,
           theta, pr, c->cbuf, c->prows, c->partL, c->P, c->R, 0, h.n_prows, h.n_wg_a, c->eps, c->gcap, 0);
     }
@@ -1999,9 +1927,9 @@ int mmsbm_set_links(mmsbm_ctx* c, int32_t which, const int32_t* ids_host, const 
   const char* bal = getenv("MMSBM_BALANCE");
   const bool balance = !(bal && bal[0] == '0');
   // one partial row per (workgroup, gene) where the pass kernel merges its waves' parts (K >=
-  // MMSBM_LDS_BIG); MMSBM_MERGE=0: one per unit stretch (measurement)
+  // BIG_K); MMSBM_MERGE=0: one per unit stretch (measurement)
   const char* mg = getenv("MMSBM_MERGE");
-  const bool merge = !c->sk && c->K >= MMSBM_LDS_BIG && !(mg && mg[0] == '0');
+  const bool merge = !c->sk && c->K >= BIG_K && !(mg && mg[0] == '0');
   // stream-0 partial rows per S partial at large K (each S partial is K^3 words the update sums);
   // MMSBM_SP_ROWS=n overrides it (measurement)
   // gm_kernel (round 5): 128 rows (two 64-row tiles) per part, at most 1,024 parts per rating
@@ -2018,7 +1946,7 @@ int mmsbm_set_links(mmsbm_ctx* c, int32_t which, const int32_t* ids_host, const 
   auto build_plan = [&]() {
     return mmsbm_plan::build(ids_host, counts_host, E, c->R, c->P, em, units_a, units_b, c->gcap, sp_rows,
                              c->sk, 1024, c->sk_fused, mmsbm_plan::sk_gu(c->K), rho, c->sk_y, balance, merge,
-                             sp_cap, pnw_host(c->K));
+                             sp_cap);
   };
   sd.h = build_plan();
   bool small_plan = false;
@@ -2027,7 +1955,7 @@ int mmsbm_set_links(mmsbm_ctx* c, int32_t which, const int32_t* ids_host, const 
     sd.h = build_plan();
     small_plan = true;
   }
-  // such a plan at K >= MMSBM_LDS_BIG also takes gm_kernel's four-group X layout (GM<K>::Q4OK):
+  // such a plan at K >= BIG_K also takes gm_kernel's four-group X layout (GM<K>::Q4OK):
   // one sample runs four workgroups per part there (MMSBM_GM_Q4=0/1 forces the choice)
   const char* q4_env = getenv("MMSBM_GM_Q4");
   const bool gm_q4 = q4_env ? q4_env[0] == '1' : small_plan;

@@ -59,7 +59,9 @@ int fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(MMSBM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-// per-iteration intermediates leave the XCD L2 while the kernel runs (mmsbm.hip, st_wt)
+// per-iteration intermediates leave the XCD L2 while the kernel runs: an agent-scope store
+// (global_store sc1).  (The triplet engine's large-K intermediates are plain stores; mmsbm.hip
+// says why.)
 __device__ __forceinline__ void st_wt(double* p, double v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -32,21 +32,6 @@
 // s summed against theta_g), so nothing waits for another workgroup: pass A's c stores, pass B's c
 // loads and one dependent launch per iteration go away for 2x the Z / d / c work.
 enum { SK_A = 0, SK_LL = 1, SK_B = 2, SK_U = 3 };
-#ifndef MMSBM_SK_TRSWZ
-#define MMSBM_SK_TRSWZ 1  // the Z operand transpose with a bank swizzle (r03u A/B: 38.5k vs 38.1k iter/s)
-#endif
-#ifndef MMSBM_SK_SCOOP
-#define MMSBM_SK_SCOOP 1  // the workgroup's S partial in one cooperative pass (0: per-wave shares + tree)
-#endif
-#ifndef MMSBM_SK_MRED
-#define MMSBM_SK_MRED 0  // 1: d's sum over b on MFMA, four chunks at a time (measured slower than the DPP row sum)
-#endif
-#ifndef MMSBM_SK_PVS
-#define MMSBM_SK_PVS 1  // P^s rows at an odd stride (0: K^2, round 3), see SKT::PVS
-#endif
-#ifndef MMSBM_SK_GHOIST
-#define MMSBM_SK_GHOIST 0  // 1: the first block's theta gathers before the V tables (after the barrier)
-#endif
 
 constexpr int LC = mmsbm_plan::SK_BLOCK;          // chunks of one block (gathered at once)
 constexpr int SK_ROWS = 4 * mmsbm_plan::SK_BLOCK;  // records staged per wave (one block, one per lane)
@@ -63,8 +48,9 @@ struct SKT {
   // up to the last word the unguarded V-operand reads touch: rows a >= K of the 4-wide a tiles,
   // cells up to 16 NCG).  The X contraction's B reads take 16 rows z at once, paired into
   // ds_read2_b64 (16-lane groups, bank (a/4) mod 32): at the K^2 stride (100 at K = 10) rows
-  // z, z + 4, z + 8 shared banks, an odd stride puts the 16 rows on distinct banks.
-  static constexpr int PVS = MMSBM_SK_PVS ? (K2 | 1) : K2;
+  // z, z + 4, z + 8 shared banks, an odd stride puts the 16 rows on distinct banks
+  // (profiles/r04p_pvs_ab.txt).
+  static constexpr int PVS = K2 | 1;
   static constexpr int PVR = (K - 1) * PVS + 16 * NCG;  // (V-operand rows a >= K read row K - 1)
   static constexpr int PSD = ((PVR > K * PVS ? PVR : K * PVS) + 1) & ~1;
   static constexpr int GUK = mmsbm_plan::sk_gu(K);  // stretches per unit (slots per wave): 8 or 4
@@ -78,10 +64,8 @@ struct SKT {
   static constexpr int WAVE_U = WAVE - SK_ROWS;   // fused: no row12 / c staging
   static constexpr int NPV = (PSD + NT - 1) / NT; // staged words per thread
   static constexpr int LDS_U = (PSD + NW * WAVE_U) * 8;
-  static constexpr int NS = NG * NCG;             // S accumulators per lane
   static constexpr int LDS = (PSD + NW * WAVE) * 8;
   static_assert(K <= 12, "small-K kernels: K <= 12");
-  static_assert(4 * NS * 64 <= PSD + NW * WAVE_U, "S reduction buffer over the LDS");
   static_assert(LDS_U <= 80 * 1024, "two fused / likelihood workgroups per CU");
   static_assert(LDS <= 160 * 1024, "pass A LDS");
   static_assert(GUK % 4 == 0 && GUK <= mmsbm_plan::GU, "stretch tiles");
@@ -149,9 +133,6 @@ __global__ __launch_bounds__(NT, 4) void sk_pass_kernel(
   double* __restrict__ xb = xpart + (size_t)b * n_prows * K;
   Stamp st_{};
   st_.mark(0);
-#ifdef MMSBM_SK_EXIT  // measurement builds: leave after phase MMSBM_SK_EXIT (0 = at once)
-  if (MMSBM_SK_EXIT == 0 && b >= 0) return;
-#endif
 
   // P^s_r once per workgroup (every unit of a workgroup has its stream and rating): its loads go
   // out first, so the barrier that publishes it (before the V tables) waits about one round trip.
@@ -227,11 +208,12 @@ __global__ __launch_bounds__(NT, 4) void sk_pass_kernel(
   if constexpr (MODE == SK_B) wave_lds_sync();
   else __syncthreads();
   st_.mark(6);
-#ifdef MMSBM_SK_EXIT
-  if (MMSBM_SK_EXIT == 1 && b >= 0) return;
-#endif
 
-  double sacc[NG][NCG];  // SK_A: this wave's share of S_r[a][cell], a = 4 at + hi
+  // Nothing reads sacc: it held a wave's share of S before the cooperative pass below took over.
+  // The compiler drops it, but without these lines it places one address instruction elsewhere
+  // in the K = 9 and K = 12 SK_U / SK_A kernels, so it stays until a change that is measured on
+  // the device anyway takes it out.
+  double sacc[NG][NCG];
 #pragma unroll
   for (int at = 0; at < NG; ++at)
 #pragma unroll
@@ -273,7 +255,6 @@ __global__ __launch_bounds__(NT, 4) void sk_pass_kernel(
         gv[i] = *reinterpret_cast<const double*>(thb + (__umul24((unsigned)rh[i].y, K * 8u) + cb));
       }
     };
-    if constexpr (MMSBM_SK_GHOIST) gather(c1 < LC ? c1 : LC);  // (in flight during the V tables)
     if constexpr (MODE != SK_B) {
       // ---- V_g[cell] = sum_a theta_g[a] P^s[a][cell] for the unit's genes (m = gene, k = a, B
       // from the staged lattice: rows a >= K meet zero theta, words past K^3 are zero), into slot g
@@ -351,7 +332,7 @@ __global__ __launch_bounds__(NT, 4) void sk_pass_kernel(
         stage_block(bk);
         wave_lds_sync();
       }
-      if (!MMSBM_SK_GHOIST || b0 > 0) gather(nb);
+      gather(nb);
       if (nb > LC) load_block(b0 / LC + 1, bk);  // the next block's records, in flight meanwhile
       if constexpr (MODE != SK_B) {
         // ---- d of every observation of the block.  Per chunk: Z[obs hi][b = col] =
@@ -359,59 +340,23 @@ __global__ __launch_bounds__(NT, 4) void sk_pass_kernel(
         // of the gathered tile, through the wave's LDS; B = the running stretch's V operand, zero for
         // b >= K and h >= K), d = eps + sum_b theta_u[b] Z[b], parked at DL[4 q + obs] (one word per
         // observation = per lane of the wave).  A chunk past the end has zero theta (never used).
-#if MMSBM_SK_MRED
-        // d of a group of 4 chunks: w_u[obs][col] = theta_u[col] Z[col] (zero for col >= K), then
-        // one v_mfma_f64_16x16x4 per chunk against a 0/1 selector, R += w_u E_u with
-        // E_u[k = obs][n] = [n == 4 u + obs], moves chunk u's observation obs to column n = 4 u + obs:
-        // lane (hi, n) receives the columns col = hi + 4 i (i = 0..3) of observation n; summed in
-        // the lane, then over the four rows by two lane swaps (xor 32, then 16: commutative, so
-        // every row gets the same bits).  d of (chunk 4 g + n / 4, obs n % 4) = DL[16 g + n].
-#pragma unroll
-        for (int g4 = 0; g4 < LC / 4; ++g4) {
-          if (4 * g4 < nb) {
-            d4v R = d4v{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const int q = 4 * g4 + u;
-              TRl[lane] = gv[q];  // (h >= K: finite, against zero V)
-              wave_lds_sync();
-              double z = 0.0;
-#pragma unroll
-              for (int hs = 0; hs < NG; ++hs) z = mfma4(TRl[16 * lo + 4 * hs + hi], vb[hs], z);
-              R = mfma16(ga[q] * z, col == 4 * u + hi ? 1.0 : 0.0, R);
-              if (q < nb && ((endm >> q) & 1u)) {  // the next stretch's V operand
-                ++vt;
-                load_v(vt);
-              }
-            }
-            double sr = (R[0] + R[1]) + (R[2] + R[3]);
-            sr += __shfl_xor(sr, 32, 64);
-            sr += __shfl_xor(sr, 16, 64);
-            DL[16 * g4 + col] = sr + eps;
-          }
-        }
-#else  // d by a DPP row sum per chunk (r03s same-box A/B: 38.2k vs 37.4k iter/s with the MFMA sum)
+        // d by a DPP row sum per chunk (r03s same-box A/B: 38.2k iter/s vs 37.4k with the sum over b
+        // on MFMA, four chunks at a time)
 #pragma unroll
         for (int q = 0; q < LC; ++q) {
           if (q < nb) {
-#if MMSBM_SK_TRSWZ  // column swizzle c ^ 4 o (o = the observation row): the compiler pairs the
-                    // reads of hs = 0, 2 into ds_read2_b64, whose 16-lane groups bank on (a/4) mod
-                    // 32, where the 4 rows (16 doubles apart) coincide; c ^ 4 o moves each row to
-                    // its own 8 banks (round 3's c ^ 4 (o >> 1) left rows 0 / 1 and 2 / 3 sharing:
-                    // 56 % of the kernel's LDS conflict cycles, profiles/r05h_lds_attribution.txt)
+            // column swizzle c ^ 4 o (o = the observation row; r03u A/B: 38.5k vs 38.1k iter/s
+            // unswizzled): the compiler pairs the reads of hs = 0, 2 into ds_read2_b64, whose
+            // 16-lane groups bank on (a/4) mod 32, where the 4 rows (16 doubles apart) coincide;
+            // c ^ 4 o moves each row to its own 8 banks (round 3's c ^ 4 (o >> 1) left rows 0 / 1
+            // and 2 / 3 sharing: 56 % of the kernel's LDS conflict cycles,
+            // profiles/r05h_lds_attribution.txt)
             TRl[16 * hi + (col ^ (4 * hi))] = gv[q];
             wave_lds_sync();
             double z = 0.0;
 #pragma unroll
             for (int hs = 0; hs < NG; ++hs)
               z = mfma4(TRl[16 * lo + ((4 * hs + hi) ^ (4 * lo))], vb[hs], z);
-#else
-            TRl[lane] = gv[q];
-            wave_lds_sync();
-            double z = 0.0;
-#pragma unroll
-            for (int hs = 0; hs < NG; ++hs) z = mfma4(TRl[16 * lo + 4 * hs + hi], vb[hs], z);
-#endif
             // (the 16 lanes of a row hold the same bits and store the same word; storing from one
             // lane per row measured no faster, r03u)
             DL[q * 4 + hi] = row16_sum(ga[q] * z) + eps;
@@ -421,7 +366,6 @@ __global__ __launch_bounds__(NT, 4) void sk_pass_kernel(
             }
           }
         }
-#endif
         wave_lds_sync();
         // ---- one observation per lane: c = n / d (or n log d), once per observation instead of
         // once per 16 lanes of it
@@ -489,34 +433,18 @@ __global__ __launch_bounds__(NT, 4) void sk_pass_kernel(
           if (4 * tt + hi < nst && blk < NG && z < K) xb[(size_t)un.prow[tt] * K + z] = xacc;
         }
       }
-      if (!MMSBM_SK_SCOOP && (MODE == SK_A || (MODE == SK_U && s == 0))) {
-        // ---- S_r[a][cell] += sum_q theta_{g_q}[a] M_q[cell] (m = a, k = q, n = cell), the
-        // unit's row tiles in order
-#pragma unroll
-        for (int tt = 0; tt < NT2; ++tt) {
-          if (tt == 0 || nst > 4 * tt) {
-#pragma unroll
-            for (int cg = 0; cg < NCG; ++cg) {
-              // (ts is zero for q >= nst; cells >= K^2 are not stored)
-              const double mb = MSl[(4 * tt + hi) * SLOT + 4 * (4 * cg + blk) + lo];
-#pragma unroll
-              for (int at = 0; at < NG; ++at)  // A: theta_{g_q}[4 at + lo] for q = 4 tt + hi
-                sacc[at][cg] = mfma4(THl[(4 * tt + hi) * 4 * NG + 4 * at + lo], mb, sacc[at][cg]);
-            }
-          }
-        }
-      }
       st_.mark(3);
     }
   }
 
-#if MMSBM_SK_SCOOP
   if (MODE == SK_A || (MODE == SK_U && s == 0)) {  // (workgroup-uniform)
     // ---- the workgroup's S partial in one pass over all its stretches: S_r[a][cell] =
     // sum_q theta_{g_q}[a] M_q[cell] over the rows q = (wave, slot) of every wave, in that order
     // (m = a, k = q, n = cell; A from the waves' pivot theta rows, B from their M rows).  Rows of
     // absent stretches are zero (V zeros, zero theta); an empty slot zeroes its own first.  One
-    // barrier, then each wave takes (a tile, cell group) items and stores its cells directly.
+    // barrier, then each wave takes (a tile, cell group) items and stores its cells directly
+    // (41.8k iter/s vs 41.1k with per-wave shares added by a 3-barrier tree,
+    // profiles/r03z_scoop_ab.txt).
     constexpr int WV = MODE == SK_U ? T::WAVE_U : T::WAVE;
     if (un.nst == 0) {
 #pragma unroll
@@ -554,44 +482,6 @@ __global__ __launch_bounds__(NT, 4) void sk_pass_kernel(
       if (it < NI && a < K && cell < K2) out[a * K2 + cell] = acc[j];
     }
   }
-#else
-  if (MODE == SK_A || (MODE == SK_U && s == 0)) {  // (workgroup-uniform)
-    // ---- the workgroup's S partial: the 8 waves' shares added in a fixed order,
-    // ((w0 + w4) + (w2 + w6)) + ((w1 + w5) + (w3 + w7)), through LDS: waves 4-7 park theirs, waves
-    // 0-3 add them to their own and park the pair sums, then every thread combines the four pairs
-    // for its share of the K^3 partial and stores it
-    constexpr int NE = NG * NCG * 64;  // (a tile, cell group, lane) entries of one share
-    double* red = smem;
-    auto put = [&](int slot) {
-#pragma unroll
-      for (int at = 0; at < NG; ++at)
-#pragma unroll
-        for (int cg = 0; cg < NCG; ++cg) red[slot * NE + (at * NCG + cg) * 64 + lane] = sacc[at][cg];
-    };
-    __syncthreads();
-    if (wv >= 4) put(wv - 4);
-    __syncthreads();
-    if (wv < 4) {
-#pragma unroll
-      for (int at = 0; at < NG; ++at)
-#pragma unroll
-        for (int cg = 0; cg < NCG; ++cg) sacc[at][cg] += red[wv * NE + (at * NCG + cg) * 64 + lane];
-      put(wv);
-    }
-    __syncthreads();
-    double* __restrict__ out = spart + ((size_t)b * n_wg + w) * K3;
-#pragma unroll
-    for (int i = 0; i < (NE + NT - 1) / NT; ++i) {
-      const int e = tid + NT * i;
-      if (e < NE) {
-        const int l = e & 63, ac = e >> 6;
-        const int a = 4 * (ac / NCG) + (l >> 4), cell = 4 * (4 * (ac % NCG) + ((l >> 2) & 3)) + (l & 3);
-        const double v = (red[e] + red[2 * NE + e]) + (red[NE + e] + red[3 * NE + e]);
-        if (a < K && cell < K2) out[a * K2 + cell] = v;
-      }
-    }
-  }
-#endif
   if constexpr (MODE == SK_LL) {
     __shared__ double redl[NW];
     ll = wave_sum(ll);
@@ -1003,12 +893,6 @@ __global__ __launch_bounds__(SKF_NT) void sk_fin_kernel(
   const int wgx = blockIdx.x;
   Stamp st_{};
   st_.mark(0);
-#ifdef MMSBM_FIN_EMPTY  // measurement builds only (results invalid): the launch without its work
-  if (b >= 0) return;
-#endif
-#ifdef MMSBM_FIN_ONLY  // measurement builds only (results invalid): 1 = gene workgroups only, 2 = cell only
-  if ((MMSBM_FIN_ONLY == 1) != (wgx < n_gene_wg)) return;
-#endif
   if (wgx < n_gene_wg && ybuf) {
     constexpr int LPX = 64 / K, LY = K * LPX, YU = 16;  // lanes per component, lanes used
     const int lane = tid & 63, wv = tid >> 6;
