@@ -264,6 +264,45 @@ int mmsbm_pair_census(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known
                       const double *thresholds, int32_t M, void *ws, int64_t ws_bytes,
                       int32_t *out_counts, void *stream);
 
+/* Threshold scan: every one of the scan's eligible triples whose score is at or above one threshold,
+ * listed.  The census says how many there are; this call says which.  order, known, n_known, theta,
+ * pr, sample (-1: the mean over the active prefix), ws and stream mean what they mean for
+ * mmsbm_scan_census; a triple is eligible exactly as there (rank positions a < b < c < P whose
+ * packed key is not among `known`), and its score carries the same bits (one score phase serves the
+ * scan, the censuses and this call).  A hit is an eligible triple with score >= threshold, so the
+ * number of hits is exactly mmsbm_scan_census's count at that threshold.
+ * Result (device): *out_count int64[1] = the number of hits, always the full number, also when it
+ * exceeds `capacity`.  The first min(*out_count, capacity) rows of out_scores f64[capacity] and
+ * out_keys int64[capacity] hold hits: the score and the packed key (a P + b) P + c (gene ids:
+ * order[a], order[b], order[c]).  The rows come in ARRIVAL order, which follows the grid and the run
+ * and may differ between two calls: only the SET of rows is defined.  When *out_count <= capacity it
+ * is the complete set of hits, each exactly once; sorted under the scan's total order (score
+ * descending; equal scores: smaller packed key first) it is a unique list that does not depend on
+ * the grid, the device or the batch the sample sits in, and its first N rows are mmsbm_scan_topn's
+ * list for that N, bit for bit.  When *out_count > capacity the rows are `capacity` distinct hits,
+ * which ones is not defined; call again with capacity >= *out_count.  Rows from
+ * min(*out_count, capacity) on are not touched: no address past row capacity - 1 is ever formed.
+ * capacity = 0 is a count-only call; out_scores and out_keys may then be NULL.
+ * The rows are placed by integer means only (ballots, popcounts, a wave's staging buffer of 256
+ * rows in LDS and one 64-bit atomic add per flush of it on a cursor in the workspace, which the
+ * call zeroes on `stream`); no floating-point value is combined anywhere.
+ * Checked before any device call: a NULL ctx, order, theta, pr or out_count, a NULL output array
+ * with capacity > 0, a NaN or infinite threshold, capacity < 0, a bad sample, a bad known-key table
+ * or a missing, misaligned or small workspace: MMSBM_ERR_INVALID; K outside [1, MMSBM_MAX_K],
+ * P above 2 000 000 (the packed key) or an ensemble whose W tile exceeds the LDS (as for the census):
+ * MMSBM_ERR_UNSUPPORTED.  P < 3: *out_count = 0.  The list itself has no cap but the caller's memory
+ * (16 bytes per row).
+ * ws: mmsbm_scan_above_workspace_bytes(ctx) bytes of device scratch, 16-byte aligned, the caller's;
+ * its size follows the context's shape only.  theta and pr are only read; all launches go to
+ * `stream` and nothing synchronises.  The environment variable MMSBM_SCAN_ABOVE_GRID=<workgroups>
+ * overrides the grid (measurement; the set of rows does not depend on it).  Needs R >= 2.  Replaces
+ * nothing in the reference. */
+int mmsbm_scan_above_workspace_bytes(const mmsbm_ctx *ctx, int64_t *bytes);
+int mmsbm_scan_above(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known, int64_t n_known,
+                     const double *theta, const double *pr, int32_t sample, double threshold,
+                     int64_t capacity, void *ws, int64_t ws_bytes, double *out_scores,
+                     int64_t *out_keys, int64_t *out_count, void *stream);
+
 /* Link-sharded iteration (single sample over N ranks): each rank's context
  * holds 1/N of the train links (mmsbm_set_links) and the GLOBAL degree (mmsbm_set_degree).
  * Step 1, the accumulation half of make_iteration (:986-1012) over this rank's links:

@@ -66,6 +66,7 @@ class EMEngine:
         self._partners_ws = None  # partners_top's scratch
         self._census_ws = None    # census's scratch
         self._pair_census_ws = None   # pair_census's scratch
+        self._scan_above_ws = None    # scan_above's scratch
         self.theta = torch.zeros((self.B, self.P, self.K), dtype=torch.float64, device=self.device)
         self.pr = torch.zeros((self.B, self.R, self.K3), dtype=torch.float64, device=self.device)
 
@@ -342,6 +343,95 @@ class EMEngine:
         if stream is not None:
             stream.synchronize()
         return counts.cpu().numpy(), int(total.cpu()[0])
+
+    # -------------------------------------------------------- threshold scan
+    def _scan_above(self, threshold, known, sample, stream, limit):
+        """-> (scores f64[n] and packed keys int64[n] on the device, sorted by the scan's total
+        order; the kernel's count int64[1] on the device; the census's count n; the launch stream)."""
+        from .scan import LimitError
+        threshold = float(threshold)
+        if not np.isfinite(threshold):
+            raise ValueError("the threshold must be a finite number")
+        counts, _ = self.census_async([threshold], known, sample, stream)    # validates known and sample
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(s):
+            n = int(counts.cpu()[0])        # the same score bits: exactly the rows the kernel will find
+        if n > int(limit):
+            raise LimitError(n, int(limit))
+        known = np.zeros(0, np.int64) if known is None else np.ascontiguousarray(known, dtype=np.int64)
+        nbytes = ctypes.c_int64()
+        _lib.check(self.lib.mmsbm_scan_above_workspace_bytes(self.ctx, ctypes.byref(nbytes)))
+        if self._scan_above_ws is None or self._scan_above_ws.numel() < nbytes.value:
+            self._scan_above_ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        with torch.cuda.stream(s):      # the tensors below belong to the stream the kernels run on
+            known_d = torch.from_numpy(known).to(self.device)
+            scores = torch.empty(n, dtype=torch.float64, device=self.device)
+            keys = torch.empty(n, dtype=torch.int64, device=self.device)
+            found = torch.empty(1, dtype=torch.int64, device=self.device)
+            _lib.check(self.lib.mmsbm_scan_above(
+                self.ctx, _ptr(self._scan_order), _ptr(known_d) if known.size else None, int(known.size),
+                _ptr(self.theta), _ptr(self.pr), -1 if sample is None else int(sample), threshold, n,
+                _ptr(self._scan_above_ws), self._scan_above_ws.numel(), _ptr(scores) if n else None,
+                _ptr(keys) if n else None, _ptr(found), s.cuda_stream))
+            # the rows arrive in any order; two stable sorts give the scan's: score descending,
+            # equal scores by key ascending
+            keys, at = torch.sort(keys, stable=True)
+            scores = scores[at]
+            scores, at = torch.sort(scores, descending=True, stable=True)
+            keys = keys[at]
+        return scores, keys, found, n, s
+
+    def _keys_to_ids(self, keys: torch.Tensor) -> torch.Tensor:
+        """Packed keys int64[n] (device) -> gene ids int32[n][3] in key order."""
+        P = max(self.P, 1)
+        order = self._scan_order
+        return torch.stack([order[keys // (P * P)], order[(keys // P) % P], order[keys % P]], dim=1)
+
+    def scan_above_async(self, threshold, known: np.ndarray = None, sample: int = None, stream=None,
+                         limit: int = 1 << 26):
+        """scan_above without the host copy: -> device tensors (scores f64[n], ids int32[n][3]) on
+        the launch stream.  The number of rows comes from the census first (one host read of one
+        integer); a count above `limit` raises before anything is launched for the list."""
+        scores, keys, _, _, s = self._scan_above(threshold, known, sample, stream, limit)
+        with torch.cuda.stream(s):
+            return scores, self._keys_to_ids(keys)
+
+    def scan_above(self, threshold, known: np.ndarray = None, sample: int = None, stream=None,
+                   limit: int = 1 << 26):
+        """Every eligible triple (those scan_top ranks: distinct genes, key not in `known`) whose
+        score is >= threshold (include/mmsbm.h mmsbm_scan_above): -> (scores f64[n], ids int32[n][3]
+        in key order) on the host, sorted by the scan's total order (score descending, equal scores
+        by packed key ascending), n = census([threshold]).  The scores are scan_top's bit for bit, so
+        the first rows are scan_top's list.  A NaN or infinite threshold raises ValueError, as does a
+        count above `limit` (scan.LimitError, with the count and the limit): 16 bytes per row on the
+        device, twice that while sorting.  known, sample: as for scan_top."""
+        scores, keys, found, n, s = self._scan_above(threshold, known, sample, stream, limit)
+        with torch.cuda.stream(s):
+            ids = self._keys_to_ids(keys).cpu().numpy()
+            scores, found = scores.cpu().numpy(), int(found.cpu()[0])
+        assert found == n, "mmsbm_scan_above found %d rows where the census counted %d" % (found, n)
+        return scores, ids
+
+    def scan_top_any(self, n: int, known: np.ndarray = None, sample: int = None, limit: int = 1 << 26):
+        """scan_top for any n >= 1: -> (scores f64[n'], ids int32[n'][3]) on the host, best first,
+        n' <= n.  Up to mmsbm_scan_max_n() it is scan_top; above, censuses bracket a threshold
+        between the eligible total and the last score of scan_top(max) (scan.bracket_threshold),
+        scan_above fetches what lies at or above it and the list is cut to n.  Exact: the three
+        kernels see the same score bits under the same total order.  `limit`: as for scan_above
+        (reached only when more than that many triples tie around rank n)."""
+        from .scan import bracket_threshold
+        n = int(n)
+        if n < 1:
+            raise ValueError("scan_top_any needs n >= 1")
+        max_n = int(self.lib.mmsbm_scan_max_n())
+        if n <= max_n:
+            return self.scan_top(n, known, sample)
+        scores, ids = self.scan_top(max_n, known, sample)
+        if scores.size < max_n:         # fewer eligible triples than that: this is all of them
+            return scores, ids
+        lo = bracket_threshold(n, float(scores[-1]), lambda t: self.census(t, known, sample)[0])
+        scores, ids = self.scan_above(lo, known, sample, limit=limit)
+        return scores[:n], ids[:n]
 
     # ----------------------------------------------------------- pair census
     def _pair_census_rank(self, thresholds, known, sample, stream):

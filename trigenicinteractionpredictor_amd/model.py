@@ -426,6 +426,26 @@ class Model:
         return [[float(p), "_".join(str(int(g)) for g in row), sorted(self.id_gene[int(g)] for g in row)]
                 for p, row in zip(scores, ids)]
 
+    def predict_novel_any(self, n, exclude=("train", "test")):
+        """predict_novel for any n >= 1: above the scan's cap of 4096 rows, censuses bracket the
+        score of rank n and one threshold scan fetches what lies at or above it
+        (engine.scan_top_any).  Up to the cap it is predict_novel."""
+        from .scan import known_keys
+        scores, ids = self._push().scan_top_any(int(n), known_keys(self, exclude), sample=0)
+        return self._rows(scores, ids)
+
+    def predict_network(self, threshold=0.5, exclude=("train", "test"), limit=1 << 26):
+        """Every triple of distinct genes outside the `exclude`d link tables with
+        P(r = 1) >= threshold, best first, equal probabilities by key: the predicted trigenic
+        network at that cut, in predict_novel's row format.  novel_census([threshold]) is its
+        length; more than `limit` rows raise ValueError (scan.LimitError) before the list is
+        formed.  One census and one threshold scan of all C(P, 3) triples on the GPU
+        (engine.scan_above)."""
+        from .scan import known_keys
+        scores, ids = self._push().scan_above(float(threshold), known_keys(self, exclude), sample=0,
+                                              limit=limit)
+        return self._rows(scores, ids)
+
     def _gene_arg(self, gene):
         """A gene id or name as do_prediction takes them -> id in [0, P) (IndexError like :537)."""
         try:

@@ -45,6 +45,16 @@ against the whole array, is which pair to build next.
                            at or above each of --thresholds (default DEFAULT_THRESHOLDS), from the
                            highest threshold down.
 
+One more comes from the threshold scan (`EMEngine.scan_above`, mmsbm_scan_above), which lists what
+the census counts: the predicted trigenic network at a probability cut.
+    --network FILE         every eligible triple (under --exclude, scored by --best or the ensemble
+                           mean) with P(r = 1) >= --network-threshold T (default 0.5, in (0, 1]), as
+                           rank, probability, ids, names rows, best first, equal probabilities by key:
+                           the main table's columns without the main table's cap.  Its row count is
+                           the --census count at T.  More than --network-limit ROWS (default
+                           10,000,000) of them is refused, with the count, before anything is
+                           written.
+
 Exactness: the counts are exact for the scan's score bits.  A listed triple's probability comes from
 the predict kernel, which sums in another order, so a triple within rounding distance (about 1e-12
 relative) of another triple's score may be placed on either side of it.  (Listed triples are
@@ -64,6 +74,8 @@ MAX_PARTNER_TOP = 1024   # mmsbm_partners_max_n(): the largest N per query gene
 MAX_CENSUS_M = 1024      # mmsbm_census_max_m(): the most thresholds one census call takes
 MAX_PAIR_CENSUS_M = 8    # mmsbm_pair_census_max_m(): the most thresholds one pair census call takes
 DEFAULT_PAIR_THRESHOLD = 0.5   # --pairs without --pair-threshold
+DEFAULT_NETWORK_THRESHOLD = 0.5    # --network without --network-threshold
+DEFAULT_NETWORK_LIMIT = 10000000   # --network without --network-limit: the most rows it writes
 DEFAULT_THRESHOLDS = (0.99, 0.95, 0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3, 0.2, 0.1, 0.05, 0.02, 0.01, 0.005,
                       0.002, 0.001)   # --census without --thresholds
 
@@ -197,6 +209,58 @@ def census_unsort(parts, perm) -> np.ndarray:
     return out
 
 
+# ----------------------------------------------------------------------------- threshold scan
+class LimitError(ValueError):
+    """A threshold scan would return more rows than its limit; nothing was launched for the list."""
+
+    def __init__(self, count: int, limit: int):
+        super().__init__("%d triples score at or above the threshold, more than the limit of %d rows: "
+                         "raise the threshold or the limit" % (count, limit))
+        self.count, self.limit = int(count), int(limit)
+
+
+def bracket_threshold(n: int, hi: float, count_at, max_m: int = MAX_CENSUS_M) -> float:
+    """The threshold scan_top_any fetches above: -> lo with count(lo) >= n, as close above n as
+    censuses can bring it.  count_at(thresholds) -> the census's counts (scores >= each); `hi` is a
+    score that at least one and fewer than n eligible triples reach unless scores tie (the last
+    score of scan_top(max)); scores are probabilities, so count(0.0) is the eligible total.
+    From (0.0, hi), each pass puts up to max_m evenly spaced thresholds strictly inside (lo, hi)
+    and keeps the adjacent pair with count(lo') >= n > count(hi').  It stops when count(lo) <=
+    n + max(n // 8, 4096), or when no double lies strictly between lo and hi: what then remains
+    above n at lo are ties of the score next above lo.  Pure: no GPU, no state."""
+    n, lo, hi = int(n), 0.0, float(hi)
+    c_lo, c_hi = (int(c) for c in count_at(np.array([lo, hi])))
+    if c_lo <= n or hi <= lo:       # everything
+        return lo
+    if c_hi >= n:                   # ties at hi reach rank n: nothing above hi holds n rows
+        return hi
+    while c_lo > n + max(n // 8, 4096):
+        grid = np.unique(np.linspace(lo, hi, int(max_m) + 2)[1:-1])
+        grid = grid[(grid > lo) & (grid < hi)]
+        if not grid.size:           # adjacent doubles
+            break
+        counts = np.asarray(count_at(grid), dtype=np.int64)
+        pts = np.concatenate([[lo], grid, [hi]])
+        cnt = np.concatenate([[c_lo], counts, [c_hi]])
+        j = int(np.flatnonzero(cnt >= n)[-1])       # counts do not increase with the threshold
+        lo, c_lo, hi, c_hi = float(pts[j]), int(cnt[j]), float(pts[j + 1]), int(cnt[j + 1])
+    return lo
+
+
+def parse_network_threshold(text) -> float:
+    """'0.5' -> 0.5; ValueError unless it is one number in (0, 1]."""
+    v = float(text)
+    if not 0.0 < v <= 1.0:      # NaN fails the comparison
+        raise ValueError("network threshold outside (0, 1]")
+    return v
+
+
+def network_rows(id_gene, scores, ids):
+    """scan_above's arrays -> the main table's rows [rank, probability, "i_j_k", names]."""
+    return [[i + 1, float(p), "_".join(str(int(g)) for g in row), sorted(id_gene[int(g)] for g in row)]
+            for i, (p, row) in enumerate(zip(scores, ids))]
+
+
 def pair_eligible(P: int, known=None) -> np.ndarray:
     """int32 [P][P] in gene ids: the eligible triples of every pair of genes, P - 2 minus the number
     of `known` keys (sorted packed keys of rank positions, scan.known_keys) that contain the pair;
@@ -311,6 +375,9 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [--pairs=] <TSV file: the --top gene pairs with the most eligible triples at or above T>
     [--pair-threshold=] <T, a float in (0, 1]; default 0.5>
     [--gene-census=] <TSV file: per gene, its eligible triples at or above each of --thresholds>
+    [--network=] <TSV file: every eligible triple at or above T, best first>
+    [--network-threshold=] <T, a float in (0, 1]; default 0.5>
+    [--network-limit=] <the most rows --network may write; default 10000000>
 """
 
 
@@ -321,12 +388,15 @@ def parse(argv):
     cfg = dict(cli.DEFAULTS, samples=1, iterations=100, top=100, exclude=SETS, best=False, out=None,
                seed=None, genes=[], all_genes=False, census=None, thresholds=None, heldout_ranks=None,
                pairs=None, pair_threshold=DEFAULT_PAIR_THRESHOLD, gene_census=None)
+    # --network adds its three keys (network, network_threshold, network_limit, the latter two with
+    # their defaults) only when one of its options is given: without them cfg is what it always was
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
                                                         "best", "out=", "gene=", "all-genes", "census=",
                                                         "thresholds=", "heldout-ranks=", "pairs=",
-                                                        "pair-threshold=", "gene-census="])
+                                                        "pair-threshold=", "gene-census=", "network=",
+                                                        "network-threshold=", "network-limit="])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -371,6 +441,19 @@ def parse(argv):
                 except ValueError:
                     print("\n\nERROR: --pair-threshold should be a number in (0, 1]")
                     raise cli.ArgError()
+            elif opt == "--network":
+                cfg["network"] = arg
+            elif opt == "--network-threshold":
+                try:
+                    cfg["network_threshold"] = parse_network_threshold(arg)
+                except ValueError:
+                    print("\n\nERROR: --network-threshold should be a number in (0, 1]")
+                    raise cli.ArgError()
+            elif opt == "--network-limit":
+                if not int(arg) >= 1:
+                    print("\n\nERROR: --network-limit should be an integer number of rows >= 1")
+                    raise cli.ArgError()
+                cfg["network_limit"] = int(arg)
             elif opt == "--thresholds":
                 try:
                     cfg["thresholds"] = parse_thresholds(arg)
@@ -385,6 +468,10 @@ def parse(argv):
                 cfg = cli.parse([opt, arg], cfg)
         except ValueError:
             raise cli.ArgError()
+    if any(key in cfg for key in ("network", "network_threshold", "network_limit")):
+        cfg.setdefault("network", None)
+        cfg.setdefault("network_threshold", DEFAULT_NETWORK_THRESHOLD)
+        cfg.setdefault("network_limit", DEFAULT_NETWORK_LIMIT)
     if cfg["genes"] and cfg["all_genes"]:
         print("\n\nERROR: --gene and --all-genes exclude each other")
         raise cli.ArgError()
@@ -435,12 +522,30 @@ def pair_tables(eng, model, cfg, sample, extras):
         extras["gene_census"] = (thresholds, [model.id_gene[g] for g in range(model.P)], counts)
 
 
+def network_table(eng, model, cfg, sample, extras):
+    """The driver's --network table into `extras` (see run); cli.ArgError when it would hold more
+    rows than --network-limit."""
+    from . import cli
+    if not cfg.get("network"):
+        return
+    try:
+        scores, ids = eng.scan_above(cfg["network_threshold"], known_keys(model, cfg["exclude"]), sample,
+                                     limit=cfg["network_limit"])
+    except LimitError as e:
+        eng.close()
+        print("\n\nERROR: --network: %d triples have a probability of %r or more, above --network-limit %d: "
+              "raise --network-threshold (or the limit)" % (e.count, cfg["network_threshold"], e.limit))
+        raise cli.ArgError()
+    extras["network"] = network_rows(model.id_gene, scores, ids)
+
+
 def run(cfg, out=print, extras=None):
     """Fit the restarts as one batch, scan once, return the rows [rank, probability, ids, names]
     (with --gene / --all-genes: [query, rank, probability, ids, names], by query then rank).
     extras: a dict that receives "census" = (thresholds, counts, total) and "heldout_ranks" = rows
     when cfg asks for them (--census, --heldout-ranks), and "pairs" = rows [count, eligible, ids,
-    names] and "gene_census" = (thresholds, names, counts int64[P][M]) for --pairs, --gene-census."""
+    names] and "gene_census" = (thresholds, names, counts int64[P][M]) for --pairs, --gene-census, and
+    "network" = rows [rank, probability, ids, names] for --network."""
     from .model import Model
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
@@ -460,6 +565,7 @@ def run(cfg, out=print, extras=None):
     if extras is not None:
         census_tables(eng, model, cfg, sample, extras)
         pair_tables(eng, model, cfg, sample, extras)
+        network_table(eng, model, cfg, sample, extras)
     if queries is not None:
         out("partner pairs of %d genes: %s" % (len(queries), "sample %d" % sample if sample is not None
                                                else "mean of %d samples" % B))
@@ -537,6 +643,9 @@ def main(argv=None, out=print):
     if "gene_census" in extras:
         with open(cfg["gene_census"], "w", encoding="utf-8") as f:
             write_gene_census_tsv(*extras["gene_census"], f)
+    if "network" in extras:
+        with open(cfg["network"], "w", encoding="utf-8") as f:
+            write_tsv(extras["network"], f)
     partners = bool(cfg["genes"] or cfg["all_genes"])
     if cfg["out"]:
         with open(cfg["out"], "w", encoding="utf-8") as f:
