@@ -145,7 +145,8 @@ int mmsbm_predict(mmsbm_ctx *ctx, const int32_t *ids, int64_t n, const double *t
  * smaller packed key first); *out_count < N when fewer are eligible (P < 3: 0); the tail is
  * NaN / -1.  That list is unique, so it does not depend on the grid, the device or the batch the
  * sample sits in.  1 <= N <= mmsbm_scan_max_n() (4096); above it MMSBM_ERR_UNSUPPORTED, as for an
- * ensemble whose W tile exceeds the LDS (n_active (K + 5) > 512: scan the slots one by one).
+ * ensemble whose W tile of 16 rows exceeds 64 KiB of LDS: n_active (4 ceil(K / 4) + 2) > 512 (scan
+ * the slots one by one).
  * ws: mmsbm_scan_workspace_bytes(ctx, N) bytes of device scratch, 16-byte aligned, the caller's
  * (independent of mmsbm_set_workspace).  theta and pr are only read; all launches go to `stream`
  * and nothing synchronises.  Needs R >= 2.  The caller guarantees that order is a permutation of

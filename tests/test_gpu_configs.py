@@ -162,7 +162,7 @@ def test_config4_all_train_multicount_K10_batch8(tmp_path):
     assert eng.loglik(1).tolist() == [0.0] * 8        # empty test set
 
 
-@pytest.mark.parametrize("K", [13, 20, 30, 32])
+@pytest.mark.parametrize("K", [13, 20, 23, 25, 30, 32])
 def test_prediction_large_K(tmp_path, K):
     """`do_prediction` (:530-547) through the batched prediction kernel at K > 10."""
     from oracle import c_oracle

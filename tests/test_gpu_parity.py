@@ -116,6 +116,80 @@ def test_against_c_oracle(tmp_path, K, P, E, iters):
     np.testing.assert_allclose(m.compute_likelihood("test"), LT_o, rtol=RTOL)
 
 
+def _every_k_sizes(K):
+    """(P, E) as test_gpu_ratings.sizes: smaller at large K, where the oracle's E K^3 R loop sets
+    the test's time."""
+    return (150, 2500) if K <= 12 else (100, 1200) if K < 25 else (60, 600)
+
+
+@pytest.mark.parametrize("K", range(1, 33))
+def test_every_k_matches_oracle(tmp_path, K):
+    """kTable instantiates the pass, gene and update kernels, the small-K family, the likelihood
+    and the prediction kernels for every K in 1..32: each of them, in the default family with one
+    sample, against the C oracle after 2 iterations (theta, p, train and held-out likelihood, 200
+    random predictions)."""
+    from oracle import c_oracle
+    P, E = _every_k_sizes(K)
+    tr, te = _fold(tmp_path, P, E, seed=200 + K, multi_frac=0.05, both_frac=0.02)
+    m = _gpu_model(tr, te)
+    random.seed(K)
+    m.initialize_parameters(K)
+    theta0, pr0 = np.array(m.theta), np.array(m.pr)
+    m.make_iterations(2)
+    assert m._engine.plan_info()["small_k"] == (2 if K <= 12 else 0)
+    th_o, pr_o, L_o, LT_o = _oracle_run(m, theta0, pr0, 2)
+    np.testing.assert_allclose(np.array(m.theta), th_o, rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(np.array(m.pr), pr_o, rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(m.compute_likelihood("train"), L_o, rtol=RTOL)
+    np.testing.assert_allclose(m.compute_likelihood("test"), LT_o, rtol=RTOL)
+    ids = np.random.default_rng(K).integers(0, m.P, (200, 3)).astype(np.int32)
+    got = m._engine.predict(ids)
+    assert got.shape == (1, 200)
+    th, pr = m._engine.download()
+    np.testing.assert_allclose(got[0], c_oracle.predict(ids, th[0], pr[0]), rtol=RTOL, atol=ATOL)
+
+
+@pytest.mark.parametrize("K", range(1, 33))
+def test_every_k_batch_of_two_matches_oracle(tmp_path, K):
+    """The same over every K with B = 2, per sample: SK_Y up to K = 12, the batched large-K
+    kernels above."""
+    from oracle import c_oracle
+    from trigenicinteractionpredictor_amd import EMEngine
+    from trigenicinteractionpredictor_amd.layout import links_to_arrays
+    P, E = _every_k_sizes(K)
+    tr, te = _fold(tmp_path, P, E, seed=200 + K, multi_frac=0.05, both_frac=0.02)
+    m = _gpu_model(tr, te)
+    random.seed(K + 50)
+    thetas, prs = [], []
+    for _ in range(2):
+        m.initialize_parameters(K)
+        thetas.append(np.array(m.theta))
+        prs.append(np.array(m.pr))
+    eng = EMEngine(K, m.P, B=2)
+    ids, counts = links_to_arrays(m.links)
+    tids, tcounts = links_to_arrays(m.test_links)
+    eng.set_links(0, ids, counts)
+    eng.set_links(1, tids, tcounts)
+    eng.upload(np.stack(thetas), np.stack(prs))
+    eng.iterate(2)
+    assert eng.plan_info()["small_k"] == (3 if K <= 12 else 0)
+    th, pr = eng.download()
+    L, LT = eng.loglik(0), eng.loglik(1)
+    pick = np.random.default_rng(K).integers(0, m.P, (200, 3)).astype(np.int32)
+    got = eng.predict(pick)
+    assert got.shape == (2, 200)
+    for b in range(2):
+        th_o, pr_o = thetas[b], prs[b]
+        for _ in range(2):
+            th_o, pr_o = c_oracle.make_iteration(ids, counts, th_o, pr_o)
+        np.testing.assert_allclose(th[b], th_o, rtol=RTOL, atol=ATOL)
+        np.testing.assert_allclose(pr[b], pr_o, rtol=RTOL, atol=ATOL)
+        np.testing.assert_allclose(L[b], c_oracle.loglik(ids, counts, th_o, pr_o), rtol=RTOL)
+        np.testing.assert_allclose(LT[b], c_oracle.loglik(tids, tcounts, th_o, pr_o), rtol=RTOL)
+        np.testing.assert_allclose(got[b], c_oracle.predict(pick, th[b], pr[b]), rtol=RTOL, atol=ATOL)
+    eng.close()
+
+
 @pytest.mark.parametrize("hub", [(0.02, 0.3), (0.01, 0.6)])
 def test_hub_fold0_against_c_oracle(tmp_path, hub):
     """A fold0-sized (P=1500, 90k triples) hub-heavy fold, shaped like get_input's trigenic screens
@@ -168,6 +242,12 @@ def test_work_plan_splits_match_oracle(tmp_path, monkeypatch, K, units):
     (20, 60, 4000, {"MMSBM_UNITS": "1,1"}),    # balanced without merging (K < 25)
     (30, 60, 4000, {"MMSBM_GM_Q4": "0"}),      # a small plan at K >= 25 on gm_kernel's two halves
     (26, 50, 3000, {"MMSBM_SP_ROWS": "128"}),  # 128-row parts forced on a small plan (no 64-row rule)
+    # K = 25 is BIG_K itself: the first K with merged rows, VREG, ZSPLIT, the 150 KB LDS target, GM::Q4
+    (25, 50, 3000, {}),
+    (25, 50, 3000, {"MMSBM_MERGE": "0"}),
+    (25, 50, 3000, {"MMSBM_UNITS": "1,1"}),
+    (25, 50, 3000, {"MMSBM_GM_Q4": "0"}),
+    (25, 50, 3000, {"MMSBM_SP_ROWS": "8"}),
 ])
 def test_large_k_plan_variants_match_oracle(tmp_path, monkeypatch, K, P, E, env):
     """The large-K work plans (csrc/plan.h pack_balanced, Plan::merge; mmsbm.hip's merged partial
@@ -558,7 +638,10 @@ def test_in_place_link_edit_between_iterations_matches_oracle():
                                    (1, {"MMSBM_SK_Y": "1"}), (2, {"MMSBM_SK_Y": "1"}),
                                    (4, {"MMSBM_SK_Y": "1", "MMSBM_UNITS": "3,3"}),
                                    (11, {"MMSBM_SK_Y": "1"}), (9, {"MMSBM_SK_Y": "1", "MMSBM_UNITS": "1,1"}),
-                                   (10, {"MMSBM_SK_RHO": "50"}), (6, {"MMSBM_SK_RHO": "100"})])
+                                   (10, {"MMSBM_SK_RHO": "50"}), (6, {"MMSBM_SK_RHO": "100"}),
+                                   # K = 8: the one small K with a single 64-cell chunk and no padding to 4
+                                   (8, {}), (8, {"MMSBM_SK_Y": "1"}), (8, {"MMSBM_SK_FUSED": "0"}),
+                                   (8, {"MMSBM_SK": "0"}), (8, {"MMSBM_UNITS": "1,1"})])
 def test_kernel_family_matches_oracle(tmp_path, monkeypatch, K, env):
     """K <= 12 runs the small-K kernels (csrc/sk.h; the three-stream fused E-step by default
     (SK_U), the stream-0 E-step with Y entries with MMSBM_SK_Y=1 (SK_Y), pass A + pass B with
@@ -597,7 +680,7 @@ def _gm_valid_cs(K):
     return [cs for cs in range(1, nq + 1) if nq % cs == 0 and (cs > 1 or nch <= 8) and (nq // cs) * qc <= 8]
 
 
-@pytest.mark.parametrize("K", [13, 16, 20, 22, 30])
+@pytest.mark.parametrize("K", [13, 16, 20, 22, 25, 30])
 def test_gm_workgroups_per_part_keep_bits(tmp_path, monkeypatch, K):
     """gm_kernel forms its X rows in NQ fixed groups of the cell chunks (up to four above K = 16,
     at K >= 25 on small plans (GM::Q4), two at K <= 16), so every valid count of workgroups per S part (MMSBM_GM_CS = 1, 2, 3,
