@@ -1,31 +1,10 @@
 """numpy float64 reference of the score census (include/mmsbm.h mmsbm_scan_census), for
-tests/test_census_host.py and tests/test_gpu_census.py: every C(P, 3) score, the counts at or above
-each threshold, and the precondition that keeps a threshold away from every score.  No GPU, no
-product code beyond the rank order."""
+tests/test_census_host.py and tests/test_gpu_census.py, over the scores of scan_ref.ref_scores: the
+counts at or above each threshold, and the precondition that keeps a threshold away from every
+score.  No GPU, no product code."""
 import numpy as np
 
-from partners_ref import RTOL, keys_to_ids, random_params, rank_tables  # noqa: F401  (re-exported)
-
 GAP = 1e-7   # a threshold must be further than this, relatively, from every reference score
-
-
-def ref_scores(theta, pr):
-    """All C(P, 3) scores in numpy float64 -> (scores, packed keys), in key order.  theta [P][K],
-    pr [K][K][K][R] in the reference nesting."""
-    P = theta.shape[0]
-    order, _ = rank_tables(P)
-    Th = np.asarray(theta, dtype=np.float64)[order]
-    T = np.einsum("ax,xyz->ayz", Th, np.asarray(pr, dtype=np.float64)[..., 1])
-    b, c = np.triu_indices(P, k=1)
-    scores, keys = [], []
-    for a in range(P - 2):
-        S = (Th @ T[a]) @ Th.T
-        keep = b > a
-        scores.append(S[b[keep], c[keep]])
-        keys.append((a * P + b[keep].astype(np.int64)) * P + c[keep])
-    if not scores:
-        return np.zeros(0), np.zeros(0, np.int64)
-    return np.concatenate(scores), np.concatenate(keys)
 
 
 def eligible(scores, keys, known=None):

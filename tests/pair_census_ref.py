@@ -1,12 +1,11 @@
 """numpy reference of the pair census (include/mmsbm.h mmsbm_pair_census), for
 tests/test_pair_census_host.py and tests/test_gpu_pair_census.py.  It builds on
-census_ref.ref_scores: every eligible score at or above a threshold is scattered to its three pairs
+scan_ref.ref_scores: every eligible score at or above a threshold is scattered to its three pairs
 with np.add.at.  Counts are integers: every comparison is equality.  No GPU, no product code beyond
 the rank order."""
 import numpy as np
 
-from census_ref import (RTOL, assert_clear, clear_of_scores, gap_thresholds, keys_to_ids,  # noqa: F401
-                        random_params, rank_tables, ref_census, ref_scores)               # (re-exported)
+from scan_ref import rank_tables
 
 
 def ref_pairs_rank(scores, keys, P, thresholds, known=None):

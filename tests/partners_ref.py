@@ -3,13 +3,7 @@ tests/test_gpu_partners.py: for one query it forms the three P x P products Th' 
 the region of every pair (b, c).  No GPU, no product code beyond the rank order."""
 import numpy as np
 
-RTOL = 1e-9
-
-
-def rank_tables(P):
-    from trigenicinteractionpredictor_amd.scan import rank_of, rank_order
-    order = rank_order(P)
-    return order, rank_of(order)
+from scan_ref import RTOL, keys_to_ids, min_gap, rank_tables, top
 
 
 def ref_query(theta, pr, q):
@@ -31,28 +25,6 @@ def ref_query(theta, pr, q):
     scores = np.where(b > q, S1[b, c], np.where(c > q, S2[b, c], S3[b, c]))
     tkeys = np.where(b > q, (q * P + b) * P + c, np.where(c > q, (b * P + q) * P + c, (b * P + c) * P + q))
     return scores, tkeys, b * P + c
-
-
-def top(scores, tkeys, n):
-    """The best n + 1 under (score descending, triple key ascending)."""
-    if scores.size > n + 1:     # everything not below the (n + 1)-th score, ties included
-        cut = np.partition(scores, scores.size - (n + 1))[scores.size - (n + 1)]
-        keep = scores >= cut
-        scores, tkeys = scores[keep], tkeys[keep]
-    idx = np.lexsort((tkeys, -scores))[:n + 1]
-    return scores[idx], tkeys[idx]
-
-
-def min_gap(top_scores):
-    if top_scores.size < 2:
-        return np.inf
-    return float(((top_scores[:-1] - top_scores[1:]) / np.abs(top_scores[:-1])).min())
-
-
-def keys_to_ids(tkeys, P):
-    order, _ = rank_tables(P)
-    k = np.asarray(tkeys, dtype=np.int64)
-    return np.stack([order[k // (P * P)], order[(k // P) % P], order[k % P]], axis=1).astype(np.int32)
 
 
 def want_list(theta, pr, gene, n, known_pairs=None, scores=None):
@@ -90,11 +62,3 @@ def check_query(got, theta, pr, gene, n, known_pairs=None, scores=None):
         assert not np.isin(others[:, 0] * P + others[:, 1], known_pairs).any()
     return gap
 
-
-def random_params(K, P, seed, B=1):
-    rng = np.random.default_rng(seed)
-    th = rng.random((B, P, K))
-    th /= th.sum(axis=2, keepdims=True)
-    pr = rng.random((B, K, K, K, 2))
-    pr /= pr.sum(axis=4, keepdims=True)
-    return th, pr

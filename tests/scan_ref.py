@@ -1,0 +1,90 @@
+"""What the numpy references of the scan families share (tests/census_ref.py, pair_census_ref.py,
+partners_ref.py and the GPU tests): the all-triples float64 scorer, the scan's total order, the
+precondition on adjacent gaps and a few helpers.  numpy only: no GPU, no product code beyond the
+rank order."""
+import numpy as np
+
+RTOL = 1e-9
+
+
+def rank_tables(P):
+    from trigenicinteractionpredictor_amd.scan import rank_of, rank_order
+    order = rank_order(P)
+    return order, rank_of(order)
+
+
+def keys_to_ids(keys, P):
+    order, _ = rank_tables(P)
+    k = np.asarray(keys, dtype=np.int64)
+    return np.stack([order[k // (P * P)], order[(k // P) % P], order[k % P]], axis=1).astype(np.int32)
+
+
+def packed(ids, P):
+    from trigenicinteractionpredictor_amd.scan import pack_keys
+    return pack_keys(ids, rank_tables(P)[1], P)
+
+
+def bits(a):
+    return np.ascontiguousarray(a).tobytes()
+
+
+def random_params(K, P, seed, B=1):
+    rng = np.random.default_rng(seed)
+    th = rng.random((B, P, K))
+    th /= th.sum(axis=2, keepdims=True)
+    pr = rng.random((B, K, K, K, 2))
+    pr /= pr.sum(axis=4, keepdims=True)
+    return th, pr
+
+
+def ref_scores(theta, pr):
+    """All C(P, 3) scores in numpy float64 -> (scores, packed keys), in key order.  theta [P][K],
+    pr [K][K][K][R] in the reference nesting."""
+    P = theta.shape[0]
+    order, _ = rank_tables(P)
+    Th = np.asarray(theta, dtype=np.float64)[order]
+    T = np.einsum("ax,xyz->ayz", Th, np.asarray(pr, dtype=np.float64)[..., 1])
+    b, c = np.triu_indices(P, k=1)
+    scores, keys = [], []
+    for a in range(P - 2):
+        S = (Th @ T[a]) @ Th.T
+        keep = b > a
+        scores.append(S[b[keep], c[keep]])
+        keys.append((a * P + b[keep].astype(np.int64)) * P + c[keep])
+    if not scores:
+        return np.zeros(0), np.zeros(0, np.int64)
+    return np.concatenate(scores), np.concatenate(keys)
+
+
+def prefix_mean(per, n):
+    """The ensemble reference: the first n slots' scores added in slot order, divided by n."""
+    total = per[0]
+    for b in range(1, n):
+        total = total + per[b]
+    return total / n if n > 1 else total.copy()
+
+
+def top(scores, keys, n, known=None):
+    """The best n + 1 under (score descending, key ascending) outside `known`."""
+    if known is not None and len(known):
+        keep = ~np.isin(keys, known)
+        scores, keys = scores[keep], keys[keep]
+    if scores.size > n + 1:     # everything not below the (n + 1)-th score, ties included
+        cut = np.partition(scores, scores.size - (n + 1))[scores.size - (n + 1)]
+        keep = scores >= cut
+        scores, keys = scores[keep], keys[keep]
+    idx = np.lexsort((keys, -scores))[:n + 1]
+    return scores[idx], keys[idx]
+
+
+def min_gap(top_scores):
+    """The smallest adjacent relative gap of a descending list (inf when it has no two entries)."""
+    if top_scores.size < 2:
+        return np.inf
+    return float(((top_scores[:-1] - top_scores[1:]) / np.abs(top_scores[:-1])).min())
+
+
+def assert_gaps(top_scores):
+    """The precondition, on the reference alone: the order inside the top N + 1 is determined."""
+    gap = min_gap(top_scores)
+    assert gap > 1e-9, gap

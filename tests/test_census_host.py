@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import census_ref as ref
+import scan_ref
 from golden_util import GOLDEN, load
 
 
@@ -18,19 +19,19 @@ def test_reference_counter_matches_the_c_oracle():
     from oracle import c_oracle
     _, vec, _, _ = load("small", "K10_s1")
     theta, pr = vec["theta_5"], vec["pr_5"]
-    scores, keys = ref.ref_scores(theta, pr)
+    scores, keys = scan_ref.ref_scores(theta, pr)
     P = theta.shape[0]
     assert scores.size == P * (P - 1) * (P - 2) // 6 and (np.diff(keys) > 0).all()
     pick = np.random.default_rng(0).choice(scores.size, 2000, replace=False)
-    np.testing.assert_allclose(scores[pick], c_oracle.predict(ref.keys_to_ids(keys[pick], P), theta, pr),
-                               rtol=ref.RTOL, atol=0)
+    np.testing.assert_allclose(scores[pick], c_oracle.predict(scan_ref.keys_to_ids(keys[pick], P), theta, pr),
+                               rtol=scan_ref.RTOL, atol=0)
 
     _, vec, _, _ = load("tiny", "K3_s1")
     theta, pr = vec["theta_5"], vec["pr_5"]
-    scores, keys = ref.ref_scores(theta, pr)
+    scores, keys = scan_ref.ref_scores(theta, pr)
     P = theta.shape[0]
-    full = c_oracle.predict(ref.keys_to_ids(keys, P), theta, pr)
-    np.testing.assert_allclose(scores, full, rtol=ref.RTOL, atol=0)
+    full = c_oracle.predict(scan_ref.keys_to_ids(keys, P), theta, pr)
+    np.testing.assert_allclose(scores, full, rtol=scan_ref.RTOL, atol=0)
     thresholds = ref.gap_thresholds(scores, 40)
     ref.assert_clear(scores, thresholds)
     known = keys[::3]

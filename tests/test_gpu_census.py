@@ -18,45 +18,11 @@ import numpy as np
 import pytest
 
 import census_ref as ref
-from golden_util import GOLDEN, load
+import scan_ref
+from golden_util import GOLDEN
+from scan_gpu import Raw, engine, fixture_case, random_case
 
 pytestmark = pytest.mark.gpu
-
-
-def engine(thetas, prs):
-    from trigenicinteractionpredictor_amd.engine import EMEngine
-    thetas, prs = np.asarray(thetas), np.asarray(prs)
-    B, P, K = thetas.shape
-    eng = EMEngine(K, P, B=B)
-    eng.upload(thetas, prs)
-    return eng
-
-
-@functools.lru_cache(maxsize=None)
-def random_case(K, P, seed):
-    """(theta [P][K], pr, reference scores, reference keys) of one random sample; computed once."""
-    th, pr = ref.random_params(K, P, seed)
-    scores, keys = ref.ref_scores(th[0], pr[0])
-    for a in (scores, keys):
-        a.setflags(write=False)
-    return th[0], pr[0], scores, keys
-
-
-@functools.lru_cache(maxsize=None)
-def fixture_case(fold, name, it):
-    """(theta, pr, P, {exclude: known keys}, reference scores, reference keys) of a committed fixture."""
-    from trigenicinteractionpredictor_amd import Model
-    from trigenicinteractionpredictor_amd.scan import known_keys
-    _, vec, train, test = load(fold, name)
-    theta, pr = vec["theta_%d" % it], vec["pr_%d" % it]
-    m = Model()
-    m.get_traintest(train, test)
-    assert m.P == theta.shape[0]
-    scores, keys = ref.ref_scores(theta, pr)
-    for a in (scores, keys):
-        a.setflags(write=False)
-    known = {ex: known_keys(m, ex) for ex in ((), ("train",), ("train", "test"))}
-    return theta, pr, m.P, known, scores, keys
 
 
 def check(eng, scores, keys, thresholds, known=None, sample=0):
@@ -77,7 +43,7 @@ FIXTURES = [("tiny", "K10_s1", 25), ("small", "K10_s1", 5), ("multi", "K3_s4", 2
 @pytest.mark.parametrize("exclude", [(), ("train",), ("train", "test")], ids=["all", "train", "novel"])
 @pytest.mark.parametrize("fold,name,it", FIXTURES, ids=["%s-%s" % c[:2] for c in FIXTURES])
 def test_exact_counts_on_reference_parameters(fold, name, it, exclude):
-    theta, pr, P, known, scores, keys = fixture_case(fold, name, it)
+    theta, pr, P, _, known, scores, keys = fixture_case(fold, name, it)
     thresholds = ref.gap_thresholds(scores, 60)      # midpoints of gaps, adjacent gaps, below the
     assert thresholds.size >= 8                      # minimum, above the maximum, one duplicate
     assert np.unique(thresholds).size == thresholds.size - 1
@@ -134,7 +100,7 @@ def test_group_counts(K):
 def test_census_at_the_scores_of_a_scan_list_numbers_the_list(mode):
     """Exact, no precondition: the census scores carry the scan's bits."""
     K, P, N = 10, 70, 50
-    th, pr = ref.random_params(K, P, 31, B=3)
+    th, pr = scan_ref.random_params(K, P, 31, B=3)
     eng = engine(th, pr)
     sample = 1 if mode == "sample" else None
     if mode == "ensemble":
@@ -154,8 +120,8 @@ def test_census_at_the_scores_of_a_scan_list_numbers_the_list(mode):
 # ------------------------------------------------------------------ 4. batch and grid
 def test_batch_grid_and_repeats(monkeypatch):
     K, P = 10, 70
-    th, pr = ref.random_params(K, P, 41, B=3)
-    scores, keys = ref.ref_scores(th[2], pr[2])
+    th, pr = scan_ref.random_params(K, P, 41, B=3)
+    scores, keys = scan_ref.ref_scores(th[2], pr[2])
     thresholds = ref.gap_thresholds(scores, 100)
     known = keys[1::5].copy()
     eng = engine(th, pr)
@@ -179,7 +145,7 @@ def test_batch_grid_and_repeats(monkeypatch):
     assert eng.theta.cpu().numpy().tobytes() == th0.tobytes()
     assert eng.pr.cpu().numpy().tobytes() == p0.tobytes()
     # the ensemble mean, added in slot order
-    per = [ref.ref_scores(th[b], pr[b])[0] for b in range(3)]
+    per = [scan_ref.ref_scores(th[b], pr[b])[0] for b in range(3)]
     mean3 = ((per[0] + per[1]) + per[2]) / 3
     check(eng, mean3, keys, ref.gap_thresholds(mean3, 100), known, sample=None)
     eng.close()
@@ -244,7 +210,7 @@ def test_ties_duplicated_theta_rows():
     """Two groups of genes with identical rows: at most 8 distinct score values, each class counted
     whole at its own value."""
     K, P = 5, 20
-    th, pr = ref.random_params(K, 2, 7)
+    th, pr = scan_ref.random_params(K, 2, 7)
     th = th[:, np.random.default_rng(3).integers(0, 2, P)]     # every gene one of two rows
     eng = engine(th, pr)
     n = comb(P, 3)
@@ -299,12 +265,9 @@ def test_threshold_caps():
     import torch
     nbytes = ctypes.c_int64()
     assert eng.lib.mmsbm_census_workspace_bytes(eng.ctx, max_m + 1, ctypes.byref(nbytes)) == _lib.MMSBM_ERR_UNSUPPORTED
-    thr = torch.from_numpy(np.sort(both)).to(eng.device)
-    out = torch.zeros(max_m + 2, dtype=torch.int64, device=eng.device)
-    rc = eng.lib.mmsbm_scan_census(eng.ctx, eng._scan_order.data_ptr(), None, 0, eng.theta.data_ptr(),
-                                   eng.pr.data_ptr(), 0, thr.data_ptr(), max_m + 1, eng._census_ws.data_ptr(),
-                                   eng._census_ws.numel(), out.data_ptr(), eng._stream())
-    assert rc == _lib.MMSBM_ERR_UNSUPPORTED
+    raw = Raw(eng, "census", max_m)
+    thr = raw.upload(np.sort(both))
+    assert raw.call((thr.data_ptr(), max_m + 1), [raw.full((max_m + 2,), torch.int64, 0)]) == _lib.MMSBM_ERR_UNSUPPORTED
     with pytest.raises(ValueError):
         eng.census([0.5, float("nan")])
     with pytest.raises(ValueError):
@@ -325,7 +288,7 @@ def fitted_model():
     for _ in range(5):
         m.make_iteration()
     theta, pr = np.array(m.theta), np.array(m.pr)
-    scores, keys = ref.ref_scores(theta, pr)
+    scores, keys = scan_ref.ref_scores(theta, pr)
     return m, theta, pr, scores, keys, known_keys(m, ("train",)), known_keys(m)
 
 
@@ -365,7 +328,7 @@ def test_model_novel_census_and_rank():
     measured = np.intersect1d(np.flatnonzero(np.isin(keys, known_all)), order[clear])
     assert measured.size >= 4
     pick = np.concatenate([pick, measured[:4]])
-    ids = ref.keys_to_ids(keys[pick], P)
+    ids = scan_ref.keys_to_ids(keys[pick], P)
     rng = np.random.default_rng(2)
     triples = []
     for n, row in enumerate(ids):
@@ -376,7 +339,7 @@ def test_model_novel_census_and_rank():
     for (rank, p, key), i, row in zip(rows, pick, ids):
         assert key == "_".join(str(int(g)) for g in row)                  # as `links` spells it
         assert p == m.do_prediction(*key.split("_"))
-        np.testing.assert_allclose(p, scores[i], rtol=ref.RTOL)
+        np.testing.assert_allclose(p, scores[i], rtol=scan_ref.RTOL)
         lo, hi = rank_bounds(scores, keys, known_all, scores[i], keys[i])
         assert lo == hi == rank, (key, rank, lo, hi)
     assert pack_keys(ids, rank_of(rank_order(P)), P).tolist() == keys[pick].tolist()
@@ -395,7 +358,7 @@ def test_model_heldout_ranks():
         assert real == (0 if m.test_links[key][0] else 1)
         ids = np.array([[int(g) for g in key.split("_")]])
         s = float(listed_score(theta, pr, ids)[0])
-        np.testing.assert_allclose(p, s, rtol=ref.RTOL)
+        np.testing.assert_allclose(p, s, rtol=scan_ref.RTOL)
         distinct = len(set(ids[0].tolist())) == 3
         lo, hi = rank_bounds(scores, keys, known_train, s, int(pack_keys(ids, rank, m.P)[0]) if distinct else -1)
         assert lo <= r <= hi, (key, r, lo, hi)

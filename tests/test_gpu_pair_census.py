@@ -17,52 +17,19 @@ from math import comb
 import numpy as np
 import pytest
 
+import census_ref
 import pair_census_ref as ref
-from golden_util import GOLDEN, load
+import scan_ref
+from golden_util import GOLDEN
+from scan_gpu import Raw, engine, fixture_case, random_case
 
 pytestmark = pytest.mark.gpu
-
-
-def engine(thetas, prs):
-    from trigenicinteractionpredictor_amd.engine import EMEngine
-    thetas, prs = np.asarray(thetas), np.asarray(prs)
-    B, P, K = thetas.shape
-    eng = EMEngine(K, P, B=B)
-    eng.upload(thetas, prs)
-    return eng
-
-
-@functools.lru_cache(maxsize=None)
-def random_case(K, P, seed):
-    """(theta [P][K], pr, reference scores, reference keys) of one random sample; computed once."""
-    th, pr = ref.random_params(K, P, seed)
-    scores, keys = ref.ref_scores(th[0], pr[0])
-    for a in (scores, keys):
-        a.setflags(write=False)
-    return th[0], pr[0], scores, keys
-
-
-@functools.lru_cache(maxsize=None)
-def fixture_case(fold, name, it):
-    """(theta, pr, P, {exclude: known keys}, reference scores, reference keys) of a committed fixture."""
-    from trigenicinteractionpredictor_amd import Model
-    from trigenicinteractionpredictor_amd.scan import known_keys
-    _, vec, train, test = load(fold, name)
-    theta, pr = vec["theta_%d" % it], vec["pr_%d" % it]
-    m = Model()
-    m.get_traintest(train, test)
-    assert m.P == theta.shape[0]
-    scores, keys = ref.ref_scores(theta, pr)
-    for a in (scores, keys):
-        a.setflags(write=False)
-    known = {ex: known_keys(m, ex) for ex in ((), ("train",), ("train", "test"))}
-    return theta, pr, m.P, known, scores, keys
 
 
 def check(eng, scores, keys, thresholds, known=None, sample=0):
     """The precondition on the reference alone, then the whole matrix equal to the reference,
     symmetric and with a zero diagonal."""
-    ref.assert_clear(scores, thresholds)
+    census_ref.assert_clear(scores, thresholds)
     P = eng.P
     _, want = ref.ref_pairs(scores, keys, P, thresholds, known)
     got = eng.pair_census(thresholds, known, sample=sample)
@@ -80,8 +47,8 @@ FIXTURES = [("tiny", "K10_s1", 25), ("multi", "K3_s4", 25)]
 @pytest.mark.parametrize("exclude", [(), ("train",), ("train", "test")], ids=["all", "train", "novel"])
 @pytest.mark.parametrize("fold,name,it", FIXTURES, ids=["%s-%s" % c[:2] for c in FIXTURES])
 def test_exact_matrix_on_reference_parameters(fold, name, it, exclude):
-    theta, pr, P, known, scores, keys = fixture_case(fold, name, it)
-    thresholds = ref.gap_thresholds(scores, 9)       # 9 gaps (+ 2 adjacent ones when they are new),
+    theta, pr, P, _, known, scores, keys = fixture_case(fold, name, it)
+    thresholds = census_ref.gap_thresholds(scores, 9)       # 9 gaps (+ 2 adjacent ones when they are new),
     assert 12 <= thresholds.size <= 14               # below the minimum, above the maximum, a duplicate
     thresholds = thresholds[:12]                     # 12 thresholds: two calls of the kernel
     eng = engine(theta[None], pr[None])
@@ -104,7 +71,7 @@ def test_gene_counts(P):
         got = eng.pair_census([1e-300, 0.5, 0.1], np.array([7], dtype=np.int64))
         assert got.shape == (P, P, 3) and not got.any()
     else:
-        thresholds = ref.gap_thresholds(scores, 6)
+        thresholds = census_ref.gap_thresholds(scores, 6)
         check(eng, scores, keys, thresholds)
         check(eng, scores, keys, thresholds, keys[::3].copy())
     eng.close()
@@ -120,7 +87,7 @@ def test_group_counts(K):
         s = float(pr[0, 0, 0, 1])
         thresholds = np.array([s * (1 - 1e-6), s * (1 + 1e-6)])
     else:
-        thresholds = ref.gap_thresholds(scores, 6)
+        thresholds = census_ref.gap_thresholds(scores, 6)
     got = check(eng, scores, keys, thresholds)
     if K == 1:
         np.testing.assert_array_equal(got[:, :, 0], (P - 2) * (1 - np.eye(P, dtype=np.int32)))
@@ -133,7 +100,7 @@ def test_group_counts(K):
 def test_pair_sums_are_three_times_the_census(mode):
     """Exact, no precondition: the pair census scores carry the census's (the scan's) bits."""
     K, P, N = 10, 70, 50
-    th, pr = ref.random_params(K, P, 31, B=3)
+    th, pr = scan_ref.random_params(K, P, 31, B=3)
     eng = engine(th, pr)
     sample = 1 if mode == "sample" else None
     if mode == "ensemble":
@@ -158,9 +125,9 @@ def test_pair_sums_are_three_times_the_census(mode):
 # ------------------------------------------------------------------ 4. batch, grid, repeats
 def test_batch_grid_and_repeats(monkeypatch):
     K, P = 10, 70
-    th, pr = ref.random_params(K, P, 41, B=3)
-    scores, keys = ref.ref_scores(th[2], pr[2])
-    thresholds = ref.gap_thresholds(scores, 6)
+    th, pr = scan_ref.random_params(K, P, 41, B=3)
+    scores, keys = scan_ref.ref_scores(th[2], pr[2])
+    thresholds = census_ref.gap_thresholds(scores, 6)
     known = keys[1::5].copy()
     eng = engine(th, pr)
     th0, p0 = eng.theta.cpu().numpy().copy(), eng.pr.cpu().numpy().copy()
@@ -178,9 +145,9 @@ def test_batch_grid_and_repeats(monkeypatch):
     assert eng.theta.cpu().numpy().tobytes() == th0.tobytes()
     assert eng.pr.cpu().numpy().tobytes() == p0.tobytes()
     # the ensemble mean, added in slot order
-    per = [ref.ref_scores(th[b], pr[b])[0] for b in range(3)]
+    per = [scan_ref.ref_scores(th[b], pr[b])[0] for b in range(3)]
     mean3 = ((per[0] + per[1]) + per[2]) / 3
-    check(eng, mean3, keys, ref.gap_thresholds(mean3, 6), known, sample=None)
+    check(eng, mean3, keys, census_ref.gap_thresholds(mean3, 6), known, sample=None)
     eng.close()
 
 
@@ -190,17 +157,13 @@ def test_the_call_zeroes_a_dirty_output():
     K, P = 3, 33
     theta, pr, scores, keys = random_case(K, P, 11 + P)
     eng = engine(theta[None], pr[None])
-    thresholds = np.sort(ref.gap_thresholds(scores, 4))[:6]
-    ref.assert_clear(scores, thresholds)
+    thresholds = np.sort(census_ref.gap_thresholds(scores, 4))[:6]
+    census_ref.assert_clear(scores, thresholds)
     want, _ = ref.ref_pairs(scores, keys, P, thresholds)
-    eng.pair_census(thresholds)                        # sizes the workspace, builds the rank order
-    thr = torch.from_numpy(thresholds).to(eng.device)
-    out = torch.ones((P, P, thresholds.size), dtype=torch.int32, device=eng.device)
-    rc = eng.lib.mmsbm_pair_census(eng.ctx, eng._scan_order.data_ptr(), None, 0, eng.theta.data_ptr(),
-                                   eng.pr.data_ptr(), 0, thr.data_ptr(), thresholds.size,
-                                   eng._pair_census_ws.data_ptr(), eng._pair_census_ws.numel(), out.data_ptr(),
-                                   eng._stream())
-    assert rc == 0
+    raw = Raw(eng, "pair_census", thresholds.size)
+    thr = raw.upload(thresholds)
+    out = raw.full((P, P, thresholds.size), torch.int32, 1)
+    assert raw.call((thr.data_ptr(), thresholds.size), [out]) == 0
     np.testing.assert_array_equal(out.cpu().numpy(), want)         # rank positions, x < y only
     eng.close()
 
@@ -210,7 +173,7 @@ def test_exclusion_one_gene_one_pair_everything():
     from trigenicinteractionpredictor_amd.scan import rank_order
     K, P = 3, 70
     theta, pr, scores, keys = random_case(K, P, 51)
-    thresholds = ref.gap_thresholds(scores, 5)
+    thresholds = census_ref.gap_thresholds(scores, 5)
     eng = engine(theta[None], pr[None])
     order = rank_order(P)
     a, b, c = keys // (P * P), (keys // P) % P, keys % P
@@ -237,14 +200,14 @@ def test_exclusion_one_gene_one_pair_everything():
 def test_dense_and_empty(K, P, B):
     """Below every score: every eligible triple through all three pair roles, = pair_eligible."""
     from trigenicinteractionpredictor_amd.scan import pair_eligible
-    th, pr = ref.random_params(K, P, 61, B=B)
-    per = [ref.ref_scores(th[b], pr[b]) for b in range(B)]
+    th, pr = scan_ref.random_params(K, P, 61, B=B)
+    per = [scan_ref.ref_scores(th[b], pr[b]) for b in range(B)]
     keys = per[0][1]
     scores = per[0][0] if B == 1 else (per[0][0] + per[1][0]) / 2
     eng = engine(th, pr)
     sample = 0 if B == 1 else None
     lo, hi = scores.min() * (1 - 1e-3), scores.max() * (1 + 1e-3)
-    ref.assert_clear(scores, [lo, hi])
+    census_ref.assert_clear(scores, [lo, hi])
     for kn in (None, keys[::3].copy()):
         got = eng.pair_census([lo], kn, sample=sample)
         np.testing.assert_array_equal(got[:, :, 0], pair_eligible(P, kn))
@@ -264,8 +227,8 @@ def test_pairs_top_is_the_lexsort_of_the_reference():
     theta, pr, scores, keys = random_case(K, P, 71)
     known = keys[::3].copy()
     eng = engine(theta[None], pr[None])
-    t = float(np.sort(ref.gap_thresholds(scores, 5))[3])      # a gap in the middle of the range
-    ref.assert_clear(scores, [t])
+    t = float(np.sort(census_ref.gap_thresholds(scores, 5))[3])      # a gap in the middle of the range
+    census_ref.assert_clear(scores, [t])
     for kn in (None, known):
         rank_mat, _ = ref.ref_pairs(scores, keys, P, [t], kn)
         el = pair_eligible(P, kn)
@@ -312,19 +275,14 @@ def test_caps_and_errors():
     assert eng.lib.mmsbm_pair_census_workspace_bytes(eng.ctx, max_m, ctypes.byref(nbytes)) == 0
     assert eng.lib.mmsbm_pair_census_workspace_bytes(eng.ctx, max_m + 1, ctypes.byref(nbytes)) == _lib.MMSBM_ERR_UNSUPPORTED
     assert eng.lib.mmsbm_pair_census_workspace_bytes(eng.ctx, max_m, None) == _lib.MMSBM_ERR_INVALID
-    eng.pair_census([0.5])                             # sizes the workspace, builds the rank order
-    thr = torch.from_numpy(np.linspace(0.1, 0.9, max_m + 1)).to(eng.device)
-    out = torch.zeros((40, 40, max_m + 1), dtype=torch.int32, device=eng.device)
-    args = [eng.ctx, eng._scan_order.data_ptr(), None, 0, eng.theta.data_ptr(), eng.pr.data_ptr(), 0,
-            thr.data_ptr(), max_m + 1, eng._pair_census_ws.data_ptr(), eng._pair_census_ws.numel(),
-            out.data_ptr(), eng._stream()]
-    assert eng.lib.mmsbm_pair_census(*args) == _lib.MMSBM_ERR_UNSUPPORTED
+    raw = Raw(eng, "pair_census", max_m)
+    thr = raw.upload(np.linspace(0.1, 0.9, max_m + 1))
+    out = raw.full((40, 40, max_m + 1), torch.int32, 0)
+    assert raw.call((thr.data_ptr(), max_m + 1), [out]) == _lib.MMSBM_ERR_UNSUPPORTED
     assert b"cap" in eng.lib.mmsbm_last_error()
-    args[8] = max_m
+    # by position in the C call: 1 order, 4 theta, 6 sample, 7 thresholds, 9 and 10 workspace, 11 out
     for i, bad in ((1, None), (4, None), (7, None), (11, None), (6, 1), (6, -2), (10, 16), (9, None)):
-        wrong = list(args)
-        wrong[i] = bad
-        assert eng.lib.mmsbm_pair_census(*wrong) == _lib.MMSBM_ERR_INVALID, i
+        assert raw.call((thr.data_ptr(), max_m), [out], replace=[(i, bad)]) == _lib.MMSBM_ERR_INVALID, i
     with pytest.raises(ValueError):
         eng.pair_census([0.5, float("nan")])
     with pytest.raises(ValueError):
@@ -351,7 +309,7 @@ def fitted_model():
     for _ in range(5):
         m.make_iteration()
     theta, pr = np.array(m.theta), np.array(m.pr)
-    scores, keys = ref.ref_scores(theta, pr)
+    scores, keys = scan_ref.ref_scores(theta, pr)
     return m, scores, keys, known_keys(m, ("train",)), known_keys(m)
 
 
@@ -359,8 +317,8 @@ def test_model_query_pairs_and_gene_counts():
     from trigenicinteractionpredictor_amd.scan import pair_eligible
     m, scores, keys, known_train, known_all = fitted_model()
     P = m.P
-    thresholds = ref.gap_thresholds(scores, 5)
-    ref.assert_clear(scores, thresholds)
+    thresholds = census_ref.gap_thresholds(scores, 5)
+    census_ref.assert_clear(scores, thresholds)
     t = float(np.sort(thresholds)[3])
     for exclude, known in ((("train", "test"), known_all), (("train",), known_train)):
         rank_mat, gene_mat = ref.ref_pairs(scores, keys, P, thresholds, known)

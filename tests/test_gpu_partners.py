@@ -17,41 +17,19 @@ import numpy as np
 import pytest
 
 import partners_ref as ref
+import scan_ref
 from golden_util import GOLDEN, load
+from scan_gpu import engine, fixture_case
+from scan_ref import bits
 
 pytestmark = pytest.mark.gpu
 
-RTOL = ref.RTOL
-
-
-def engine(thetas, prs):
-    from trigenicinteractionpredictor_amd.engine import EMEngine
-    thetas, prs = np.asarray(thetas), np.asarray(prs)
-    B, P, K = thetas.shape
-    eng = EMEngine(K, P, B=B)
-    eng.upload(thetas, prs)
-    return eng
-
-
-@functools.lru_cache(maxsize=None)
-def fixture_case(fold, name, it):
-    """(theta, pr, P, model) of one committed fixture."""
-    from trigenicinteractionpredictor_amd import Model
-    _, vec, train, test = load(fold, name)
-    theta, pr = vec["theta_%d" % it], vec["pr_%d" % it]
-    m = Model()
-    m.get_traintest(train, test)
-    assert m.P == theta.shape[0]
-    return theta, pr, m.P, m
+RTOL = scan_ref.RTOL
 
 
 def slices(known):
     off, pairs = known
     return [pairs[off[i]:off[i + 1]] for i in range(off.size - 1)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 def same_rows(x, y):
@@ -65,7 +43,7 @@ def candidates(P):
 # ------------------------------------------------------------------ the reference vs the oracle
 def test_reference_scorer_matches_the_c_oracle():
     from oracle import c_oracle
-    theta, pr, P, _ = fixture_case("small", "K10_s1", 5)
+    theta, pr, P, _ = fixture_case("small", "K10_s1", 5)[:4]
     rng = np.random.default_rng(0)
     scores, ids = [], []
     for q in (0, 1, 137, 150, 298, 299):                     # every region, the edges of the order
@@ -73,7 +51,7 @@ def test_reference_scorer_matches_the_c_oracle():
         assert s.size == candidates(P) == 44551
         pick = rng.choice(s.size, 334, replace=False)
         scores.append(s[pick])
-        ids.append(ref.keys_to_ids(tk[pick], P))
+        ids.append(scan_ref.keys_to_ids(tk[pick], P))
     scores, ids = np.concatenate(scores), np.concatenate(ids)
     assert scores.size >= 2000
     np.testing.assert_allclose(scores, c_oracle.predict(ids, theta, pr), rtol=RTOL, atol=0)
@@ -91,7 +69,7 @@ CASES = [("tiny", "K10_s1", 25, 64, 4.9e-6), ("tiny", "K10_s1", 25, 741, 7.1e-7)
                          ids=["%s-%s-it%d-N%d" % c[:4] for c in CASES])
 def test_exact_lists_for_every_query(fold, name, it, n, gap, exclude):
     from trigenicinteractionpredictor_amd.scan import partner_known
-    theta, pr, P, m = fixture_case(fold, name, it)
+    theta, pr, P, m = fixture_case(fold, name, it)[:4]
     queries = list(range(P))
     known = partner_known(m, queries) if exclude else None
     eng = engine(theta[None], pr[None])
@@ -113,10 +91,10 @@ def test_regions_and_small_gene_counts(P):
     count: the whole region structure comes back, then part and all of it excluded."""
     import torch
     N = 512
-    th, pr = ref.random_params(3, P, 40 + P)
+    th, pr = scan_ref.random_params(3, P, 40 + P)
     eng = engine(th, pr)
     queries = list(range(P))
-    order, rank = ref.rank_tables(P)
+    order, rank = scan_ref.rank_tables(P)
     assert {int(rank[g]) for g in queries} >= {0, P // 2, P - 1}
     sd, idd, cd = eng.partners_top_async(queries, N)
     torch.cuda.synchronize()
@@ -155,7 +133,7 @@ def test_regions_and_small_gene_counts(P):
 # ------------------------------------------------------------------ 3. schedule independence
 def test_rows_do_not_depend_on_the_other_queries():
     from trigenicinteractionpredictor_amd.scan import partner_known
-    theta, pr, P, m = fixture_case("tiny", "K10_s1", 25)
+    theta, pr, P, m = fixture_case("tiny", "K10_s1", 25)[:4]
     N = 64
     eng = engine(theta[None], pr[None])
     th0, p0 = bits(eng.theta.cpu().numpy()), bits(eng.pr.cpu().numpy())
@@ -178,9 +156,9 @@ def test_rows_do_not_depend_on_the_other_queries():
 def test_one_query_spread_over_the_device_equals_its_row_in_a_full_call():
     """P = 300: a Q = 1 call gives the query hundreds of workgroups and two merge levels, the
     Q = P call a handful and one."""
-    theta, pr, P, _ = fixture_case("small", "K10_s1", 25)
+    theta, pr, P, _ = fixture_case("small", "K10_s1", 25)[:4]
     N = 64
-    order, _ = ref.rank_tables(P)
+    order, _ = scan_ref.rank_tables(P)
     eng = engine(theta[None], pr[None])
     every = eng.partners_top(list(range(P)), N, sample=0)
     for q in (0, 150, P - 1):                               # first, middle and last rank position
@@ -199,7 +177,7 @@ def test_ensemble_and_slots():
     prs = np.stack([vec["pr_%d" % it] for it in (1, 5, 25)])
     P, N = thetas.shape[1], 64
     queries = list(range(P))
-    _, rank = ref.rank_tables(P)
+    _, rank = scan_ref.rank_tables(P)
     per = [[ref.ref_query(thetas[b], prs[b], int(rank[g]))[0] for g in queries] for b in range(3)]
     eng = engine(thetas, prs)
     # the mean over the active prefix, added in slot order
@@ -231,13 +209,13 @@ def key_order_ids(P, q, n, skip=0):
     """The first candidates of rank position q by packed triple key alone."""
     keys = sorted((lambda t: (t[0] * P + t[1]) * P + t[2])(sorted((q, b, c)))
                   for b, c in itertools.combinations([x for x in range(P) if x != q], 2))
-    return ref.keys_to_ids(np.array(keys[skip:skip + n], dtype=np.int64), P)
+    return scan_ref.keys_to_ids(np.array(keys[skip:skip + n], dtype=np.int64), P)
 
 
 def test_ties_resolve_by_packed_triple_key():
     K, P, N = 5, 37, 50
-    order, rank = ref.rank_tables(P)
-    th, pr = ref.random_params(K, 1, 7)
+    order, rank = scan_ref.rank_tables(P)
+    th, pr = scan_ref.random_params(K, 1, 7)
     th = np.repeat(th, P, axis=1)                       # every gene the same row
     eng = engine(th, pr)
     for q in (0, P - 1):          # one region each (q < b < c, b < c < q): one contraction, one score
@@ -277,8 +255,8 @@ def test_ties_resolve_by_packed_triple_key():
 def test_larger_k(K, B):
     """K padding, the large-K LDS sizing and the narrower row blocks of the ensemble."""
     P, N = 48, 64
-    th, pr = ref.random_params(K, P, 100 + K + B, B)
-    _, rank = ref.rank_tables(P)
+    th, pr = scan_ref.random_params(K, P, 100 + K + B, B)
+    _, rank = scan_ref.rank_tables(P)
     queries = list(range(P))
     eng = engine(th, pr)
     rows = eng.partners_top(queries, N)
@@ -293,8 +271,8 @@ def test_larger_k(K, B):
 @pytest.mark.parametrize("K", [1, 2])
 def test_smallest_k(K):
     P, N = 20, 64
-    th, pr = ref.random_params(K, P, 60 + K)
-    order, rank = ref.rank_tables(P)
+    th, pr = scan_ref.random_params(K, P, 60 + K)
+    order, rank = scan_ref.rank_tables(P)
     queries = list(range(P))
     eng = engine(th, pr)
     rows = eng.partners_top(queries, N)
@@ -309,7 +287,7 @@ def test_smallest_k(K):
 
 # ------------------------------------------------------------------ 7. the genome-wide scan
 def test_the_best_triple_heads_its_three_genes_lists():
-    theta, pr, P, _ = fixture_case("small", "K10_s1", 25)
+    theta, pr, P, _ = fixture_case("small", "K10_s1", 25)[:4]
     eng = engine(theta[None], pr[None])
     s, ids = eng.scan_top(1, None, sample=0)
     rows = eng.partners_top([int(g) for g in ids[0]], 4, sample=0)
@@ -322,7 +300,7 @@ def test_the_best_triple_heads_its_three_genes_lists():
 # ------------------------------------------------------------------ 8. errors
 def test_errors():
     from trigenicinteractionpredictor_amd import _lib
-    th, pr = ref.random_params(3, 20, 5)
+    th, pr = scan_ref.random_params(3, 20, 5)
     eng = engine(th, pr)
     cap = eng.lib.mmsbm_partners_max_n()
     assert cap >= 1024

@@ -378,13 +378,13 @@ def scan_case(R, K, B):
     """B samples of random parameters at P = 40 and the reference scores of the rating-1 slice,
     of the mean over the samples, and of the same parameters with rating 0 / rating 2 in rating
     1's place (what a kernel reading the wrong slice would rank)."""
-    from test_gpu_scan import ref_scan
+    import scan_ref
     P = 40
     th = np.stack([start(P, K, R, 50 * K + R + b)[0] for b in range(B)])
     pr = np.stack([start(P, K, R, 50 * K + R + b)[1] for b in range(B)])
 
     def mean_scores(prs):
-        per = [ref_scan(th[b], prs[b]) for b in range(B)]
+        per = [scan_ref.ref_scores(th[b], prs[b]) for b in range(B)]
         total = per[0][0]
         for b in range(1, B):
             total = total + per[b][0]
@@ -401,24 +401,24 @@ SCAN_PARAMS = [(R, K, B) for R in (3, 8) for K in (4, 13) for B in (1, 2)]
 def test_scan_partners_and_census_read_the_rating_1_slice(R, K, B):
     import census_ref
     import partners_ref
-    from test_gpu_scan import check, ref_top
+    import scan_ref
+    from test_gpu_scan import check
     from trigenicinteractionpredictor_amd import EMEngine
     N = 50
     P, th, pr, scores, keys, wrong = scan_case(R, K, B)
-    want_keys = ref_top(scores, keys, N)[1][:N]
+    want_keys = scan_ref.top(scores, keys, N)[1][:N]
     for other in wrong:     # on the reference alone: another rating's slice ranks another list
-        assert not np.array_equal(ref_top(other, keys, N)[1][:N], want_keys)
+        assert not np.array_equal(scan_ref.top(other, keys, N)[1][:N], want_keys)
     eng = EMEngine(K, P, B=B, R=R)
     eng.upload(th, pr)
     # the genome-wide scan
     s, ids = eng.scan_top(N)
     check(s, ids, scores, keys, N, P)
     if B > 1:
-        from test_gpu_scan import ref_scan
         s1, ids1 = eng.scan_top(N, sample=1)
-        check(s1, ids1, ref_scan(th[1], pr[1])[0], keys, N, P)
+        check(s1, ids1, scan_ref.ref_scores(th[1], pr[1])[0], keys, N, P)
     # the partner scan of five genes
-    _, rank = partners_ref.rank_tables(P)
+    _, rank = scan_ref.rank_tables(P)
     queries = [0, 7, 19, 20, P - 1]
     rows = eng.partners_top(queries, N)
     for g, row in zip(queries, rows):

@@ -6,123 +6,40 @@ tests demand the identical ordered id list.  Each first asserts, on the referenc
 adjacent relative gap inside the reference's top N + 1 exceeds 1e-9 (the project's RTOL; the
 kernel's re-association error is about K^3 2^-53 <= 4e-12), so the order is determined.
 """
-import functools
 import itertools
 import os
 
 import numpy as np
 import pytest
 
+import scan_ref
 from golden_util import GOLDEN, load
+from scan_gpu import engine, fixture_case
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-9
-
-
-# ------------------------------------------------------------------------------ the reference
-def ref_scan(theta, pr):
-    """All C(P, 3) scores in numpy float64 -> (scores, packed keys), unsorted.  theta [P][K],
-    pr [K][K][K][R] in the reference nesting."""
-    from trigenicinteractionpredictor_amd.scan import rank_order
-    P = theta.shape[0]
-    Th = np.asarray(theta, dtype=np.float64)[rank_order(P)]
-    T = np.einsum("ax,xyz->ayz", Th, np.asarray(pr, dtype=np.float64)[..., 1])
-    scores, keys = [], []
-    for a in range(P - 2):
-        S = (Th @ T[a]) @ Th.T
-        b, c = np.triu_indices(P, k=1)
-        keep = b > a
-        b, c = b[keep], c[keep]
-        scores.append(S[b, c])
-        keys.append((a * P + b.astype(np.int64)) * P + c)
-    if not scores:
-        return np.zeros(0), np.zeros(0, np.int64)
-    return np.concatenate(scores), np.concatenate(keys)
-
-
-def ref_top(scores, keys, n, known=None):
-    """The best n + 1 under (score descending, key ascending) outside `known`."""
-    if known is not None and len(known):
-        keep = ~np.isin(keys, known)
-        scores, keys = scores[keep], keys[keep]
-    if scores.size > n + 1:     # everything not below the (n + 1)-th score, ties included
-        cut = np.partition(scores, scores.size - (n + 1))[scores.size - (n + 1)]
-        keep = scores >= cut
-        scores, keys = scores[keep], keys[keep]
-    idx = np.lexsort((keys, -scores))[:n + 1]
-    return scores[idx], keys[idx]
-
-
-def keys_to_ids(keys, P):
-    from trigenicinteractionpredictor_amd.scan import rank_order
-    order = rank_order(P)
-    keys = np.asarray(keys, dtype=np.int64)
-    return np.stack([order[keys // (P * P)], order[(keys // P) % P], order[keys % P]], axis=1)
-
-
-def assert_gaps(top_scores):
-    """The precondition, on the reference alone: the order inside the top N + 1 is determined."""
-    if top_scores.size > 1:
-        gaps = (top_scores[:-1] - top_scores[1:]) / np.abs(top_scores[:-1])
-        assert gaps.min() > 1e-9, gaps.min()
+RTOL = scan_ref.RTOL
 
 
 def check(got_scores, got_ids, scores, keys, n, P, known=None):
-    want_s, want_k = ref_top(scores, keys, n, known)
-    assert_gaps(want_s)
+    want_s, want_k = scan_ref.top(scores, keys, n, known)
+    scan_ref.assert_gaps(want_s)
     want_s, want_k = want_s[:n], want_k[:n]
     assert got_ids.dtype == np.int32 and got_scores.dtype == np.float64
     assert got_ids.shape == (want_k.size, 3)
-    np.testing.assert_array_equal(got_ids, keys_to_ids(want_k, P))
+    np.testing.assert_array_equal(got_ids, scan_ref.keys_to_ids(want_k, P))
     np.testing.assert_allclose(got_scores, want_s, rtol=RTOL, atol=0)
     if known is not None and len(known):
-        from trigenicinteractionpredictor_amd.scan import pack_keys, rank_of, rank_order
-        got_k = pack_keys(got_ids, rank_of(rank_order(P)), P)
-        assert not np.isin(got_k, known).any()
-
-
-@functools.lru_cache(maxsize=None)
-def fixture_case(fold, name, it):
-    """(theta, pr, P, known keys, reference scores, reference keys) of one committed fixture."""
-    from trigenicinteractionpredictor_amd import Model
-    from trigenicinteractionpredictor_amd.scan import known_keys
-    _, vec, train, test = load(fold, name)
-    theta, pr = vec["theta_%d" % it], vec["pr_%d" % it]
-    m = Model()
-    m.get_traintest(train, test)
-    assert m.P == theta.shape[0]
-    scores, keys = ref_scan(theta, pr)
-    for a in (scores, keys):
-        a.setflags(write=False)
-    return theta, pr, m.P, known_keys(m), scores, keys
-
-
-def engine(thetas, prs):
-    from trigenicinteractionpredictor_amd.engine import EMEngine
-    thetas, prs = np.asarray(thetas), np.asarray(prs)
-    B, P, K = thetas.shape
-    eng = EMEngine(K, P, B=B)
-    eng.upload(thetas, prs)
-    return eng
-
-
-def random_params(K, P, seed, B=1):
-    rng = np.random.default_rng(seed)
-    th = rng.random((B, P, K))
-    th /= th.sum(axis=2, keepdims=True)
-    pr = rng.random((B, K, K, K, 2))
-    pr /= pr.sum(axis=4, keepdims=True)
-    return th, pr
+        assert not np.isin(scan_ref.packed(got_ids, P), known).any()
 
 
 # ------------------------------------------------------------------ the reference vs the oracle
 def test_reference_scorer_matches_the_c_oracle():
     from oracle import c_oracle
-    theta, pr, P, _, scores, keys = fixture_case("small", "K10_s1", 5)
+    theta, pr, P, _, _, scores, keys = fixture_case("small", "K10_s1", 5)
     assert scores.size == 4455100
     pick = np.random.default_rng(0).choice(scores.size, 2000, replace=False)
-    ids = keys_to_ids(keys[pick], P).astype(np.int32)
+    ids = scan_ref.keys_to_ids(keys[pick], P).astype(np.int32)
     np.testing.assert_allclose(scores[pick], c_oracle.predict(ids, theta, pr), rtol=RTOL, atol=0)
 
 
@@ -135,7 +52,8 @@ CASES = [("tiny", "K10_s1", 25, n) for n in (1, 64, 1000)] + \
 @pytest.mark.parametrize("exclude", [False, True], ids=["all", "novel"])
 @pytest.mark.parametrize("fold,name,it,n", CASES, ids=["%s-%s-N%d" % (c[0], c[1], c[3]) for c in CASES])
 def test_exact_list_on_reference_parameters(fold, name, it, n, exclude):
-    theta, pr, P, known, scores, keys = fixture_case(fold, name, it)
+    theta, pr, P, _, known, scores, keys = fixture_case(fold, name, it)
+    known = known["train", "test"]
     eng = engine(theta[None], pr[None])
     got_s, got_ids = eng.scan_top(n, known if exclude else None, sample=0)
     check(got_s, got_ids, scores, keys, n, P, known if exclude else None)
@@ -145,16 +63,16 @@ def test_exact_list_on_reference_parameters(fold, name, it, n, exclude):
 # ------------------------------------------------------------------ 2. ties
 def test_ties_resolve_by_packed_key():
     K, P, N = 5, 37, 50
-    th, pr = random_params(K, 1, 7)
+    th, pr = scan_ref.random_params(K, 1, 7)
     th = np.repeat(th, P, axis=1)                       # every gene the same row
     eng = engine(th, pr)
     first = np.array(list(itertools.combinations(range(P), 3))[:N + 10])
     first_keys = (first[:, 0] * P + first[:, 1]) * P + first[:, 2]
     s, ids = eng.scan_top(N)
     assert np.unique(s.view(np.int64)).size == 1        # all scores share their bits
-    np.testing.assert_array_equal(ids, keys_to_ids(first_keys[:N], P))
+    np.testing.assert_array_equal(ids, scan_ref.keys_to_ids(first_keys[:N], P))
     s2, ids2 = eng.scan_top(N, known=first_keys[:10])
-    np.testing.assert_array_equal(ids2, keys_to_ids(first_keys[10:N + 10], P))
+    np.testing.assert_array_equal(ids2, scan_ref.keys_to_ids(first_keys[10:N + 10], P))
     np.testing.assert_array_equal(s2.view(np.int64), s.view(np.int64))
     eng.close()
 
@@ -166,7 +84,7 @@ def test_ensemble_and_slots():
     thetas = np.stack([vec["theta_%d" % it] for it in (1, 5, 25)])
     prs = np.stack([vec["pr_%d" % it] for it in (1, 5, 25)])
     P, N = thetas.shape[1], 64
-    per = [ref_scan(thetas[b], prs[b]) for b in range(3)]
+    per = [scan_ref.ref_scores(thetas[b], prs[b]) for b in range(3)]
     keys = per[0][1]
     eng = engine(thetas, prs)
     # the mean over the active prefix, added in slot order
@@ -199,9 +117,9 @@ def test_ensemble_and_slots():
 # ------------------------------------------------------------------ 4. edges
 def test_fewer_eligible_than_n():
     import torch
-    th, pr = random_params(4, 5, 3)
+    th, pr = scan_ref.random_params(4, 5, 3)
     eng = engine(th, pr)
-    scores, keys = ref_scan(th[0], pr[0])
+    scores, keys = scan_ref.ref_scores(th[0], pr[0])
     assert scores.size == 10
     s, ids = eng.scan_top(64)
     check(s, ids, scores, keys, 64, 5)
@@ -218,9 +136,9 @@ def test_fewer_eligible_than_n():
 
 @pytest.mark.parametrize("P", [1, 2, 3, 16, 17])
 def test_small_gene_counts(P):
-    th, pr = random_params(3, P, 11 + P)
+    th, pr = scan_ref.random_params(3, P, 11 + P)
     eng = engine(th, pr)
-    scores, keys = ref_scan(th[0], pr[0])
+    scores, keys = scan_ref.ref_scores(th[0], pr[0])
     assert scores.size == P * (P - 1) * (P - 2) // 6
     s, ids = eng.scan_top(32)
     check(s, ids, scores, keys, 32, P)
@@ -229,7 +147,7 @@ def test_small_gene_counts(P):
 
 def test_n_above_the_cap_is_unsupported():
     from trigenicinteractionpredictor_amd import _lib
-    th, pr = random_params(3, 20, 5)
+    th, pr = scan_ref.random_params(3, 20, 5)
     eng = engine(th, pr)
     cap = eng.lib.mmsbm_scan_max_n()
     assert cap >= 4096
@@ -243,7 +161,8 @@ def test_n_above_the_cap_is_unsupported():
 
 
 def test_scan_leaves_parameters_untouched_and_repeats_bitwise():
-    theta, pr, P, known, _, _ = fixture_case("tiny", "K10_s1", 25)
+    theta, pr, P, _, known, _, _ = fixture_case("tiny", "K10_s1", 25)
+    known = known["train", "test"]
     eng = engine(theta[None], pr[None])
     th0, p0 = eng.theta.cpu().numpy().copy(), eng.pr.cpu().numpy().copy()
     a = eng.scan_top(1000, known)
@@ -260,8 +179,8 @@ def test_scan_leaves_parameters_untouched_and_repeats_bitwise():
 def test_larger_k(K, B):
     """K padding, the large-K LDS sizing and (B = 4, 8 at K = 30) the narrower row blocks."""
     P, N = 50, 64
-    th, pr = random_params(K, P, 100 + K + B, B)
-    per = [ref_scan(th[b], pr[b]) for b in range(B)]
+    th, pr = scan_ref.random_params(K, P, 100 + K + B, B)
+    per = [scan_ref.ref_scores(th[b], pr[b]) for b in range(B)]
     total = per[0][0]
     for b in range(1, B):
         total = total + per[b][0]

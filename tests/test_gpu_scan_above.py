@@ -10,7 +10,6 @@ is checked on the product's own values (score descending, equal scores by key as
 for bit, against the product's other kernels: the census's counts and the scan's top-N list.
 """
 import ctypes
-import functools
 import os
 from math import comb
 
@@ -18,34 +17,13 @@ import numpy as np
 import pytest
 
 import census_ref as ref
+import scan_gpu
+import scan_ref
 from golden_util import GOLDEN, load
+from scan_gpu import engine, random_case
+from scan_ref import packed
 
 pytestmark = pytest.mark.gpu
-
-
-def engine(thetas, prs):
-    from trigenicinteractionpredictor_amd.engine import EMEngine
-    thetas, prs = np.asarray(thetas), np.asarray(prs)
-    B, P, K = thetas.shape
-    eng = EMEngine(K, P, B=B)
-    eng.upload(thetas, prs)
-    return eng
-
-
-@functools.lru_cache(maxsize=None)
-def random_case(K, P, seed):
-    """(theta [P][K], pr, reference scores, reference keys ascending) of one random sample; once."""
-    th, pr = ref.random_params(K, P, seed)
-    scores, keys = ref.ref_scores(th[0], pr[0])
-    assert (np.diff(keys) > 0).all()
-    for a in (scores, keys):
-        a.setflags(write=False)
-    return th[0], pr[0], scores, keys
-
-
-def packed(ids, P):
-    from trigenicinteractionpredictor_amd.scan import pack_keys
-    return pack_keys(ids, ref.rank_tables(P)[1], P)
 
 
 def assert_list_properties(s, ids, P):
@@ -56,7 +34,7 @@ def assert_list_properties(s, ids, P):
     assert np.unique(keys).size == keys.size
     assert (np.diff(s) <= 0).all()                                   # scores do not increase
     assert (np.diff(keys)[np.diff(s) == 0] > 0).all()                # equal scores: keys increase
-    np.testing.assert_array_equal(ids, ref.keys_to_ids(keys, P))    # key order, no slot swapped
+    np.testing.assert_array_equal(ids, scan_ref.keys_to_ids(keys, P))    # key order, no slot swapped
     return keys
 
 
@@ -80,7 +58,7 @@ def check(eng, scores, keys, thresholds, known=None, sample=0):
         if known is not None and len(known):
             want &= ~np.isin(keys, known)
         np.testing.assert_array_equal(np.sort(got), keys[want])
-        np.testing.assert_allclose(s, scores[np.searchsorted(keys, got)], rtol=ref.RTOL, atol=0)
+        np.testing.assert_allclose(s, scores[np.searchsorted(keys, got)], rtol=scan_ref.RTOL, atol=0)
         assert (s >= t).all()
         out.append((s, ids))
     return out
@@ -134,7 +112,7 @@ def test_list_starts_with_the_scan_list_bit_for_bit(mode):
     """Product against product, no tolerance: with t the last score of scan_top(n), the first n
     rows of scan_above(t) are that list and its length is the census's count at t."""
     K, P = 10, 33
-    th, pr = ref.random_params(K, P, 31, B=3)
+    th, pr = scan_ref.random_params(K, P, 31, B=3)
     eng = engine(th, pr)
     sample = 1 if mode == "sample" else None
     known = random_case(K, P, 32)[3][::4].copy()
@@ -179,8 +157,8 @@ def test_exclusion():
 # ------------------------------------------------------------------ 5. ensemble and slots
 def test_ensemble_and_slots():
     K, P = 10, 40
-    th, pr = ref.random_params(K, P, 41, B=3)
-    per = [ref.ref_scores(th[b], pr[b]) for b in range(3)]
+    th, pr = scan_ref.random_params(K, P, 41, B=3)
+    per = [scan_ref.ref_scores(th[b], pr[b]) for b in range(3)]
     keys = per[0][1]
     known = keys[1::5].copy()
     eng = engine(th, pr)
@@ -226,34 +204,18 @@ SENTINEL_ROWS = 64
 SENTINEL_SCORE, SENTINEL_KEY = -7.0, -7
 
 
-class Raw:
-    """mmsbm_scan_above as C sees it: outputs with SENTINEL_ROWS sentinel rows behind `capacity`."""
-
-    def __init__(self, eng):
-        import torch
-        self.eng, self.torch = eng, torch
-        eng.census([])                                              # builds the rank order
-        nbytes = ctypes.c_int64()
-        assert eng.lib.mmsbm_scan_above_workspace_bytes(eng.ctx, ctypes.byref(nbytes)) == 0
-        assert nbytes.value > 0
-        self.ws = torch.empty(nbytes.value, dtype=torch.uint8, device=eng.device)
-
-    def call(self, threshold, capacity, null=False, sample=0, known=None, ws_ptr=None, ws_bytes=None,
-             rows=None):
-        torch, eng = self.torch, self.eng
-        rows = max(capacity, 0) if rows is None else rows
-        self.scores = torch.full((rows + SENTINEL_ROWS,), SENTINEL_SCORE, dtype=torch.float64, device=eng.device)
-        self.keys = torch.full((rows + SENTINEL_ROWS,), SENTINEL_KEY, dtype=torch.int64, device=eng.device)
-        self.count = torch.full((1,), -1, dtype=torch.int64, device=eng.device)
-        known_d = None if known is None else torch.from_numpy(known).to(eng.device)
-        rc = eng.lib.mmsbm_scan_above(
-            eng.ctx, eng._scan_order.data_ptr(), None if known is None else known_d.data_ptr(),
-            0 if known is None else int(known.size), eng.theta.data_ptr(), eng.pr.data_ptr(), sample,
-            float(threshold), capacity, self.ws.data_ptr() if ws_ptr is None else ws_ptr,
-            self.ws.numel() if ws_bytes is None else ws_bytes, None if null else self.scores.data_ptr(),
-            None if null else self.keys.data_ptr(), self.count.data_ptr(), eng._stream())
-        torch.cuda.synchronize(eng.device)
-        return rc, self.scores.cpu().numpy(), self.keys.cpu().numpy(), int(self.count.cpu()[0])
+def above_call(raw, threshold, capacity, null=False, sample=0, known=None, ws_ptr=None, ws_bytes=None, rows=None):
+    """mmsbm_scan_above as C sees it (scan_gpu.Raw), its outputs with SENTINEL_ROWS sentinel rows
+    behind `capacity`: -> (return code, scores, keys, count)."""
+    torch = raw.torch
+    rows = max(capacity, 0) if rows is None else rows
+    scores = raw.full((rows + SENTINEL_ROWS,), torch.float64, SENTINEL_SCORE)
+    keys = raw.full((rows + SENTINEL_ROWS,), torch.int64, SENTINEL_KEY)
+    count = raw.full((1,), torch.int64, -1)
+    ws = (raw.ws.data_ptr() if ws_ptr is None else ws_ptr, raw.ws.numel() if ws_bytes is None else ws_bytes)
+    rc = raw.call((float(threshold), capacity), [None if null else scores, None if null else keys, count],
+                  sample, known, ws=ws)
+    return rc, scores.cpu().numpy(), keys.cpu().numpy(), int(count.cpu()[0])
 
 
 def test_c_call_and_its_capacity_guard():
@@ -265,35 +227,35 @@ def test_c_call_and_its_capacity_guard():
     want = dict(zip(packed(want_ids, P).tolist(), want_s.tolist()))
     count = len(want)
     assert count > 1000 and count == eng.census([t])[0][0]
-    raw = Raw(eng)
+    raw = scan_gpu.Raw(eng, "scan_above")
     # (a) capacity = count: the whole set, the sentinels intact
-    rc, s, k, n = raw.call(t, count)
+    rc, s, k, n = above_call(raw, t, count)
     assert rc == 0 and n == count
     assert dict(zip(k[:count].tolist(), s[:count].tolist())) == want
     assert (s[count:] == SENTINEL_SCORE).all() and (k[count:] == SENTINEL_KEY).all()
     # (b) capacity = count // 3: the full count, distinct members of the set, the sentinels intact
     cap = count // 3
-    rc, s, k, n = raw.call(t, cap)
+    rc, s, k, n = above_call(raw, t, cap)
     assert rc == 0 and n == count
     assert np.unique(k[:cap]).size == cap
     assert all(want.get(key) == score for key, score in zip(k[:cap].tolist(), s[:cap].tolist()))
     assert (s[cap:] == SENTINEL_SCORE).all() and (k[cap:] == SENTINEL_KEY).all()
     # (c) capacity = 0 with null arrays: the count alone
-    rc, _, _, n = raw.call(t, 0, null=True)
+    rc, _, _, n = above_call(raw, t, 0, null=True)
     assert rc == 0 and n == count
     # capacity = 0 with arrays: nothing is written
-    rc, s, k, n = raw.call(t, 0)
+    rc, s, k, n = above_call(raw, t, 0)
     assert rc == 0 and n == count and (s == SENTINEL_SCORE).all() and (k == SENTINEL_KEY).all()
     # (d) the same workspace again, at another threshold and back: the cursor starts from zero
     t2 = float(np.quantile(scores, 0.95))
-    rc, _, _, n2 = raw.call(t2, 0, null=True)
+    rc, _, _, n2 = above_call(raw, t2, 0, null=True)
     assert rc == 0 and n2 == eng.census([t2])[0][0] and 0 < n2 < count
-    rc, _, _, n = raw.call(t, 0, null=True)
+    rc, _, _, n = above_call(raw, t, 0, null=True)
     assert rc == 0 and n == count
     # (e) a threshold above every score: nothing is written
-    rc, s, k, n = raw.call(float(scores.max()) * 1.001, 0, rows=count)
+    rc, s, k, n = above_call(raw, float(scores.max()) * 1.001, 0, rows=count)
     assert rc == 0 and n == 0 and (s == SENTINEL_SCORE).all() and (k == SENTINEL_KEY).all()
-    rc, s, k, n = raw.call(float(scores.max()) * 1.001, count)
+    rc, s, k, n = above_call(raw, float(scores.max()) * 1.001, count)
     assert rc == 0 and n == 0 and (s == SENTINEL_SCORE).all() and (k == SENTINEL_KEY).all()
     eng.close()
 
@@ -304,10 +266,10 @@ def test_refusals_leave_the_context_usable():
     from trigenicinteractionpredictor_amd.scan import LimitError
     K, P = 5, 40
     theta, pr, scores, keys = random_case(K, P, 71)
-    th3, pr3 = ref.random_params(K, P, 72, B=3)
+    th3, pr3 = scan_ref.random_params(K, P, 72, B=3)
     eng = engine(th3, pr3)
     eng.set_active(2)
-    raw = Raw(eng)
+    raw = scan_gpu.Raw(eng, "scan_above")
     t = float(np.quantile(scores, 0.7))
     INVALID = _lib.MMSBM_ERR_INVALID
     for bad in (float("nan"), float("inf"), float("-inf")):
@@ -315,22 +277,20 @@ def test_refusals_leave_the_context_usable():
             eng.scan_above(bad)
         with pytest.raises(ValueError):
             eng.scan_above_async(bad)
-        assert raw.call(bad, 16)[0] == INVALID
-    assert raw.call(t, -1, rows=16)[0] == INVALID                                   # negative capacity
-    assert raw.call(t, 16, null=True)[0] == INVALID                                 # null arrays, capacity > 0
-    assert raw.call(t, 16, ws_bytes=raw.ws.numel() - 1)[0] == INVALID               # too small
-    assert raw.call(t, 16, ws_ptr=raw.ws.data_ptr() + 8, ws_bytes=raw.ws.numel() - 8)[0] == INVALID  # misaligned
-    assert raw.call(t, 16, ws_ptr=0)[0] == INVALID                                  # missing
+        assert above_call(raw, bad, 16)[0] == INVALID
+    assert above_call(raw, t, -1, rows=16)[0] == INVALID                                   # negative capacity
+    assert above_call(raw, t, 16, null=True)[0] == INVALID                                 # null arrays, capacity > 0
+    assert above_call(raw, t, 16, ws_bytes=raw.ws.numel() - 1)[0] == INVALID               # too small
+    assert above_call(raw, t, 16, ws_ptr=raw.ws.data_ptr() + 8, ws_bytes=raw.ws.numel() - 8)[0] == INVALID  # misaligned
+    assert above_call(raw, t, 16, ws_ptr=0)[0] == INVALID                                  # missing
     for sample in (2, 3, -2):                                                       # outside the active prefix
-        assert raw.call(t, 16, sample=sample)[0] == INVALID
+        assert above_call(raw, t, 16, sample=sample)[0] == INVALID
     for sample in (2, 3, -1):
         with pytest.raises(ValueError):
             eng.scan_above(t, sample=sample)
-    assert raw.call(t, 16, known=np.array([5, 3], dtype=np.int64)[:0])[0] == 0      # an empty table is none
-    rc = eng.lib.mmsbm_scan_above(eng.ctx, eng._scan_order.data_ptr(), None, 3, eng.theta.data_ptr(),
-                                  eng.pr.data_ptr(), 0, t, 0, raw.ws.data_ptr(), raw.ws.numel(), None, None,
-                                  raw.count.data_ptr(), eng._stream())
-    assert rc == INVALID                                                            # keys announced, none given
+    assert above_call(raw, t, 16, known=np.array([5, 3], dtype=np.int64)[:0])[0] == 0      # an empty table is none
+    count = raw.full((1,), raw.torch.int64, -1)
+    assert raw.call((t, 0), [None, None, count], n_known=3) == INVALID              # keys announced, none given
     with pytest.raises(ValueError):
         eng.scan_above(t, known=np.array([5, 3], dtype=np.int64))                   # unsorted
     with pytest.raises(ValueError):
@@ -339,10 +299,7 @@ def test_refusals_leave_the_context_usable():
     nbytes = ctypes.c_int64()
     assert eng.lib.mmsbm_scan_above_workspace_bytes(None, ctypes.byref(nbytes)) == INVALID
     assert eng.lib.mmsbm_scan_above_workspace_bytes(eng.ctx, None) == INVALID
-    rc = eng.lib.mmsbm_scan_above(eng.ctx, eng._scan_order.data_ptr(), None, 0, eng.theta.data_ptr(),
-                                  eng.pr.data_ptr(), 0, t, 0, raw.ws.data_ptr(), raw.ws.numel(), None, None,
-                                  None, eng._stream())
-    assert rc == INVALID                                                            # no out_count
+    assert raw.call((t, 0), [None, None, None]) == INVALID                          # no out_count
     # a limit below the count: the message holds the count, and nothing was launched for the list
     count = int(eng.census([t], sample=0)[0][0])
     assert count > 100
@@ -350,7 +307,7 @@ def test_refusals_leave_the_context_usable():
         eng.scan_above(t, sample=0, limit=count - 1)
     assert isinstance(e.value, LimitError) and (e.value.count, e.value.limit) == (count, count - 1)
     # after all of it the context answers a valid call, through the C call and the binding
-    rc, s, k, n = raw.call(t, count)
+    rc, s, k, n = above_call(raw, t, count)
     assert rc == 0 and n == count
     s2, ids2 = eng.scan_above(t, sample=0, limit=count)
     assert s2.size == count and sorted(packed(ids2, P).tolist()) == sorted(k[:count].tolist())
@@ -379,7 +336,7 @@ def test_scan_top_any():
     assert (np.abs(scores - star) <= 1e-7 * star).sum() <= 8        # the precondition, reference alone
     assert np.isin(keys[scores > star * (1 + 1e-7)], got).all()     # everything clearly above is listed
     assert (scores[np.searchsorted(keys, got)] >= star * (1 - 1e-7)).all()
-    np.testing.assert_allclose(s, scores[np.searchsorted(keys, got)], rtol=ref.RTOL, atol=0)
+    np.testing.assert_allclose(s, scores[np.searchsorted(keys, got)], rtol=scan_ref.RTOL, atol=0)
     # n above the eligible total: everything, with and without exclusion
     s, ids = eng.scan_top_any(20000)
     assert s.size == total

@@ -20,20 +20,23 @@ error against the reference it saw (the census and the pair census return intege
 cells show the number of exact count comparisons).  These numbers are reported, not asserted.
 """
 import collections
-import ctypes
 import functools
 from math import comb
 
 import numpy as np
 import pytest
 
+import census_ref
 import pair_census_ref as ref
 import partners_ref
+import scan_ref
 import scan_rule
+from scan_gpu import Raw, engine
+from scan_ref import bits, packed, prefix_mean
 
 pytestmark = pytest.mark.gpu
 
-RTOL = ref.RTOL
+RTOL = scan_ref.RTOL
 P_MATRIX = 70       # 5 b-tiles: 2, 3 and 5 row blocks per a at WB = 4, 2 and 1
 N_TOP = 64
 N_PARTNERS = 50
@@ -68,8 +71,8 @@ Case = collections.namedtuple("Case", "K B P th pr per scores keys")
 def case(K, B, P, seed):
     """Random parameters of B samples with the reference scores of every slot and of the ensemble
     (added in slot order, divided by B); computed once and read-only."""
-    th, pr = ref.random_params(K, P, seed, B)
-    per = [ref.ref_scores(th[b], pr[b]) for b in range(B)]
+    th, pr = scan_ref.random_params(K, P, seed, B)
+    per = [scan_ref.ref_scores(th[b], pr[b]) for b in range(B)]
     keys = per[0][1]
     assert (np.diff(keys) > 0).all()
     per = [s for s, _ in per]
@@ -77,20 +80,6 @@ def case(K, B, P, seed):
     for a in per + [scores, keys, th, pr]:
         a.setflags(write=False)
     return Case(K, B, P, th, pr, per, scores, keys)
-
-
-def prefix_mean(per, n):
-    total = per[0]
-    for b in range(1, n):
-        total = total + per[b]
-    return total / n if n > 1 else total.copy()
-
-
-def engine(c):
-    from trigenicinteractionpredictor_amd.engine import EMEngine
-    eng = EMEngine(c.K, c.P, B=c.B)
-    eng.upload(c.th.copy(), c.pr.copy())        # (the case's arrays are read-only)
-    return eng
 
 
 def cell_of(family, K, ns):
@@ -116,11 +105,6 @@ def known_keys(keys, P):
     return np.union1d(keys[::4], np.array(edge, dtype=np.int64)).astype(np.int64)
 
 
-def packed(ids, P):
-    from trigenicinteractionpredictor_amd.scan import pack_keys
-    return pack_keys(ids, ref.rank_tables(P)[1], P)
-
-
 def threshold_near(scores, q):
     """The midpoint of the wide gap (census_ref.gap_thresholds' kind) nearest the q-quantile."""
     s = np.unique(scores)
@@ -132,30 +116,23 @@ def threshold_near(scores, q):
 
 # ------------------------------------------------------------------------------ the five checks
 def check_scan(eng, c, scores, known, sample, cell, n=N_TOP):
-    want_s, want_k = partners_ref.top(*eligible(scores, c.keys, known), n)
-    assert partners_ref.min_gap(want_s) > 1e-9          # the precondition, reference alone
+    want_s, want_k = scan_ref.top(scores, c.keys, n, known)
+    assert scan_ref.min_gap(want_s) > 1e-9          # the precondition, reference alone
     want_s, want_k = want_s[:n], want_k[:n]
     got_s, got_ids = eng.scan_top(n, known, sample=sample)
     record(cell, got_s, want_s)
     assert got_ids.dtype == np.int32 and got_s.dtype == np.float64
     assert got_ids.shape == (want_k.size, 3)
-    np.testing.assert_array_equal(got_ids, ref.keys_to_ids(want_k, c.P))
+    np.testing.assert_array_equal(got_ids, scan_ref.keys_to_ids(want_k, c.P))
     np.testing.assert_allclose(got_s, want_s, rtol=RTOL, atol=0)
     return got_s, got_ids
 
 
-def eligible(scores, keys, known):
-    if known is not None and len(known):
-        keep = ~np.isin(keys, known)
-        return scores[keep], keys[keep]
-    return scores, keys
-
-
 def check_census(eng, c, scores, known, sample, cell, thresholds=None):
     if thresholds is None:
-        thresholds = ref.gap_thresholds(scores, 40)
-    ref.assert_clear(scores, thresholds)                # the precondition, reference alone
-    want, want_total = ref.ref_census(scores, c.keys, thresholds, known)
+        thresholds = census_ref.gap_thresholds(scores, 40)
+    census_ref.assert_clear(scores, thresholds)         # the precondition, reference alone
+    want, want_total = census_ref.ref_census(scores, c.keys, thresholds, known)
     got, got_total = eng.census(thresholds, known, sample=sample)
     record(cell)
     assert got.dtype == np.int64 and got.shape == want.shape
@@ -166,8 +143,8 @@ def check_census(eng, c, scores, known, sample, cell, thresholds=None):
 
 def check_pair_census(eng, c, scores, known, sample, cell, thresholds=None):
     if thresholds is None:
-        thresholds = ref.gap_thresholds(scores, 40)[:8]
-    ref.assert_clear(scores, thresholds)
+        thresholds = census_ref.gap_thresholds(scores, 40)[:8]
+    census_ref.assert_clear(scores, thresholds)
     _, want = ref.ref_pairs(scores, c.keys, c.P, thresholds, known)
     got = eng.pair_census(thresholds, known, sample=sample)
     record(cell)
@@ -176,7 +153,7 @@ def check_pair_census(eng, c, scores, known, sample, cell, thresholds=None):
 
 
 def check_scan_above(eng, c, scores, known, sample, cell, t):
-    ref.assert_clear(scores, [t])
+    census_ref.assert_clear(scores, [t])
     s, ids = eng.scan_above(t, known, sample=sample)
     assert s.dtype == np.float64 and ids.dtype == np.int32 and ids.shape == (s.size, 3)
     got = packed(ids, c.P)
@@ -196,14 +173,14 @@ def check_scan_above(eng, c, scores, known, sample, cell, t):
 
 def partner_queries(P):
     """The genes at the first, the middle and the last rank position."""
-    order, _ = ref.rank_tables(P)
+    order, _ = scan_ref.rank_tables(P)
     return [int(order[q]) for q in (0, P // 2, P - 1)]
 
 
 def check_partners(eng, c, n_slots, known, sample, cell, n=N_PARTNERS):
     """Three queries against the reference mean of the first n_slots slots; `known` (packed triple
     keys) becomes each query's known pairs."""
-    _, rank = ref.rank_tables(c.P)
+    _, rank = scan_ref.rank_tables(c.P)
     queries = partner_queries(c.P)
     per_query, off, pairs = [], [0], []
     for g in queries:
@@ -237,7 +214,7 @@ def single(K):
 @pytest.mark.parametrize("K", SINGLE_K)
 def test_single_scan(K):
     c = single(K)
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     for known in (None, known_keys(c.keys, c.P)):
         check_scan(eng, c, c.scores, known, 0, cell_of("scan", K, 1))
     eng.close()
@@ -246,7 +223,7 @@ def test_single_scan(K):
 @pytest.mark.parametrize("K", SINGLE_K)
 def test_single_partners(K):
     c = single(K)
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     for known in (None, known_keys(c.keys, c.P)):
         check_partners(eng, c, 1, known, 0, cell_of("partners", K, 1))
     eng.close()
@@ -255,7 +232,7 @@ def test_single_partners(K):
 @pytest.mark.parametrize("K", SINGLE_K)
 def test_single_census(K):
     c = single(K)
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     for known in (None, known_keys(c.keys, c.P)):
         check_census(eng, c, c.scores, known, 0, cell_of("census", K, 1))
     eng.close()
@@ -264,7 +241,7 @@ def test_single_census(K):
 @pytest.mark.parametrize("K", SINGLE_K)
 def test_single_pair_census(K):
     c = single(K)
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     for known in (None, known_keys(c.keys, c.P)):
         check_pair_census(eng, c, c.scores, known, 0, cell_of("pair_census", K, 1))
     eng.close()
@@ -273,7 +250,7 @@ def test_single_pair_census(K):
 @pytest.mark.parametrize("K", SINGLE_K)
 def test_single_scan_above(K):
     c = single(K)
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     t = threshold_near(c.scores, 0.99)
     for known in (None, known_keys(c.keys, c.P)):
         s, _ = check_scan_above(eng, c, c.scores, known, 0, cell_of("scan_above", K, 1), t)
@@ -309,7 +286,7 @@ def test_the_ensemble_cases_cover_the_matrix():
 @pytest.mark.parametrize("K,B,WB", ENSEMBLES, ids=ens_ids)
 def test_ensemble_scan(K, B, WB):
     c, cell = ensemble(K, B, WB, "scan")
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     for known in (None, known_keys(c.keys, c.P)):
         check_scan(eng, c, c.scores, known, None, cell)
     eng.close()
@@ -318,7 +295,7 @@ def test_ensemble_scan(K, B, WB):
 @pytest.mark.parametrize("K,B,WB", ENSEMBLES, ids=ens_ids)
 def test_ensemble_census(K, B, WB):
     c, cell = ensemble(K, B, WB, "census")
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     for known in (None, known_keys(c.keys, c.P)):
         check_census(eng, c, c.scores, known, None, cell)
     eng.close()
@@ -327,7 +304,7 @@ def test_ensemble_census(K, B, WB):
 @pytest.mark.parametrize("K,B,WB", ENSEMBLES, ids=ens_ids)
 def test_ensemble_pair_census(K, B, WB):
     c, cell = ensemble(K, B, WB, "pair_census")
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     for known in (None, known_keys(c.keys, c.P)):
         check_pair_census(eng, c, c.scores, known, None, cell)
     eng.close()
@@ -336,7 +313,7 @@ def test_ensemble_pair_census(K, B, WB):
 @pytest.mark.parametrize("K,B,WB", ENSEMBLES, ids=ens_ids)
 def test_ensemble_scan_above(K, B, WB):
     c, cell = ensemble(K, B, WB, "scan_above")
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     t = threshold_near(c.scores, 0.99)
     for known in (None, known_keys(c.keys, c.P)):
         s, _ = check_scan_above(eng, c, c.scores, known, None, cell, t)
@@ -347,7 +324,7 @@ def test_ensemble_scan_above(K, B, WB):
 @pytest.mark.parametrize("K,B,WB", PARTNER_ENSEMBLES, ids=partner_ens_ids)
 def test_ensemble_partners(K, B, WB):
     c, cell = ensemble(K, B, WB, "partners")
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     for known in (None, known_keys(c.keys, c.P)):
         check_partners(eng, c, B, known, None, cell)
     eng.close()
@@ -364,7 +341,7 @@ def test_tile_edges_at_narrow_row_blocks(K, B, WB, P, family):
     """P below, at and above one 32-row item and two, and around the 16-row items of WB = 1: padded
     rows and columns, items that start mid-triangle and items with no triple."""
     c, cell = ensemble(K, B, WB, family, P)
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     for known in (None, known_keys(c.keys, P)):
         if family == "census":
             check_census(eng, c, c.scores, known, None, cell)
@@ -383,8 +360,8 @@ def test_everything_known_counts_nothing_at_narrow_row_blocks(K, B, WB):
     P = 33
     cells = [ensemble(K, B, WB, f, P)[1] for f in ("census", "pair_census", "scan_above")]
     c = ensemble(K, B, WB, "census", P)[0]
-    eng = engine(c)
-    thresholds = ref.gap_thresholds(c.scores, 20)
+    eng = engine(c.th.copy(), c.pr.copy())
+    thresholds = census_ref.gap_thresholds(c.scores, 20)
     every = c.keys.copy()
     check_census(eng, c, c.scores, every, None, cells[0], thresholds)
     counts, total = eng.census(thresholds, every)
@@ -401,17 +378,13 @@ NARROW = [(10, 10, 2), (10, 19, 1)]
 narrow_ids = ["WB2", "WB1"]
 
 
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
-
-
 @pytest.mark.parametrize("K,B,WB", NARROW, ids=narrow_ids)
 def test_identities_at_narrow_row_blocks(K, B, WB):
     """Product against product, exact, no precondition: the consumers of the shared sweep see the
     scan's score bits and the scan's triples at WB < 4 too."""
     c, _ = ensemble(K, B, WB, "census")
     P, N = c.P, 50
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     upper = np.triu(np.ones((P, P), dtype=bool), k=1)
     for kn in (None, known_keys(c.keys, P)):
         scores, ids = eng.scan_top(N, kn)
@@ -442,18 +415,18 @@ def test_a_slot_of_a_wide_batch_equals_a_batch_of_one(K, B, WB):
     c, _ = ensemble(K, B, WB, "census")
     assert scan_rule.width(K, 1) == 4 and scan_rule.width(K, 1, scan_rule.PARTNERS) == 4
     known = known_keys(c.keys, c.P)
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     queries = partner_queries(c.P)
     for k in (1, B - 1):
         solo_case = Case(K, 1, c.P, c.th[k:k + 1], c.pr[k:k + 1], [c.per[k]], c.per[k], c.keys)
-        solo = engine(solo_case)
+        solo = engine(solo_case.th.copy(), solo_case.pr.copy())
         t = threshold_near(c.per[k], 0.99)
         for e, sample in ((eng, k), (solo, 0)):
             check_census(e, solo_case, c.per[k], known, sample, cell_of("census", K, 1))
         mine, theirs = [], []
         for out, (e, sample) in ((mine, (eng, k)), (theirs, (solo, 0))):
             out.extend(e.scan_top(N_TOP, known, sample=sample))
-            out.extend(e.census(ref.gap_thresholds(c.per[k], 40), known, sample=sample))
+            out.extend(e.census(census_ref.gap_thresholds(c.per[k], 40), known, sample=sample))
             out.append(e.pair_census([t], known, sample=sample))
             out.extend(e.scan_above(t, known, sample=sample))
             for row in e.partners_top(queries, N_PARTNERS, sample=sample):
@@ -470,9 +443,9 @@ def test_repeats_and_grids_at_narrow_row_blocks(K, B, WB, monkeypatch):
     c, _ = ensemble(K, B, WB, "census")
     assert scan_rule.width(K, B, scan_rule.PARTNERS) == WB      # the partner scan narrows here too
     known = known_keys(c.keys, c.P)
-    thresholds = ref.gap_thresholds(c.scores, 40)
+    thresholds = census_ref.gap_thresholds(c.scores, 40)
     t = threshold_near(c.scores, 0.9)
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     th0, p0 = bits(eng.theta.cpu().numpy()), bits(eng.pr.cpu().numpy())
 
     def everything():
@@ -500,7 +473,7 @@ def test_repeats_and_grids_at_narrow_row_blocks(K, B, WB, monkeypatch):
 def test_the_active_prefix_moves_the_width():
     K, B = 10, 19
     c, _ = ensemble(K, B, 1, "census")
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     for n, WB in ((19, 1), (10, 2), (9, 4), (1, 4)):
         assert scan_rule.width(K, n) == WB
         eng.set_active(n)
@@ -512,63 +485,25 @@ def test_the_active_prefix_moves_the_width():
 
 
 # ------------------------------------------------------------------ (f) the refusal boundary
-SENTINEL = -7
+def raw_call(raw, sample):
+    """The family's C call at a small size into sentinel-filled outputs -> the return code."""
+    torch, P = raw.torch, raw.eng.P
+    f64, i32, i64 = torch.float64, torch.int32, torch.int64
+    if raw.family == "scan":
+        return raw.call((8,), [raw.full((8,), f64), raw.full((8, 3), i32), raw.full((1,), i64)], sample)
+    if raw.family == "partners":
+        queries = np.array(partner_queries(P), dtype=np.int32)
+        Q = queries.size
+        return raw.call((8,), [raw.full((Q, 8), f64), raw.full((Q, 8, 3), i32), raw.full((Q,), i64)], sample,
+                        queries=queries)
+    if raw.family == "scan_above":
+        return raw.call((0.6, 64), [raw.full((64,), f64), raw.full((64,), i64), raw.full((1,), i64)], sample)
+    thr = raw.upload(np.array([0.4, 0.6]))
+    out = raw.full((3,), i64) if raw.family == "census" else raw.full((P, P, 2), i32)
+    return raw.call((thr.data_ptr(), 2), [out], sample)
 
 
-class Raw:
-    """One family's C call with sentinel-filled outputs: call(sample) -> the return code; intact()
-    says whether every output word still holds the sentinel."""
-
-    def __init__(self, eng, family):
-        import torch
-        self.eng, self.family, self.torch = eng, family, torch
-        eng.census([], sample=0)                        # builds the rank order
-        lib, ctx, P = eng.lib, eng.ctx, eng.P
-        nbytes = ctypes.c_int64()
-        self.queries = np.array(partner_queries(P), dtype=np.int32)
-        sizes = {"scan": lambda: lib.mmsbm_scan_workspace_bytes(ctx, 8, ctypes.byref(nbytes)),
-                 "partners": lambda: lib.mmsbm_partners_workspace_bytes(ctx, self.queries.size, 8, ctypes.byref(nbytes)),
-                 "census": lambda: lib.mmsbm_census_workspace_bytes(ctx, 2, ctypes.byref(nbytes)),
-                 "pair_census": lambda: lib.mmsbm_pair_census_workspace_bytes(ctx, 2, ctypes.byref(nbytes)),
-                 "scan_above": lambda: lib.mmsbm_scan_above_workspace_bytes(ctx, ctypes.byref(nbytes))}
-        assert sizes[family]() == 0 and nbytes.value > 0        # the workspace follows the shape, not the prefix
-        self.ws = torch.empty(nbytes.value, dtype=torch.uint8, device=eng.device)
-        self.thr = torch.tensor([0.4, 0.6], dtype=torch.float64, device=eng.device)
-
-    def full(self, shape, dtype):
-        return self.torch.full(shape, SENTINEL, dtype=dtype, device=self.eng.device)
-
-    def call(self, sample):
-        torch, eng, lib, P = self.torch, self.eng, self.eng.lib, self.eng.P
-        head = (eng.ctx, eng._scan_order.data_ptr())
-        par = (eng.theta.data_ptr(), eng.pr.data_ptr(), sample)
-        ws = (self.ws.data_ptr(), self.ws.numel())
-        if self.family == "scan":
-            self.outs = [self.full((8,), torch.float64), self.full((8, 3), torch.int32), self.full((1,), torch.int64)]
-            rc = lib.mmsbm_scan_topn(*head, None, 0, *par, 8, *ws, *[o.data_ptr() for o in self.outs], eng._stream())
-        elif self.family == "partners":
-            Q = self.queries.size
-            self.outs = [self.full((Q, 8), torch.float64), self.full((Q, 8, 3), torch.int32),
-                         self.full((Q,), torch.int64)]
-            rc = lib.mmsbm_partners_topn(*head, self.queries.ctypes.data_as(ctypes.c_void_p), Q, None, None, *par, 8,
-                                         *ws, *[o.data_ptr() for o in self.outs], eng._stream())
-        elif self.family == "census":
-            self.outs = [self.full((3,), torch.int64)]
-            rc = lib.mmsbm_scan_census(*head, None, 0, *par, self.thr.data_ptr(), 2, *ws, self.outs[0].data_ptr(),
-                                       eng._stream())
-        elif self.family == "pair_census":
-            self.outs = [self.full((P, P, 2), torch.int32)]
-            rc = lib.mmsbm_pair_census(*head, None, 0, *par, self.thr.data_ptr(), 2, *ws, self.outs[0].data_ptr(),
-                                       eng._stream())
-        else:
-            self.outs = [self.full((64,), torch.float64), self.full((64,), torch.int64), self.full((1,), torch.int64)]
-            rc = lib.mmsbm_scan_above(*head, None, 0, *par, 0.6, 64, *ws, *[o.data_ptr() for o in self.outs],
-                                      eng._stream())
-        torch.cuda.synchronize(eng.device)
-        return rc
-
-    def intact(self):
-        return all(bool((o == SENTINEL).all()) for o in self.outs)
+RAW_SIZES = {"scan": (8,), "partners": (3, 8), "census": (2,), "pair_census": (2,), "scan_above": ()}
 
 
 def binding_call(eng, family, c, scores, n_slots, sample, cell):
@@ -595,18 +530,50 @@ def test_the_first_refused_ensemble_and_the_last_supported(K, family):
     assert B == {(10, False): 37, (32, False): 16, (10, True): 28, (32, True): 12}[(K, family == "partners")]
     assert scan_rule.width(K, B, rule) == 0 and scan_rule.width(K, B - 1, rule) == 1
     c = case(K, B, 40, 800 + K + B)
-    eng = engine(c)
+    eng = engine(c.th.copy(), c.pr.copy())
     # the full prefix: refused through the binding, and through the C call with its outputs untouched
     with pytest.raises(_lib.MMSBMError) as e:
         binding_call(eng, family, c, c.scores, B, None, None)
     assert e.value.code == _lib.MMSBM_ERR_UNSUPPORTED and "one by one" in str(e.value)
-    raw = Raw(eng, family)
-    assert raw.call(-1) == _lib.MMSBM_ERR_UNSUPPORTED and raw.intact()
+    raw = Raw(eng, family, *RAW_SIZES[family])       # the workspace follows the shape, not the prefix
+    assert raw_call(raw, -1) == _lib.MMSBM_ERR_UNSUPPORTED and raw.intact()
     # one slot of the refused engine is a single-sample call
     binding_call(eng, family, c, c.per[0], 1, 0, cell_of(family, K, 1))
-    assert raw.call(0) == _lib.MMSBM_OK and not raw.intact()
+    assert raw_call(raw, 0) == _lib.MMSBM_OK and not raw.intact()
     # one slot fewer: the last supported ensemble
     eng.set_active(B - 1)
     binding_call(eng, family, c, prefix_mean(c.per, B - 1), B - 1, None, cell_of(family, K, B - 1))
-    assert raw.call(-1) == _lib.MMSBM_OK and not raw.intact()
+    assert raw_call(raw, -1) == _lib.MMSBM_OK and not raw.intact()
+    eng.close()
+
+
+# ------------------------------------------------------------------ (g) the launch stream
+@pytest.mark.parametrize("sample", [0, None], ids=["sample", "ensemble"])
+@pytest.mark.parametrize("family", ["scan", "partners", "census", "pair_census", "scan_above"])
+def test_a_side_stream_returns_the_bytes_of_the_current_stream(family, sample):
+    """Two valid calls, plain equality: every tensor of a call belongs to its launch stream.  P = 40
+    has three b-tiles, the last one ragged; B = 2 takes the ensemble path."""
+    import torch
+    from trigenicinteractionpredictor_amd.scan import partner_known
+    c = case(5, 2, 40, 900)
+    known = c.keys[::4].copy()
+    queries = partner_queries(c.P)
+    pairs = partner_known((c.P, scan_ref.keys_to_ids(known, c.P), None), queries)
+    scores = c.per[0] if sample == 0 else c.scores
+    thresholds = census_ref.gap_thresholds(scores, 40)      # unsorted, one duplicate
+    eng = engine(c.th.copy(), c.pr.copy())
+    call = {"scan": lambda s: eng.scan_top_async(N_TOP, known, sample, s),
+            "partners": lambda s: eng.partners_top_async(queries, N_PARTNERS, pairs, sample, s),
+            "census": lambda s: eng.census_async(thresholds, known, sample, s),
+            "pair_census": lambda s: (eng.pair_census_async(thresholds[:12], known, sample, s),),
+            "scan_above": lambda s: eng.scan_above_async(threshold_near(scores, 0.99), known, sample, s)}[family]
+    here = [x.cpu().numpy() for x in call(None)]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    out = call(side)
+    side.synchronize()
+    there = [x.cpu().numpy() for x in out]
+    assert len(here) == len(there) and sum(x.size for x in here) > 0
+    for x, y in zip(here, there):
+        assert x.dtype == y.dtype and x.shape == y.shape and bits(x) == bits(y)
     eng.close()

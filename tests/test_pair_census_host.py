@@ -7,7 +7,9 @@ import os
 import numpy as np
 import pytest
 
+import census_ref
 import pair_census_ref as ref
+import scan_ref
 from golden_util import GOLDEN
 
 TRAIN = os.path.join(GOLDEN, "tiny", "train.dat")
@@ -44,13 +46,13 @@ def test_pair_eligible_against_a_brute_force_loop(P):
 
 
 def test_reference_pairs_sum_to_three_times_the_census():
-    th, pr = ref.random_params(3, 13, 5)
-    scores, keys = ref.ref_scores(th[0], pr[0])
-    thresholds = np.sort(ref.gap_thresholds(scores, 6))
+    th, pr = scan_ref.random_params(3, 13, 5)
+    scores, keys = scan_ref.ref_scores(th[0], pr[0])
+    thresholds = np.sort(census_ref.gap_thresholds(scores, 6))
     known = keys[::4].copy()
     for kn in (None, known):
         rank_mat, gene_mat = ref.ref_pairs(scores, keys, 13, thresholds, kn)
-        counts, _ = ref.ref_census(scores, keys, thresholds, kn)
+        counts, _ = census_ref.ref_census(scores, keys, thresholds, kn)
         assert not np.tril(rank_mat.transpose(2, 0, 1)).any()       # x < y only
         np.testing.assert_array_equal(rank_mat.sum(axis=(0, 1)), 3 * counts)
         np.testing.assert_array_equal(gene_mat, gene_mat.transpose(1, 0, 2))

@@ -114,3 +114,58 @@ def test_driver_parses_its_flags():
     assert (cfg["seed"], cfg["top"], cfg["exclude"], cfg["best"], cfg["out"]) == (1, 10, ("train",), True, "x.tsv")
     assert scan.parse(["--exclude", "none"])["exclude"] == ()
     assert scan.parse([])["exclude"] == ("train", "test")
+
+
+# ------------------------------------------------------------------ the engine's argument checks
+@pytest.mark.parametrize("known,want", [(None, []), ([], []), ([7], [7]), ([3, 5, 9], [3, 5, 9]),
+                                        (np.array([1, 2, 8], dtype=np.int32)[::-1][::-1], [1, 2, 8])],
+                         ids=["none", "empty", "one", "sorted", "int32-view"])
+def test_check_known_keys_returns_contiguous_int64(known, want):
+    from trigenicinteractionpredictor_amd.scan import check_known_keys
+    got = check_known_keys(known)
+    assert got.dtype == np.int64 and got.flags["C_CONTIGUOUS"] and got.tolist() == want
+
+
+@pytest.mark.parametrize("known", [[3, 3], [1, 4, 4, 9], [5, 3], [1, 2, 9, 8]],
+                         ids=["duplicate", "duplicate-inside", "descent", "descent-at-the-end"])
+def test_check_known_keys_refuses_unsorted_or_repeated_keys(known):
+    from trigenicinteractionpredictor_amd.scan import check_known_keys
+    with pytest.raises(ValueError, match=r"^known keys must be sorted and unique \(scan\.known_keys\)$"):
+        check_known_keys(np.array(known, dtype=np.int64))
+
+
+OFFSETS = "known offsets must be 3 non-decreasing indices into the pair keys (scan.partner_known)"
+SLICES = "each query's known pair keys must be sorted and unique (scan.partner_known)"
+
+
+@pytest.mark.parametrize("off,pairs,message", [
+    ([0, 2], [4, 5], OFFSETS),                  # offsets of another Q
+    ([0, 1, 2, 4], [4, 5, 7, 9], OFFSETS),
+    ([-1, 2, 4], [4, 5, 7, 9], OFFSETS),        # a negative first offset
+    ([0, 3, 2], [4, 5, 7, 9], OFFSETS),         # a decreasing offset
+    ([0, 2, 5], [4, 5, 7, 9], OFFSETS),         # a last offset beyond the pairs
+    ([0, 2, 4], [5, 4, 7, 9], SLICES),          # a descent inside the first slice
+    ([0, 2, 4], [4, 5, 9, 7], SLICES),          # ... inside the last
+    ([0, 2, 4], [4, 5, 9, 9], SLICES),          # a repeated key
+    ([1, 3, 4], [0, 9, 4, 7], SLICES)],         # ... inside a slice that starts past the first pair
+    ids=["short-offsets", "long-offsets", "negative-offset", "decreasing-offset", "offset-beyond-pairs",
+         "descent-first-slice", "descent-last-slice", "repeat", "descent-offset-start"])
+def test_check_partner_known_refuses(off, pairs, message):
+    from trigenicinteractionpredictor_amd.scan import check_partner_known
+    with pytest.raises(ValueError) as e:
+        check_partner_known((np.array(off), np.array(pairs)), 2)
+    assert str(e.value) == message
+
+
+def test_check_partner_known_accepts_a_descent_at_a_slice_boundary():
+    from trigenicinteractionpredictor_amd.scan import check_partner_known, partner_known
+    off, pairs = check_partner_known(([0, 2, 4], np.array([4, 9, 5, 7], dtype=np.int32)), 2)
+    assert off.dtype == pairs.dtype == np.int64 and off.tolist() == [0, 2, 4] and pairs.tolist() == [4, 9, 5, 7]
+    for known in (([0, 0, 0], []), ([0, 0, 2], [3, 1][::-1]), ([2, 3, 4], [9, 8, 5, 1])):   # empty slices; pairs
+        off, pairs = check_partner_known(known, 2)                                          # outside every slice
+        assert off.flags["C_CONTIGUOUS"] and pairs.flags["C_CONTIGUOUS"]
+    m = _model("tiny")
+    queries = [5, 0, 5, m.P - 1]
+    off, pairs = partner_known(m, queries)              # what the helper builds passes its own check
+    got = check_partner_known((off, pairs), len(queries))
+    assert got[0].tolist() == off.tolist() and got[1].tolist() == pairs.tolist() and pairs.size > 0

@@ -35,7 +35,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
-from scan_bench import params, random_known  # noqa: E402
+from scan_bench import params, random_known, resident  # noqa: E402
 
 
 def device_ms(call, reps, warmup):
@@ -102,17 +102,9 @@ def shape_record(K, P, B, n_known, reps, warmup):
 
 def resident_call(eng, known, sample):
     import torch
-    known_d = torch.from_numpy(known).to(eng.device)
     thr_d = torch.tensor([2.0], dtype=torch.float64, device=eng.device)
     out = torch.empty(2, dtype=torch.int64, device=eng.device)
-    args = (eng.ctx, eng._scan_order.data_ptr(), known_d.data_ptr(), int(known.size), eng.theta.data_ptr(),
-            eng.pr.data_ptr(), -1 if sample is None else sample, thr_d.data_ptr(), 1, eng._census_ws.data_ptr(),
-            eng._census_ws.numel(), out.data_ptr())
-    keep = (known_d, thr_d, out)
-
-    def call():
-        assert eng.lib.mmsbm_scan_census(*args, eng._stream()) == 0, keep
-    return call
+    return resident(eng, known, sample)("census", (1,), (thr_d, 1), (out,))
 
 
 def heldout_record(K, P, n_train, n_test, reps):

@@ -36,7 +36,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
 from census_bench import device_ms, quantile_thresholds  # noqa: E402
-from scan_bench import params, random_known  # noqa: E402
+from scan_bench import params, random_known, resident  # noqa: E402
 
 
 def dense_adds(P):
@@ -51,22 +51,11 @@ def dense_adds(P):
 def resident_calls(eng, known, sample):
     """The bare C calls (census, pair census) at one threshold above every score."""
     import torch
-    known_d = torch.from_numpy(known).to(eng.device)
     thr_d = torch.tensor([2.0], dtype=torch.float64, device=eng.device)
     out = torch.empty(2, dtype=torch.int64, device=eng.device)
     mat = torch.empty((eng.P, eng.P, 1), dtype=torch.int32, device=eng.device)
-    head = (eng.ctx, eng._scan_order.data_ptr(), known_d.data_ptr(), int(known.size), eng.theta.data_ptr(),
-            eng.pr.data_ptr(), -1 if sample is None else sample, thr_d.data_ptr(), 1)
-    keep = (known_d, thr_d, out, mat)
-
-    def census():
-        assert eng.lib.mmsbm_scan_census(*head, eng._census_ws.data_ptr(), eng._census_ws.numel(),
-                                         out.data_ptr(), eng._stream()) == 0, keep
-
-    def pair():
-        assert eng.lib.mmsbm_pair_census(*head, eng._pair_census_ws.data_ptr(), eng._pair_census_ws.numel(),
-                                         mat.data_ptr(), eng._stream()) == 0, keep
-    return census, pair
+    bind = resident(eng, known, sample)
+    return bind("census", (1,), (thr_d, 1), (out,)), bind("pair_census", (1,), (thr_d, 1), (mat,))
 
 
 def shape_record(K, P, B, n_known, reps, warmup):

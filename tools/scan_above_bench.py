@@ -35,31 +35,20 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
 from census_bench import device_ms, quantile_thresholds  # noqa: E402
-from scan_bench import params, random_known  # noqa: E402
+from scan_bench import params, random_known, resident  # noqa: E402
 
 
 def resident_calls(eng, known, sample, threshold, rows):
     """The bare C calls (census, threshold scan with capacity = rows) at one threshold."""
     import torch
-    known_d = torch.from_numpy(known).to(eng.device)
     thr_d = torch.tensor([threshold], dtype=torch.float64, device=eng.device)
     out = torch.empty(2, dtype=torch.int64, device=eng.device)
     scores = torch.empty(max(rows, 1), dtype=torch.float64, device=eng.device)
     keys = torch.empty(max(rows, 1), dtype=torch.int64, device=eng.device)
     found = torch.zeros(1, dtype=torch.int64, device=eng.device)
-    head = (eng.ctx, eng._scan_order.data_ptr(), known_d.data_ptr(), int(known.size), eng.theta.data_ptr(),
-            eng.pr.data_ptr(), -1 if sample is None else sample)
-    keep = (known_d, thr_d, out, scores, keys)
-
-    def census():
-        assert eng.lib.mmsbm_scan_census(*head, thr_d.data_ptr(), 1, eng._census_ws.data_ptr(),
-                                         eng._census_ws.numel(), out.data_ptr(), eng._stream()) == 0, keep
-
-    def above():
-        assert eng.lib.mmsbm_scan_above(*head, threshold, rows, eng._scan_above_ws.data_ptr(),
-                                        eng._scan_above_ws.numel(), scores.data_ptr(), keys.data_ptr(),
-                                        found.data_ptr(), eng._stream()) == 0, keep
-    return census, above, found
+    bind = resident(eng, known, sample)
+    return (bind("census", (1,), (thr_d, 1), (out,)),
+            bind("scan_above", (), (threshold, rows), (scores, keys, found)), found)
 
 
 def shape_record(K, P, B, n_known, cases, reps, warmup):

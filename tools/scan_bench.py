@@ -49,6 +49,33 @@ def random_known(P, n, seed):
     return np.unique((t[:, 0] * P + t[:, 1]) * P + t[:, 2])
 
 
+ENTRY = {"census": "mmsbm_scan_census", "pair_census": "mmsbm_pair_census", "scan_above": "mmsbm_scan_above"}
+
+
+def resident(eng, known, sample):
+    """The bare C calls of the key-table families on resident tensors (no upload, nothing done to
+    the outputs): -> bind(family, size_args, mid, outs), which gives the call as a function of no
+    arguments.  size_args: what the family's workspace size asks (EMEngine.scan_workspace); mid: the
+    entry's arguments between the sample and the workspace, outs: its output tensors (tensors go by
+    pointer)."""
+    import torch
+    known_d = torch.from_numpy(known).to(eng.device)
+    head = (eng.ctx, eng.scan_order.data_ptr(), known_d.data_ptr(), int(known.size), eng.theta.data_ptr(),
+            eng.pr.data_ptr(), -1 if sample is None else sample)
+
+    def bind(family, size_args, mid, outs):
+        ws = eng.scan_workspace(family, *size_args)
+        entry = getattr(eng.lib, ENTRY[family])
+        args = (*head, *[m.data_ptr() if torch.is_tensor(m) else m for m in mid], ws.data_ptr(), ws.numel(),
+                *[o.data_ptr() for o in outs])
+        keep = (known_d, mid, outs)
+
+        def call():
+            assert entry(*args, eng._stream()) == 0, keep
+        return call
+    return bind
+
+
 def device_ms(eng, N, known, sample, reps, warmup):
     import torch
     for _ in range(warmup):

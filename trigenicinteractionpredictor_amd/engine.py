@@ -7,12 +7,17 @@ is a HIP kernel.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib
+from .scan import (LimitError, bracket_threshold, census_chunks, check_known_keys, check_partner_known,
+                   pair_eligible, rank_of, rank_order)
+
+_CURRENT_STREAM = contextlib.nullcontext()     # a scan call without a stream: nothing to make current
 
 
 def _ptr(t: torch.Tensor) -> int:
@@ -61,12 +66,8 @@ class EMEngine:
         self.active = self.B
         self._sets = set()
         self.workspace = None
-        self._scan_ws = None      # scan_top's scratch and rank order (built on first use)
-        self._scan_order = None
-        self._partners_ws = None  # partners_top's scratch
-        self._census_ws = None    # census's scratch
-        self._pair_census_ws = None   # pair_census's scratch
-        self._scan_above_ws = None    # scan_above's scratch
+        self._scan_ws = {}        # the scan families' scratch, by family (scan_workspace)
+        self._scan_order = None   # their rank order (scan_order: built on first use)
         self.theta = torch.zeros((self.B, self.P, self.K), dtype=torch.float64, device=self.device)
         self.pr = torch.zeros((self.B, self.R, self.K3), dtype=torch.float64, device=self.device)
 
@@ -200,31 +201,85 @@ class EMEngine:
                                               _ptr(out), self._stream()))
         return out[:, :n].cpu().numpy()
 
+    # --------------------------------------------------------- scan families
+    # The scan, the partner scan, the census, the pair census and the threshold scan share what is
+    # below: one check of the sample, one rank order, one scratch tensor per family and one context
+    # that owns every tensor of a call.
+    def _sample(self, sample) -> int:
+        """A slot of the active prefix, or None (-1 in C) for the mean over it."""
+        if sample is None:
+            return -1
+        if not 0 <= int(sample) < self.active:
+            raise ValueError("sample %r outside the active prefix [0, %d)" % (sample, self.active))
+        return int(sample)
+
+    @property
+    def scan_order(self) -> torch.Tensor:
+        """scan.rank_order(P) on the device, int32[P]: the first argument of every scan family's C
+        call.  Built by whichever call comes first, and complete before it returns, so every
+        stream may read it."""
+        if self._scan_order is None:
+            self._scan_order = torch.from_numpy(rank_order(max(self.P, 1))).to(self.device)
+            torch.cuda.current_stream(self.device).synchronize()
+        return self._scan_order
+
+    def scan_workspace(self, family: str, *size_args) -> torch.Tensor:
+        """The scratch of one family ("scan", "partners", "census", "pair_census", "scan_above"),
+        grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device."""
+        nbytes = ctypes.c_int64()
+        _lib.check(getattr(self.lib, "mmsbm_%s_workspace_bytes" % family)(self.ctx, *size_args,
+                                                                          ctypes.byref(nbytes)))
+        ws = self._scan_ws.get(family)
+        if ws is None or ws.numel() < nbytes.value:
+            ws = self._scan_ws[family] = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        return ws
+
+    @contextlib.contextmanager
+    def _scan_call(self, known, sample, stream):
+        """One call of a scan family: checks `known` and `sample`, makes the launch stream current
+        and uploads the keys; -> (head, the stream), head = the C calls' (ctx, order, known or NULL,
+        n_known, theta, pr, sample).  Whatever the call uploads or allocates it creates inside, so
+        every tensor belongs to the stream its kernels run on."""
+        known = check_known_keys(known)
+        sample = self._sample(sample)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(s) if stream is not None else _CURRENT_STREAM:
+            known_d = torch.from_numpy(known).to(self.device) if known.size else None
+            yield (self.ctx, _ptr(self.scan_order), _ptr(known_d) if known.size else None, int(known.size),
+                   _ptr(self.theta), _ptr(self.pr), sample), s
+
+    def _per_threshold(self, family, entry, plan, call, shape, dtype, axis):
+        """The census families' loop inside a _scan_call: one call of `entry` per chunk of `plan`
+        (scan.census_chunks) into a tensor of shape(len(chunk)) -> (the chunks' first len(chunk)
+        entries along `axis`, joined and put back in the caller's threshold order; the last chunk's
+        whole output).  An output without elements is passed as NULL."""
+        (chunks, perm), (head, s) = plan, call
+        ws = self.scan_workspace(family, max(c.size for c in chunks))
+        outs = []
+        for chunk in chunks:
+            thr_d = torch.from_numpy(chunk if chunk.size else np.zeros(1)).to(self.device)
+            out = torch.empty(shape(chunk.size), dtype=dtype, device=self.device)
+            _lib.check(entry(*head, _ptr(thr_d), int(chunk.size), _ptr(ws), ws.numel(),
+                             _ptr(out) if out.numel() else None, s.cuda_stream))
+            outs.append(out)
+        parts = [o.narrow(axis, 0, c.size) for o, c in zip(outs, chunks)]
+        if len(parts) == 1 and (perm == np.arange(perm.size)).all():
+            return parts[0], outs[-1]   # one call, thresholds already ascending: nothing to put back
+        joined = torch.cat(parts, dim=axis)     # sorted position i answers the caller's thresholds[perm[i]]
+        perm_d = torch.from_numpy(perm).to(self.device)
+        return torch.empty_like(joined).index_copy_(axis, perm_d, joined), outs[-1]
+
     def scan_top_async(self, n: int, known: np.ndarray = None, sample: int = None, stream=None):
         """scan_top without the host copy: -> device tensors (scores f64[n], ids int32[n][3],
         count int64[1]); rows from `count` on are NaN / -1.  Nothing synchronises."""
-        from .scan import rank_order
         n = int(n)
-        known = np.zeros(0, np.int64) if known is None else np.ascontiguousarray(known, dtype=np.int64)
-        if known.size > 1 and not (known[1:] > known[:-1]).all():
-            raise ValueError("known keys must be sorted and unique (scan.known_keys)")
-        if sample is not None and not 0 <= int(sample) < self.active:
-            raise ValueError("sample %r outside the active prefix [0, %d)" % (sample, self.active))
-        nbytes = ctypes.c_int64()
-        _lib.check(self.lib.mmsbm_scan_workspace_bytes(self.ctx, n, ctypes.byref(nbytes)))
-        if self._scan_ws is None or self._scan_ws.numel() < nbytes.value:
-            self._scan_ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
-        if self._scan_order is None:
-            self._scan_order = torch.from_numpy(rank_order(max(self.P, 1))).to(self.device)
-        known_d = torch.from_numpy(known).to(self.device)
-        scores = torch.empty(n, dtype=torch.float64, device=self.device)
-        ids = torch.empty((n, 3), dtype=torch.int32, device=self.device)
-        count = torch.empty(1, dtype=torch.int64, device=self.device)
-        _lib.check(self.lib.mmsbm_scan_topn(
-            self.ctx, _ptr(self._scan_order), _ptr(known_d) if known.size else None, int(known.size),
-            _ptr(self.theta), _ptr(self.pr), -1 if sample is None else int(sample), n,
-            _ptr(self._scan_ws), self._scan_ws.numel(), _ptr(scores), _ptr(ids), _ptr(count),
-            self._stream(stream)))
+        with self._scan_call(known, sample, stream) as (head, s):
+            ws = self.scan_workspace("scan", n)
+            scores = torch.empty(n, dtype=torch.float64, device=self.device)
+            ids = torch.empty((n, 3), dtype=torch.int32, device=self.device)
+            count = torch.empty(1, dtype=torch.int64, device=self.device)
+            _lib.check(self.lib.mmsbm_scan_topn(*head, n, _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids),
+                                                _ptr(count), s.cuda_stream))
         return scores, ids, count
 
     def scan_top(self, n: int, known: np.ndarray = None, sample: int = None, stream=None):
@@ -242,44 +297,23 @@ class EMEngine:
         """partners_top without the host copy: -> device tensors (scores f64[Q][n],
         ids int32[Q][n][3], counts int64[Q]); row i answers queries[i], its rows from counts[i] on
         are NaN / -1.  Nothing synchronises."""
-        from .scan import rank_order
         n = int(n)
         queries = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
         Q = int(queries.size)
-        off = pairs = None
-        if known is not None:
-            off = np.ascontiguousarray(known[0], dtype=np.int64).reshape(-1)
-            pairs = np.ascontiguousarray(known[1], dtype=np.int64).reshape(-1)
-            if off.size != Q + 1 or off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > pairs.size:
-                raise ValueError("known offsets must be %d non-decreasing indices into the pair keys "
-                                 "(scan.partner_known)" % (Q + 1))
-            rising = pairs[1:] > pairs[:-1]
-            starts = off[1:-1]
-            rising[starts[(starts > 0) & (starts < pairs.size)] - 1] = True   # a new query's slice
-            if not rising[int(off[0]):max(int(off[-1]) - 1, int(off[0]))].all():
-                raise ValueError("each query's known pair keys must be sorted and unique "
-                                 "(scan.partner_known)")
-        if sample is not None and not 0 <= int(sample) < self.active:
-            raise ValueError("sample %r outside the active prefix [0, %d)" % (sample, self.active))
-        nbytes = ctypes.c_int64()
-        _lib.check(self.lib.mmsbm_partners_workspace_bytes(self.ctx, Q, n, ctypes.byref(nbytes)))
-        if self._partners_ws is None or self._partners_ws.numel() < nbytes.value:
-            self._partners_ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
-        if self._scan_order is None:
-            self._scan_order = torch.from_numpy(rank_order(max(self.P, 1))).to(self.device)
-        off_d = pairs_d = None
-        if off is not None:
-            off_d = torch.from_numpy(off).to(self.device)
-            pairs_d = torch.from_numpy(pairs if pairs.size else np.zeros(1, np.int64)).to(self.device)
-        scores = torch.empty((Q, n), dtype=torch.float64, device=self.device)
-        ids = torch.empty((Q, n, 3), dtype=torch.int32, device=self.device)
-        counts = torch.empty(Q, dtype=torch.int64, device=self.device)
-        _lib.check(self.lib.mmsbm_partners_topn(
-            self.ctx, _ptr(self._scan_order), _host_ptr(queries), Q,
-            _ptr(off_d) if off_d is not None else None, _ptr(pairs_d) if pairs_d is not None else None,
-            _ptr(self.theta), _ptr(self.pr), -1 if sample is None else int(sample), n,
-            _ptr(self._partners_ws), self._partners_ws.numel(), _ptr(scores), _ptr(ids), _ptr(counts),
-            self._stream(stream)))
+        off, pairs = (None, None) if known is None else check_partner_known(known, Q)
+        with self._scan_call(None, sample, stream) as ((ctx, order, _, _, *params), s):   # no key table
+            ws = self.scan_workspace("partners", Q, n)
+            off_d = pairs_d = None
+            if off is not None:
+                off_d = torch.from_numpy(off).to(self.device)
+                pairs_d = torch.from_numpy(pairs if pairs.size else np.zeros(1, np.int64)).to(self.device)
+            scores = torch.empty((Q, n), dtype=torch.float64, device=self.device)
+            ids = torch.empty((Q, n, 3), dtype=torch.int32, device=self.device)
+            counts = torch.empty(Q, dtype=torch.int64, device=self.device)
+            _lib.check(self.lib.mmsbm_partners_topn(
+                ctx, order, _host_ptr(queries), Q, _ptr(off_d) if off_d is not None else None,
+                _ptr(pairs_d) if pairs_d is not None else None, *params, n, _ptr(ws), ws.numel(),
+                _ptr(scores), _ptr(ids), _ptr(counts), s.cuda_stream))
         return scores, ids, counts
 
     def partners_top(self, queries, n: int, known=None, sample: int = None, stream=None):
@@ -297,40 +331,19 @@ class EMEngine:
     def census_async(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None):
         """census without the host copy: -> device tensors (counts int64[len(thresholds)] in the
         caller's order, total int64[1]).  Nothing synchronises."""
-        from .scan import census_chunks, rank_order
-        max_m = int(self.lib.mmsbm_census_max_m())
-        chunks, perm = census_chunks(thresholds, max_m)      # ValueError on a NaN or infinite one
-        known = np.zeros(0, np.int64) if known is None else np.ascontiguousarray(known, dtype=np.int64)
-        if known.size > 1 and not (known[1:] > known[:-1]).all():
-            raise ValueError("known keys must be sorted and unique (scan.known_keys)")
-        if sample is not None and not 0 <= int(sample) < self.active:
-            raise ValueError("sample %r outside the active prefix [0, %d)" % (sample, self.active))
-        nbytes = ctypes.c_int64()
-        _lib.check(self.lib.mmsbm_census_workspace_bytes(self.ctx, max(c.size for c in chunks),
-                                                         ctypes.byref(nbytes)))
-        if self._census_ws is None or self._census_ws.numel() < nbytes.value:
-            self._census_ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
-        if self._scan_order is None:
-            self._scan_order = torch.from_numpy(rank_order(max(self.P, 1))).to(self.device)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(s):      # the tensors below belong to the stream the kernels run on
-            known_d = torch.from_numpy(known).to(self.device)
-            outs = []
-            for chunk in chunks:
-                thr_d = torch.from_numpy(chunk if chunk.size else np.zeros(1)).to(self.device)
-                out = torch.empty(chunk.size + 1, dtype=torch.int64, device=self.device)
-                _lib.check(self.lib.mmsbm_scan_census(
-                    self.ctx, _ptr(self._scan_order), _ptr(known_d) if known.size else None, int(known.size),
-                    _ptr(self.theta), _ptr(self.pr), -1 if sample is None else int(sample), _ptr(thr_d),
-                    int(chunk.size), _ptr(self._census_ws), self._census_ws.numel(), _ptr(out), s.cuda_stream))
-                outs.append(out)
-            total = outs[-1][-1:]
-            if len(outs) == 1 and (perm == np.arange(perm.size)).all():
-                counts = outs[0][:-1]      # one call, thresholds already ascending: nothing to put back
-            else:            # sorted position i answers the caller's thresholds[perm[i]]
-                counts = torch.empty(perm.size, dtype=torch.int64, device=self.device)
-                counts[torch.from_numpy(perm).to(self.device)] = torch.cat([o[:-1] for o in outs])
-        return counts, total
+        plan = self._census_plan(thresholds)
+        with self._scan_call(known, sample, stream) as call:
+            return self._census(plan, call)
+
+    def _census_plan(self, thresholds):
+        return census_chunks(thresholds, int(self.lib.mmsbm_census_max_m()))   # ValueError on a NaN or infinite one
+
+    def _census(self, plan, call):
+        """census_async inside a _scan_call: every chunk's output is its counts and then the total
+        of the eligible triples (an empty chunk: the call that returns the total)."""
+        counts, last = self._per_threshold("census", self.lib.mmsbm_scan_census, plan, call,
+                                           lambda m: (m + 1,), torch.int64, 0)
+        return counts, last[-1:]
 
     def census(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None):
         """The score census (include/mmsbm.h mmsbm_scan_census): -> (counts int64[len(thresholds)],
@@ -348,31 +361,22 @@ class EMEngine:
     def _scan_above(self, threshold, known, sample, stream, limit):
         """-> (scores f64[n] and packed keys int64[n] on the device, sorted by the scan's total
         order; the kernel's count int64[1] on the device; the census's count n; the launch stream)."""
-        from .scan import LimitError
         threshold = float(threshold)
         if not np.isfinite(threshold):
             raise ValueError("the threshold must be a finite number")
-        counts, _ = self.census_async([threshold], known, sample, stream)    # validates known and sample
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(s):
-            n = int(counts.cpu()[0])        # the same score bits: exactly the rows the kernel will find
-        if n > int(limit):
-            raise LimitError(n, int(limit))
-        known = np.zeros(0, np.int64) if known is None else np.ascontiguousarray(known, dtype=np.int64)
-        nbytes = ctypes.c_int64()
-        _lib.check(self.lib.mmsbm_scan_above_workspace_bytes(self.ctx, ctypes.byref(nbytes)))
-        if self._scan_above_ws is None or self._scan_above_ws.numel() < nbytes.value:
-            self._scan_above_ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
-        with torch.cuda.stream(s):      # the tensors below belong to the stream the kernels run on
-            known_d = torch.from_numpy(known).to(self.device)
+        plan = self._census_plan([threshold])
+        with self._scan_call(known, sample, stream) as call:    # one upload of the keys for both kernels
+            head, s = call
+            n = int(self._census(plan, call)[0].cpu()[0])   # the same score bits: exactly the rows the kernel will find
+            if n > int(limit):
+                raise LimitError(n, int(limit))
+            ws = self.scan_workspace("scan_above")
             scores = torch.empty(n, dtype=torch.float64, device=self.device)
             keys = torch.empty(n, dtype=torch.int64, device=self.device)
             found = torch.empty(1, dtype=torch.int64, device=self.device)
-            _lib.check(self.lib.mmsbm_scan_above(
-                self.ctx, _ptr(self._scan_order), _ptr(known_d) if known.size else None, int(known.size),
-                _ptr(self.theta), _ptr(self.pr), -1 if sample is None else int(sample), threshold, n,
-                _ptr(self._scan_above_ws), self._scan_above_ws.numel(), _ptr(scores) if n else None,
-                _ptr(keys) if n else None, _ptr(found), s.cuda_stream))
+            _lib.check(self.lib.mmsbm_scan_above(*head, threshold, n, _ptr(ws), ws.numel(),
+                                                 _ptr(scores) if n else None, _ptr(keys) if n else None,
+                                                 _ptr(found), s.cuda_stream))
             # the rows arrive in any order; two stable sorts give the scan's: score descending,
             # equal scores by key ascending
             keys, at = torch.sort(keys, stable=True)
@@ -384,7 +388,7 @@ class EMEngine:
     def _keys_to_ids(self, keys: torch.Tensor) -> torch.Tensor:
         """Packed keys int64[n] (device) -> gene ids int32[n][3] in key order."""
         P = max(self.P, 1)
-        order = self._scan_order
+        order = self.scan_order
         return torch.stack([order[keys // (P * P)], order[(keys // P) % P], order[keys % P]], dim=1)
 
     def scan_above_async(self, threshold, known: np.ndarray = None, sample: int = None, stream=None,
@@ -419,7 +423,6 @@ class EMEngine:
         scan_above fetches what lies at or above it and the list is cut to n.  Exact: the three
         kernels see the same score bits under the same total order.  `limit`: as for scan_above
         (reached only when more than that many triples tie around rank n)."""
-        from .scan import bracket_threshold
         n = int(n)
         if n < 1:
             raise ValueError("scan_top_any needs n >= 1")
@@ -438,46 +441,16 @@ class EMEngine:
         """The pair census in rank positions: -> (device int32 [P][P][len(thresholds)], filled for
         x < y only, thresholds in the caller's order; the launch stream).  One call of
         mmsbm_pair_census per mmsbm_pair_census_max_m() thresholds."""
-        from .scan import census_chunks, rank_order
-        max_m = int(self.lib.mmsbm_pair_census_max_m())
-        chunks, perm = census_chunks(thresholds, max_m)      # ValueError on a NaN or infinite one
-        known = np.zeros(0, np.int64) if known is None else np.ascontiguousarray(known, dtype=np.int64)
-        if known.size > 1 and not (known[1:] > known[:-1]).all():
-            raise ValueError("known keys must be sorted and unique (scan.known_keys)")
-        if sample is not None and not 0 <= int(sample) < self.active:
-            raise ValueError("sample %r outside the active prefix [0, %d)" % (sample, self.active))
-        nbytes = ctypes.c_int64()
-        _lib.check(self.lib.mmsbm_pair_census_workspace_bytes(self.ctx, max(c.size for c in chunks),
-                                                              ctypes.byref(nbytes)))
-        if self._pair_census_ws is None or self._pair_census_ws.numel() < nbytes.value:
-            self._pair_census_ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
-        if self._scan_order is None:
-            self._scan_order = torch.from_numpy(rank_order(max(self.P, 1))).to(self.device)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(s):      # the tensors below belong to the stream the kernels run on
-            known_d = torch.from_numpy(known).to(self.device)
-            outs = []
-            for chunk in chunks:
-                thr_d = torch.from_numpy(chunk if chunk.size else np.zeros(1)).to(self.device)
-                out = torch.empty((self.P, self.P, chunk.size), dtype=torch.int32, device=self.device)
-                _lib.check(self.lib.mmsbm_pair_census(
-                    self.ctx, _ptr(self._scan_order), _ptr(known_d) if known.size else None, int(known.size),
-                    _ptr(self.theta), _ptr(self.pr), -1 if sample is None else int(sample), _ptr(thr_d),
-                    int(chunk.size), _ptr(self._pair_census_ws), self._pair_census_ws.numel(),
-                    _ptr(out) if chunk.size else None, s.cuda_stream))
-                outs.append(out)
-            if len(outs) == 1 and (perm == np.arange(perm.size)).all():
-                mat = outs[0]           # one call, thresholds already ascending: nothing to put back
-            else:            # sorted position i answers the caller's thresholds[perm[i]]
-                mat = torch.empty((self.P, self.P, perm.size), dtype=torch.int32, device=self.device)
-                mat[:, :, torch.from_numpy(perm).to(self.device)] = torch.cat(outs, dim=2)
-        return mat, s
+        plan = census_chunks(thresholds, int(self.lib.mmsbm_pair_census_max_m()))   # ValueError on a NaN or infinite one
+        with self._scan_call(known, sample, stream) as call:
+            mat, _ = self._per_threshold("pair_census", self.lib.mmsbm_pair_census, plan, call,
+                                         lambda m: (self.P, self.P, m), torch.int32, 2)
+        return mat, call[1]
 
     def pair_census_async(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None):
         """pair_census without the host copy: -> a device tensor int32 [P][P][len(thresholds)] in
         gene ids, symmetric with a zero diagonal, thresholds in the caller's order.  Nothing
         synchronises."""
-        from .scan import rank_of, rank_order
         mat, s = self._pair_census_rank(thresholds, known, sample, stream)
         with torch.cuda.stream(s):
             rank = torch.from_numpy(rank_of(rank_order(self.P))).to(self.device)
@@ -503,7 +476,6 @@ class EMEngine:
         int32[n'][2] in key order) on the host, n' = min(n, C(P, 2)).  Ordered by count descending,
         equal counts by the pair's rank-position key x P + y ascending.  The selection is one
         torch.topk on the device over count * P^2 + (P^2 - 1 - key)."""
-        from .scan import pair_eligible, rank_order
         mat, s = self._pair_census_rank([float(threshold)], known, sample, None)
         P = self.P
         n = max(0, min(int(n), P * (P - 1) // 2))

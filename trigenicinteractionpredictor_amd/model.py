@@ -423,8 +423,7 @@ class Model:
         from .scan import known_keys
         eng = self._push()
         scores, ids = eng.scan_top(int(n), known_keys(self, exclude), sample=0)
-        return [[float(p), "_".join(str(int(g)) for g in row), sorted(self.id_gene[int(g)] for g in row)]
-                for p, row in zip(scores, ids)]
+        return self._rows(scores, ids)
 
     def predict_novel_any(self, n, exclude=("train", "test")):
         """predict_novel for any n >= 1: above the scan's cap of 4096 rows, censuses bracket the

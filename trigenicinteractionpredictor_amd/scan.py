@@ -164,6 +164,34 @@ def partner_known(source, queries, exclude=SETS):
     return off, pairs.astype(np.int64)
 
 
+def check_known_keys(known) -> np.ndarray:
+    """The known-key table as the engine's scan families take it -> contiguous int64 (None: no
+    keys); ValueError unless the keys are sorted and unique, as known_keys gives them."""
+    known = np.zeros(0, np.int64) if known is None else np.ascontiguousarray(known, dtype=np.int64)
+    if known.size > 1 and not (known[1:] > known[:-1]).all():
+        raise ValueError("known keys must be sorted and unique (scan.known_keys)")
+    return known
+
+
+def check_partner_known(known, Q: int):
+    """The partner scan's (known_off, known_pairs) for Q queries -> both as contiguous int64;
+    ValueError unless the offsets are Q + 1 non-decreasing indices into the pairs and every query's
+    slice is sorted and unique (a key may fall from one slice to the next), as partner_known gives
+    them."""
+    off = np.ascontiguousarray(known[0], dtype=np.int64).reshape(-1)
+    pairs = np.ascontiguousarray(known[1], dtype=np.int64).reshape(-1)
+    if off.size != Q + 1 or off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > pairs.size:
+        raise ValueError("known offsets must be %d non-decreasing indices into the pair keys "
+                         "(scan.partner_known)" % (Q + 1))
+    rising = pairs[1:] > pairs[:-1]
+    starts = off[1:-1]
+    rising[starts[(starts > 0) & (starts < pairs.size)] - 1] = True   # a new query's slice
+    if not rising[int(off[0]):max(int(off[-1]) - 1, int(off[0]))].all():
+        raise ValueError("each query's known pair keys must be sorted and unique "
+                         "(scan.partner_known)")
+    return off, pairs
+
+
 # ------------------------------------------------------------------------------------- census
 def strict_thresholds(scores) -> np.ndarray:
     """The next double above each score: a census at them counts the triples scoring STRICTLY
@@ -247,11 +275,12 @@ def bracket_threshold(n: int, hi: float, count_at, max_m: int = MAX_CENSUS_M) ->
     return lo
 
 
-def parse_network_threshold(text) -> float:
-    """'0.5' -> 0.5; ValueError unless it is one number in (0, 1]."""
+def parse_unit_threshold(text, what: str) -> float:
+    """'0.5' -> 0.5; ValueError unless it is one number in (0, 1].  `what` names the option's
+    threshold in the message ("pair", "network")."""
     v = float(text)
     if not 0.0 < v <= 1.0:      # NaN fails the comparison
-        raise ValueError("network threshold outside (0, 1]")
+        raise ValueError("%s threshold outside (0, 1]" % what)
     return v
 
 
@@ -291,14 +320,6 @@ def pair_rows(id_gene, counts, eligible, ids):
     """pairs_top's arrays -> rows [count, eligible, "i_j", [name1, name2]], names sorted."""
     return [[int(n), int(e), pair_key(i, j), sorted((id_gene[int(i)], id_gene[int(j)]))]
             for n, e, (i, j) in zip(counts, eligible, ids)]
-
-
-def parse_pair_threshold(text) -> float:
-    """'0.5' -> 0.5; ValueError unless it is one number in (0, 1]."""
-    v = float(text)
-    if not 0.0 < v <= 1.0:      # NaN fails the comparison
-        raise ValueError("pair threshold outside (0, 1]")
-    return v
 
 
 def parse_thresholds(text):
@@ -437,7 +458,7 @@ def parse(argv):
                 cfg["gene_census"] = arg
             elif opt == "--pair-threshold":
                 try:
-                    cfg["pair_threshold"] = parse_pair_threshold(arg)
+                    cfg["pair_threshold"] = parse_unit_threshold(arg, "pair")
                 except ValueError:
                     print("\n\nERROR: --pair-threshold should be a number in (0, 1]")
                     raise cli.ArgError()
@@ -445,7 +466,7 @@ def parse(argv):
                 cfg["network"] = arg
             elif opt == "--network-threshold":
                 try:
-                    cfg["network_threshold"] = parse_network_threshold(arg)
+                    cfg["network_threshold"] = parse_unit_threshold(arg, "network")
                 except ValueError:
                     print("\n\nERROR: --network-threshold should be a number in (0, 1]")
                     raise cli.ArgError()
@@ -498,11 +519,12 @@ def partner_queries(model, cfg):
         raise cli.ArgError()
 
 
-def census_tables(eng, model, cfg, sample, extras):
-    """The driver's --census and --heldout-ranks tables into `extras` (see run)."""
+def census_tables(eng, model, cfg, known, sample, extras):
+    """The driver's --census and --heldout-ranks tables into `extras` (see run); `known`: the
+    keys --exclude names."""
     if cfg.get("census"):
         thresholds = sorted(cfg.get("thresholds") or DEFAULT_THRESHOLDS, reverse=True)
-        counts, total = eng.census(thresholds, known_keys(model, cfg["exclude"]), sample)
+        counts, total = eng.census(thresholds, known, sample)
         extras["census"] = (thresholds, [int(c) for c in counts], total)
     if cfg.get("heldout_ranks"):
         ids, link_counts = model._link_arrays(1)
@@ -510,27 +532,25 @@ def census_tables(eng, model, cfg, sample, extras):
         extras["heldout_ranks"] = heldout_rows(ids, link_counts, probs, ranks)
 
 
-def pair_tables(eng, model, cfg, sample, extras):
+def pair_tables(eng, model, cfg, known, sample, extras):
     """The driver's --pairs and --gene-census tables into `extras` (see run)."""
     if cfg.get("pairs"):
-        counts, eligible, ids = eng.pairs_top(cfg["top"], cfg["pair_threshold"],
-                                              known_keys(model, cfg["exclude"]), sample)
+        counts, eligible, ids = eng.pairs_top(cfg["top"], cfg["pair_threshold"], known, sample)
         extras["pairs"] = pair_rows(model.id_gene, counts, eligible, ids)
     if cfg.get("gene_census"):
         thresholds = sorted(cfg.get("thresholds") or DEFAULT_THRESHOLDS, reverse=True)
-        counts = eng.gene_census(thresholds, known_keys(model, cfg["exclude"]), sample)
+        counts = eng.gene_census(thresholds, known, sample)
         extras["gene_census"] = (thresholds, [model.id_gene[g] for g in range(model.P)], counts)
 
 
-def network_table(eng, model, cfg, sample, extras):
+def network_table(eng, model, cfg, known, sample, extras):
     """The driver's --network table into `extras` (see run); cli.ArgError when it would hold more
     rows than --network-limit."""
     from . import cli
     if not cfg.get("network"):
         return
     try:
-        scores, ids = eng.scan_above(cfg["network_threshold"], known_keys(model, cfg["exclude"]), sample,
-                                     limit=cfg["network_limit"])
+        scores, ids = eng.scan_above(cfg["network_threshold"], known, sample, limit=cfg["network_limit"])
     except LimitError as e:
         eng.close()
         print("\n\nERROR: --network: %d triples have a probability of %r or more, above --network-limit %d: "
@@ -562,10 +582,11 @@ def run(cfg, out=print, extras=None):
         eng.upload_slot(b, theta, pr)
     eng.iterate(cfg["iterations"])
     sample = int(np.argmax(eng.loglik(_lib.SET_TRAIN))) if cfg["best"] else None
+    known = known_keys(model, cfg["exclude"])
     if extras is not None:
-        census_tables(eng, model, cfg, sample, extras)
-        pair_tables(eng, model, cfg, sample, extras)
-        network_table(eng, model, cfg, sample, extras)
+        census_tables(eng, model, cfg, known, sample, extras)
+        pair_tables(eng, model, cfg, known, sample, extras)
+        network_table(eng, model, cfg, known, sample, extras)
     if queries is not None:
         out("partner pairs of %d genes: %s" % (len(queries), "sample %d" % sample if sample is not None
                                                else "mean of %d samples" % B))
@@ -576,10 +597,9 @@ def run(cfg, out=print, extras=None):
                 for g, (scores, ids) in zip(queries, lists) for i, (p, row) in enumerate(zip(scores, ids))]
     out("scanning %d genes: %s" % (model.P, "sample %d" % sample if sample is not None
                                    else "mean of %d samples" % B))
-    scores, ids = eng.scan_top(cfg["top"], known_keys(model, cfg["exclude"]), sample)
+    scores, ids = eng.scan_top(cfg["top"], known, sample)
     eng.close()
-    return [[i + 1, float(p), "_".join(str(g) for g in row), sorted(model.id_gene[int(g)] for g in row)]
-            for i, (p, row) in enumerate(zip(scores, ids))]
+    return network_rows(model.id_gene, scores, ids)
 
 
 def write_tsv(rows, stream, partners=False):
