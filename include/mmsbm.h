@@ -304,6 +304,56 @@ int mmsbm_scan_above(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known,
                      int64_t capacity, void *ws, int64_t ws_bytes, double *out_scores,
                      int64_t *out_keys, int64_t *out_count, void *stream);
 
+/* Vote scan: for every one of the scan's eligible triples, in how many of the scored slots (EM
+ * restarts) its score is at or above one threshold; counted and listed.  A mean of 0.5 can be eight
+ * restarts at 0.5 or four at 0.95 and four at 0.05: every other family reduces the batch to one score
+ * per triple first and cannot tell.  order, known, n_known, theta, pr, sample, ws and stream mean what
+ * they mean for mmsbm_scan_census, and a triple is eligible exactly as there (rank positions
+ * a < b < c < P whose packed key is not among `known`).
+ * The scored slots: the ns = active-prefix slots for sample = -1, that one slot (ns = 1) for
+ * sample >= 0.  A slot's own score is the bits a single-sample call on that slot forms (the ensemble
+ * path forms every slot's tile from zero with that call's MFMA chain before it adds them; the compare
+ * sits there).  An eligible triple's votes = the number of scored slots whose own score is
+ * >= threshold, in [0, ns].  A hit is an eligible triple with votes >= min_votes, 1 <= min_votes <= ns.
+ * Result (device): out_hist int64[ns + 1], zeroed by the call on `stream` and always written:
+ * out_hist[v] = the eligible triples with exactly v votes; its sum is mmsbm_scan_census's total, and
+ * sum_v v out_hist[v] is the sum over the scored slots s of mmsbm_scan_census's count at `threshold`
+ * for sample = s.  *out_count int64[1] = the number of hits, always the full number, also when it
+ * exceeds `capacity`: the sum of out_hist[v] over v >= min_votes.  The first
+ * min(*out_count, capacity) rows of out_scores f64[capacity], out_keys int64[capacity] and out_votes
+ * int32[capacity] hold hits: the ensemble score (the slots' tiles added in slot order and divided by
+ * ns: the bits mmsbm_scan_topn, the census and the threshold scan give that triple for the same
+ * `sample`), the packed key (a P + b) P + c and the votes.  The rows are written exactly as
+ * mmsbm_scan_above writes its rows: in ARRIVAL order, so that only the SET of rows is defined;
+ * complete, each hit once, when *out_count <= capacity; `capacity` distinct hits otherwise; rows from
+ * min(*out_count, capacity) on are not touched and no address at or past row `capacity` is ever
+ * formed.  capacity = 0 is a histogram-only call; the three row arrays may then be NULL.  P < 3:
+ * out_hist is all zeros and *out_count = 0.
+ * Everything that crosses a lane or a workgroup is an integer (ballots, popcounts, LDS adds, one
+ * 64-bit global add per workgroup and nonzero counter into out_hist, one 64-bit atomic add per flush
+ * of a wave's staging buffer on a cursor in the workspace, which the call zeroes on `stream`; a
+ * histogram-only call stages nothing and takes *out_count from out_hist); no
+ * floating-point value is combined beyond the score phase's own fixed-order sums, so out_hist, the
+ * set of rows and every row's bits do not depend on the grid, the batch the slots sit in or the
+ * arrival order.
+ * Checked before any device call: a NULL ctx, order, theta, pr, out_hist or out_count, a NULL row
+ * array with capacity > 0, a NaN or infinite threshold, capacity < 0, min_votes outside [1, ns], a
+ * bad sample, a bad known-key table or a missing, misaligned or small workspace: MMSBM_ERR_INVALID;
+ * K outside [1, MMSBM_MAX_K], P above 2 000 000 (the packed key) or an ensemble whose W tile exceeds
+ * the LDS (the census's rule and its 64 KiB): MMSBM_ERR_UNSUPPORTED.  The list has no cap but the
+ * caller's memory (20 bytes per row).
+ * ws: mmsbm_scan_votes_workspace_bytes(ctx) bytes of device scratch, 16-byte aligned, the caller's;
+ * its size follows the context's shape only.  theta and pr are only read; all launches go to
+ * `stream` and nothing synchronises.  The environment variable MMSBM_SCAN_VOTES_GRID=<workgroups>
+ * overrides the grid (measurement; neither out_hist nor the set of rows depends on it).  Needs
+ * R >= 2.  Replaces nothing in the reference. */
+int mmsbm_scan_votes_workspace_bytes(const mmsbm_ctx *ctx, int64_t *bytes);
+int mmsbm_scan_votes(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known, int64_t n_known,
+                     const double *theta, const double *pr, int32_t sample, double threshold,
+                     int32_t min_votes, int64_t capacity, void *ws, int64_t ws_bytes,
+                     int64_t *out_hist, double *out_scores, int64_t *out_keys, int32_t *out_votes,
+                     int64_t *out_count, void *stream);
+
 /* Link-sharded iteration (single sample over N ranks): each rank's context
  * holds 1/N of the train links (mmsbm_set_links) and the GLOBAL degree (mmsbm_set_degree).
  * Step 1, the accumulation half of make_iteration (:986-1012) over this rank's links:

@@ -49,7 +49,8 @@ def random_known(P, n, seed):
     return np.unique((t[:, 0] * P + t[:, 1]) * P + t[:, 2])
 
 
-ENTRY = {"census": "mmsbm_scan_census", "pair_census": "mmsbm_pair_census", "scan_above": "mmsbm_scan_above"}
+ENTRY = {"census": "mmsbm_scan_census", "pair_census": "mmsbm_pair_census", "scan_above": "mmsbm_scan_above",
+         "scan_votes": "mmsbm_scan_votes"}
 
 
 def resident(eng, known, sample):

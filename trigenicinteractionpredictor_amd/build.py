@@ -19,7 +19,8 @@ SRC_PARTNERS = os.path.join(PKG, "csrc", "partners.hip")   # per-gene partner sc
 SRC_CENSUS = os.path.join(PKG, "csrc", "census.hip")   # score census (mmsbm_census_*, mmsbm_scan_census)
 SRC_PAIR_CENSUS = os.path.join(PKG, "csrc", "pair_census.hip")   # pair census (mmsbm_pair_census_*)
 SRC_SCAN_ABOVE = os.path.join(PKG, "csrc", "scan_above.hip")   # threshold scan (mmsbm_scan_above_*)
-SRCS = [SRC, SRC_PAIRS, SRC_SCAN, SRC_PARTNERS, SRC_CENSUS, SRC_PAIR_CENSUS, SRC_SCAN_ABOVE]
+SRC_SCAN_VOTES = os.path.join(PKG, "csrc", "scan_votes.hip")   # vote scan (mmsbm_scan_votes_*)
+SRCS = [SRC, SRC_PAIRS, SRC_SCAN, SRC_PARTNERS, SRC_CENSUS, SRC_PAIR_CENSUS, SRC_SCAN_ABOVE, SRC_SCAN_VOTES]
 INCLUDE = os.path.join(REPO, "include")
 OUT_DIR = os.path.join(PKG, "_build")
 LIB = os.path.join(OUT_DIR, "libmmsbm.so")
@@ -41,6 +42,9 @@ DEPS = {
                       os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(PKG, "csrc", "scan_sweep.h"),
                       os.path.join(INCLUDE, "mmsbm.h")],
     SRC_SCAN_ABOVE: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
+                     os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(PKG, "csrc", "scan_sweep.h"),
+                     os.path.join(INCLUDE, "mmsbm.h")],
+    SRC_SCAN_VOTES: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
                      os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(PKG, "csrc", "scan_sweep.h"),
                      os.path.join(INCLUDE, "mmsbm.h")],
 }

@@ -113,6 +113,39 @@ struct Score {
     }
     return tot / div;
   }
+
+  // The vote scan (scan_votes.hip): which of a slot's four scores are at or above thr, one byte per
+  // element (byte i: element i), so that the bytes of up to 255 slots add without a carry between
+  // them (the W tile holds at most 85: 64 KiB / (16 rows of 6 doubles)).
+  static __device__ __forceinline__ unsigned votes_of(const d4v& acc, double thr) {
+    unsigned v = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v |= (unsigned)(acc[i] >= thr) << (8 * i);
+    return v;
+  }
+
+  // tile_mean that also votes: the same operands in the same order, each slot's accumulator compared
+  // with thr before it joins the slot-order sum (the accumulator is that slot's single-sample score,
+  // bit for bit: tile_one's chain over the same W row and Th' column).  votes: byte i = the slots
+  // with element i at or above thr.
+  static __device__ __forceinline__ d4v tile_votes(const double* W, const double* __restrict__ thT, int ns,
+                                                   int RB, int P16, int wb, int c0, int m, int kk, double div,
+                                                   double thr, unsigned& votes) {
+    d4v tot = {0.0, 0.0, 0.0, 0.0};
+    unsigned v = 0;
+    for (int s = 0; s < ns; ++s) {
+      const double* __restrict__ tc = thT + ((size_t)s * KP + kk) * P16 + c0 + m;
+      const double* wr = W + ((size_t)s * RB + wb * 16 + m) * WS + kk;
+      d4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[4 * ks], tc[(size_t)(4 * ks) * P16], acc, 0, 0, 0);
+      v += votes_of(acc, thr);
+      tot = s == 0 ? acc : tot + acc;  // samples added in slot order
+    }
+    votes = v;
+    return tot / div;
+  }
 };
 
 }  // namespace scan_score

@@ -1,7 +1,8 @@
-// scan_sweep.h — the triangle sweep shared by the score census (census.hip) and the pair census
-// (pair_census.hip): every eligible triple (the scan's: rank positions a < b < c < P, packed key not
-// among the known ones) with its score, handed to the kernel's consumer one 16 x 16 tile at a time.
-// Both kernels see their triples through sweep() and nothing else, so exactly the same triples are
+// scan_sweep.h — the triangle sweep shared by the score census (census.hip), the pair census
+// (pair_census.hip), the threshold scan (scan_above.hip) and the vote scan (scan_votes.hip): every
+// eligible triple (the scan's: rank positions a < b < c < P, packed key not among the known ones)
+// with its score, handed to the kernel's consumer one 16 x 16 tile at a time.
+// The kernels see their triples through sweep() and nothing else, so exactly the same triples are
 // hits in either: for every threshold the pair census's counts sum to three times the census's.
 //
 // The score phase is the scan's (scan_score.h), and so are the work items (a, a block of 16 WB rows
@@ -58,9 +59,15 @@ __device__ __forceinline__ void sweep_begin(Head* st) {
 // can hold a triple the wave then calls consume(ct, tot, el): the lane holds
 // S_a[b0 + kk + 4 i][16 ct + m] in tot[i] (m = lane & 15, kk = lane >> 4) and el[i] says whether
 // that triple is eligible.
-template <int KS, bool ENS, class BeginItem>
-__device__ __forceinline__ void sweep(const SweepArgs& A, Head* st, double* W, unsigned* bm,
-                                      BeginItem&& begin_item) {
+//
+// VOTES (sweep_votes, for scan_votes.hip): the score phase also compares every scored slot's own
+// tile with vthr (Score::tile_votes; a single sample: the one tile) and the consumer is called as
+// consume(ct, tot, votes, el), votes holding in byte i the number of slots whose element i is at or
+// above vthr, for eligible and other elements alike.  sweep() itself is the instantiation without
+// it, which holds nothing of the votes.
+template <int KS, bool ENS, bool VOTES, class BeginItem>
+__device__ __forceinline__ void sweep_impl(const SweepArgs& A, Head* st, double* W, unsigned* bm, double vthr,
+                                           BeginItem&& begin_item) {
   using namespace scan_select;
   using Sc = scan_score::Score<KS>;
   const int RB = 16 * A.WB;  // rows b of one item
@@ -110,7 +117,7 @@ __device__ __forceinline__ void sweep(const SweepArgs& A, Head* st, double* W, u
     if (!ENS && ct < nct) Sc::load_b(bnext, A.thT, P16, ct * 16, m, kk);
     auto consume = begin_item(a, b0);
     // Resolve a finished tile's eligibility and hand it over.
-    auto finish = [&](const d4v& tot, int ct) {
+    auto finish = [&](const d4v& tot, [[maybe_unused]] unsigned votes, int ct) {
       const int c0 = ct * 16, c = c0 + m;
       bool el[4];
       if (b0 > a && c0 > b0 + 15 && c0 + 16 <= P) {  // an interior tile: a < b < c < P everywhere
@@ -129,13 +136,17 @@ __device__ __forceinline__ void sweep(const SweepArgs& A, Head* st, double* W, u
           if (el[i]) el[i] = !is_known(A.known, klo, khi, key);
         }
       }
-      consume(ct, tot, el);
+      if constexpr (VOTES)  // a single sample votes with the tile itself: nothing to carry for a tile
+        consume(ct, tot, ENS ? votes : Sc::votes_of(tot, vthr), el);
+      else
+        consume(ct, tot, el);
     };
     // A tile is handed over after the next tile's MFMA chain has been issued, so the consumer's code
     // does not depend on the newest accumulator (measured on the census: 12 % off the B = 8
     // ensemble, nothing at B = 1).
     d4v prev = {0.0, 0.0, 0.0, 0.0};
     int prev_ct = -1;
+    [[maybe_unused]] unsigned votes = 0, prev_votes = 0;
     for (; ct < nct; ct += CW) {
       const int c0 = ct * 16;
       d4v tot;
@@ -145,15 +156,30 @@ __device__ __forceinline__ void sweep(const SweepArgs& A, Head* st, double* W, u
         for (int ks = 0; ks < KS; ++ks) bcur[ks] = bnext[ks];
         if (ct + CW < nct) Sc::load_b(bnext, A.thT, P16, c0 + 16 * CW, m, kk);
         tot = Sc::tile_one(areg, bcur);
+      } else if constexpr (VOTES) {
+        tot = Sc::tile_votes(W, A.thT, ns, RB, P16, wb, c0, m, kk, div, vthr, votes);
       } else {
         tot = Sc::tile_mean(W, A.thT, ns, RB, P16, wb, c0, m, kk, div);
       }
-      if (prev_ct >= 0) finish(prev, prev_ct);
+      if (prev_ct >= 0) finish(prev, prev_votes, prev_ct);
       prev = tot;
       prev_ct = ct;
+      if constexpr (VOTES && ENS) prev_votes = votes;
     }
-    if (prev_ct >= 0) finish(prev, prev_ct);
+    if (prev_ct >= 0) finish(prev, prev_votes, prev_ct);
   }
+}
+
+template <int KS, bool ENS, class BeginItem>
+__device__ __forceinline__ void sweep(const SweepArgs& A, Head* st, double* W, unsigned* bm,
+                                      BeginItem&& begin_item) {
+  sweep_impl<KS, ENS, false>(A, st, W, bm, 0.0, static_cast<BeginItem&&>(begin_item));
+}
+
+template <int KS, bool ENS, class BeginItem>
+__device__ __forceinline__ void sweep_votes(const SweepArgs& A, Head* st, double* W, unsigned* bm, double vthr,
+                                            BeginItem&& begin_item) {
+  sweep_impl<KS, ENS, true>(A, st, W, bm, vthr, static_cast<BeginItem&&>(begin_item));
 }
 
 }  // namespace scan_sweep

@@ -202,8 +202,8 @@ class EMEngine:
         return out[:, :n].cpu().numpy()
 
     # --------------------------------------------------------- scan families
-    # The scan, the partner scan, the census, the pair census and the threshold scan share what is
-    # below: one check of the sample, one rank order, one scratch tensor per family and one context
+    # The scan, the partner scan, the census, the pair census, the threshold scan and the vote scan
+    # share what is below: one check of the sample, one rank order, one scratch tensor per family and one context
     # that owns every tensor of a call.
     def _sample(self, sample) -> int:
         """A slot of the active prefix, or None (-1 in C) for the mean over it."""
@@ -224,8 +224,8 @@ class EMEngine:
         return self._scan_order
 
     def scan_workspace(self, family: str, *size_args) -> torch.Tensor:
-        """The scratch of one family ("scan", "partners", "census", "pair_census", "scan_above"),
-        grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device."""
+        """The scratch of one family ("scan", "partners", "census", "pair_census", "scan_above",
+        "scan_votes"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device."""
         nbytes = ctypes.c_int64()
         _lib.check(getattr(self.lib, "mmsbm_%s_workspace_bytes" % family)(self.ctx, *size_args,
                                                                           ctypes.byref(nbytes)))
@@ -435,6 +435,102 @@ class EMEngine:
         lo = bracket_threshold(n, float(scores[-1]), lambda t: self.census(t, known, sample)[0])
         scores, ids = self.scan_above(lo, known, sample, limit=limit)
         return scores[:n], ids[:n]
+
+    # ------------------------------------------------------------- vote scan
+    def _votes_call(self, call, threshold, min_votes, capacity):
+        """One mmsbm_scan_votes inside a _scan_call: -> device tensors (hist int64[ns + 1],
+        votes int32[capacity], scores f64[capacity], keys int64[capacity], count int64[1]); the rows
+        in arrival order.  capacity = 0: the histogram-only call, the row arrays NULL."""
+        head, s = call
+        ns = self.active if head[-1] < 0 else 1
+        ws = self.scan_workspace("scan_votes")
+        hist = torch.empty(ns + 1, dtype=torch.int64, device=self.device)
+        votes = torch.empty(capacity, dtype=torch.int32, device=self.device)
+        scores = torch.empty(capacity, dtype=torch.float64, device=self.device)
+        keys = torch.empty(capacity, dtype=torch.int64, device=self.device)
+        count = torch.empty(1, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.mmsbm_scan_votes(*head, threshold, int(min_votes), int(capacity), _ptr(ws), ws.numel(),
+                                             _ptr(hist), *(_ptr(t) if capacity else None for t in (scores, keys, votes)),
+                                             _ptr(count), s.cuda_stream))
+        return hist, votes, scores, keys, count
+
+    def _vote_args(self, threshold, min_votes, sample):
+        """-> (threshold as a float, min_votes as an int; None: every scored slot); ValueError on a
+        NaN or infinite threshold and on min_votes outside [1, the scored slots]."""
+        threshold = float(threshold)
+        if not np.isfinite(threshold):
+            raise ValueError("the threshold must be a finite number")
+        ns = self.active if sample is None else 1
+        min_votes = ns if min_votes is None else int(min_votes)
+        if not 1 <= min_votes <= ns:
+            raise ValueError("min_votes %d outside [1, %d], the scored slots" % (min_votes, ns))
+        return threshold, min_votes
+
+    def vote_census_async(self, threshold, known: np.ndarray = None, sample: int = None, stream=None):
+        """vote_census without the host copy: -> the device tensor hist int64[ns + 1].  Nothing
+        synchronises."""
+        threshold, _ = self._vote_args(threshold, None, sample)
+        with self._scan_call(known, sample, stream) as call:
+            return self._votes_call(call, threshold, 1, 0)[0]
+
+    def vote_census(self, threshold, known: np.ndarray = None, sample: int = None, stream=None):
+        """The vote histogram (include/mmsbm.h mmsbm_scan_votes): -> hist int64[ns + 1] on the host,
+        hist[v] = the eligible triples (those scan_top ranks: distinct genes, key not in `known`)
+        that exactly v of the scored slots score >= threshold.  The scored slots are the ns = active
+        slots for sample = None and that one slot (ns = 1) otherwise; a slot's score carries the bits
+        census(sample=slot) sees, so hist.sum() is the census's total and sum(v * hist[v]) the sum
+        of the slots' census counts at the threshold.  A NaN or infinite threshold raises
+        ValueError.  known, sample: as for scan_top."""
+        hist = self.vote_census_async(threshold, known, sample, stream)
+        if stream is not None:
+            stream.synchronize()
+        return hist.cpu().numpy()
+
+    def _consensus(self, threshold, min_votes, known, sample, stream, limit):
+        """-> (hist, votes int32[n], scores f64[n] and packed keys int64[n] on the device, sorted by
+        votes descending, then score descending, then key ascending; the list call's count int64[1]
+        on the device; the histogram's count n; the launch stream)."""
+        threshold, min_votes = self._vote_args(threshold, min_votes, sample)
+        with self._scan_call(known, sample, stream) as call:    # one upload of the keys for both calls
+            hist = self._votes_call(call, threshold, min_votes, 0)[0]
+            n = int(hist[min_votes:].sum().cpu())   # the same votes: exactly the rows the list call will find
+            if n > int(limit):
+                raise LimitError(n, int(limit))
+            _, votes, scores, keys, found = self._votes_call(call, threshold, min_votes, n)
+            # the rows arrive in any order; three stable sorts, the last key first
+            keys, at = torch.sort(keys, stable=True)
+            votes, scores = votes[at], scores[at]
+            scores, at = torch.sort(scores, descending=True, stable=True)
+            votes, keys = votes[at], keys[at]
+            votes, at = torch.sort(votes, descending=True, stable=True)
+            scores, keys = scores[at], keys[at]
+        return hist, votes, scores, keys, found, n, call[1]
+
+    def consensus_async(self, threshold, min_votes: int = None, known: np.ndarray = None, sample: int = None,
+                        stream=None, limit: int = 1 << 26):
+        """consensus without the host copy: -> device tensors (votes int32[n], scores f64[n],
+        ids int32[n][3]) on the launch stream.  The number of rows comes from a histogram-only call
+        first (one host read of one integer); a count above `limit` raises before the list call."""
+        _, votes, scores, keys, _, _, s = self._consensus(threshold, min_votes, known, sample, stream, limit)
+        with torch.cuda.stream(s):
+            return votes, scores, self._keys_to_ids(keys)
+
+    def consensus(self, threshold, min_votes: int = None, known: np.ndarray = None, sample: int = None,
+                  stream=None, limit: int = 1 << 26):
+        """Every eligible triple that at least min_votes of the scored slots score >= threshold
+        (include/mmsbm.h mmsbm_scan_votes; min_votes = None: all of them): -> (votes int32[n],
+        scores f64[n], ids int32[n][3] in key order) on the host, sorted by votes descending, then
+        score descending, then packed key ascending; n = vote_census(threshold)[min_votes:].sum().
+        A row's score is the ensemble score, scan_top's and scan_above's bits for the same `sample`.
+        A NaN or infinite threshold and min_votes outside [1, the scored slots] raise ValueError, as
+        does a count above `limit` (scan.LimitError, with the count and the limit): 20 bytes per row
+        on the device, twice that while sorting.  known, sample: as for scan_top."""
+        _, votes, scores, keys, found, n, s = self._consensus(threshold, min_votes, known, sample, stream, limit)
+        with torch.cuda.stream(s):
+            ids = self._keys_to_ids(keys).cpu().numpy()
+            votes, scores, found = votes.cpu().numpy(), scores.cpu().numpy(), int(found.cpu()[0])
+        assert found == n, "mmsbm_scan_votes found %d rows where its histogram counted %d" % (found, n)
+        return votes, scores, ids
 
     # ----------------------------------------------------------- pair census
     def _pair_census_rank(self, thresholds, known, sample, stream):

@@ -55,6 +55,20 @@ the census counts: the predicted trigenic network at a probability cut.
                            10,000,000) of them is refused, with the count, before anything is
                            written.
 
+One more comes from the vote scan (`EMEngine.vote_census` / `EMEngine.consensus`, mmsbm_scan_votes).
+Every table above reduces the -n restarts to one score per triple first; EM restarts settle in
+different optima, and a mean of 0.5 can be eight restarts at 0.5 or four at 0.95 and four at 0.05.
+    --consensus FILE       per eligible triple (under --exclude), its votes: in how many of the -n
+                           restarts its P(r = 1) is >= --consensus-threshold T (default 0.5, in
+                           (0, 1]).  The header comments give `# samples`, `# threshold` and one
+                           `# votes  v  count` line per v from -n down to 0: how many eligible triples
+                           have exactly v votes.  Then rank, votes, probability, ids, names rows for
+                           every triple with at least --min-votes M votes (in [1, -n]; default -n: the
+                           restarts agree), by votes descending, then probability (the ensemble
+                           mean, the main table's) descending, then key.  More than --consensus-limit
+                           ROWS (default 10,000,000) of them is refused, with the count, before
+                           anything is written.  Not with --best: one restart has nothing to vote on.
+
 Exactness: the counts are exact for the scan's score bits.  A listed triple's probability comes from
 the predict kernel, which sums in another order, so a triple within rounding distance (about 1e-12
 relative) of another triple's score may be placed on either side of it.  (Listed triples are
@@ -76,6 +90,8 @@ MAX_PAIR_CENSUS_M = 8    # mmsbm_pair_census_max_m(): the most thresholds one pa
 DEFAULT_PAIR_THRESHOLD = 0.5   # --pairs without --pair-threshold
 DEFAULT_NETWORK_THRESHOLD = 0.5    # --network without --network-threshold
 DEFAULT_NETWORK_LIMIT = 10000000   # --network without --network-limit: the most rows it writes
+DEFAULT_CONSENSUS_THRESHOLD = 0.5    # --consensus without --consensus-threshold
+DEFAULT_CONSENSUS_LIMIT = 10000000   # --consensus without --consensus-limit: the most rows it writes
 DEFAULT_THRESHOLDS = (0.99, 0.95, 0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3, 0.2, 0.1, 0.05, 0.02, 0.01, 0.005,
                       0.002, 0.001)   # --census without --thresholds
 
@@ -399,6 +415,10 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [--network=] <TSV file: every eligible triple at or above T, best first>
     [--network-threshold=] <T, a float in (0, 1]; default 0.5>
     [--network-limit=] <the most rows --network may write; default 10000000>
+    [--consensus=] <TSV file: votes across the restarts; every eligible triple with >= M votes>
+    [--consensus-threshold=] <T, a float in (0, 1]: a restart votes for a triple it scores >= T; default 0.5>
+    [--min-votes=] <M, an integer in [1, restarts]; default: all restarts>
+    [--consensus-limit=] <the most rows --consensus may write; default 10000000>
 """
 
 
@@ -410,14 +430,18 @@ def parse(argv):
                seed=None, genes=[], all_genes=False, census=None, thresholds=None, heldout_ranks=None,
                pairs=None, pair_threshold=DEFAULT_PAIR_THRESHOLD, gene_census=None)
     # --network adds its three keys (network, network_threshold, network_limit, the latter two with
-    # their defaults) only when one of its options is given: without them cfg is what it always was
+    # their defaults) only when one of its options is given: without them cfg is what it always was;
+    # --consensus does the same with its four (consensus, consensus_threshold, min_votes,
+    # consensus_limit)
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
                                                         "best", "out=", "gene=", "all-genes", "census=",
                                                         "thresholds=", "heldout-ranks=", "pairs=",
                                                         "pair-threshold=", "gene-census=", "network=",
-                                                        "network-threshold=", "network-limit="])
+                                                        "network-threshold=", "network-limit=", "consensus=",
+                                                        "consensus-threshold=", "min-votes=",
+                                                        "consensus-limit="])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -475,6 +499,24 @@ def parse(argv):
                     print("\n\nERROR: --network-limit should be an integer number of rows >= 1")
                     raise cli.ArgError()
                 cfg["network_limit"] = int(arg)
+            elif opt == "--consensus":
+                cfg["consensus"] = arg
+            elif opt == "--consensus-threshold":
+                try:
+                    cfg["consensus_threshold"] = parse_unit_threshold(arg, "consensus")
+                except ValueError:
+                    print("\n\nERROR: --consensus-threshold should be a number in (0, 1]")
+                    raise cli.ArgError()
+            elif opt == "--min-votes":
+                if not int(arg) >= 1:
+                    print("\n\nERROR: --min-votes should be an integer number in [1, restarts (-n)]")
+                    raise cli.ArgError()
+                cfg["min_votes"] = int(arg)
+            elif opt == "--consensus-limit":
+                if not int(arg) >= 1:
+                    print("\n\nERROR: --consensus-limit should be an integer number of rows >= 1")
+                    raise cli.ArgError()
+                cfg["consensus_limit"] = int(arg)
             elif opt == "--thresholds":
                 try:
                     cfg["thresholds"] = parse_thresholds(arg)
@@ -493,6 +535,17 @@ def parse(argv):
         cfg.setdefault("network", None)
         cfg.setdefault("network_threshold", DEFAULT_NETWORK_THRESHOLD)
         cfg.setdefault("network_limit", DEFAULT_NETWORK_LIMIT)
+    if any(key in cfg for key in ("consensus", "consensus_threshold", "min_votes", "consensus_limit")):
+        cfg.setdefault("consensus", None)
+        cfg.setdefault("consensus_threshold", DEFAULT_CONSENSUS_THRESHOLD)
+        cfg.setdefault("min_votes", cfg["samples"])     # every restart
+        cfg.setdefault("consensus_limit", DEFAULT_CONSENSUS_LIMIT)
+        if cfg["min_votes"] > cfg["samples"]:           # -n may come after --min-votes
+            print("\n\nERROR: --min-votes should be an integer number in [1, restarts (-n)]")
+            raise cli.ArgError()
+        if cfg["consensus"] and cfg["best"]:
+            print("\n\nERROR: --consensus counts votes across the restarts: it does not go with --best")
+            raise cli.ArgError()
     if cfg["genes"] and cfg["all_genes"]:
         print("\n\nERROR: --gene and --all-genes exclude each other")
         raise cli.ArgError()
@@ -559,13 +612,39 @@ def network_table(eng, model, cfg, known, sample, extras):
     extras["network"] = network_rows(model.id_gene, scores, ids)
 
 
+def consensus_rows(id_gene, votes, scores, ids):
+    """consensus's arrays -> rows [rank, votes, probability, "i_j_k", names]."""
+    return [[i + 1, int(v), float(p), "_".join(str(int(g)) for g in row), sorted(id_gene[int(g)] for g in row)]
+            for i, (v, p, row) in enumerate(zip(votes, scores, ids))]
+
+
+def consensus_table(eng, model, cfg, known, extras):
+    """The driver's --consensus table into `extras` (see run); cli.ArgError when it would hold more
+    rows than --consensus-limit."""
+    from . import cli
+    if not cfg.get("consensus"):
+        return
+    T, M = cfg["consensus_threshold"], cfg["min_votes"]
+    hist = eng.vote_census(T, known)
+    try:
+        votes, scores, ids = eng.consensus(T, M, known, limit=cfg["consensus_limit"])
+    except LimitError as e:
+        eng.close()
+        print("\n\nERROR: --consensus: %d triples have a probability of %r or more in at least %d restarts, above "
+              "--consensus-limit %d: raise --consensus-threshold or --min-votes (or the limit)"
+              % (e.count, T, M, e.limit))
+        raise cli.ArgError()
+    extras["consensus"] = (eng.active, T, [int(c) for c in hist], consensus_rows(model.id_gene, votes, scores, ids))
+
+
 def run(cfg, out=print, extras=None):
     """Fit the restarts as one batch, scan once, return the rows [rank, probability, ids, names]
     (with --gene / --all-genes: [query, rank, probability, ids, names], by query then rank).
     extras: a dict that receives "census" = (thresholds, counts, total) and "heldout_ranks" = rows
     when cfg asks for them (--census, --heldout-ranks), and "pairs" = rows [count, eligible, ids,
     names] and "gene_census" = (thresholds, names, counts int64[P][M]) for --pairs, --gene-census, and
-    "network" = rows [rank, probability, ids, names] for --network."""
+    "network" = rows [rank, probability, ids, names] for --network, and "consensus" = (restarts,
+    threshold, hist, rows [rank, votes, probability, ids, names]) for --consensus."""
     from .model import Model
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
@@ -587,6 +666,7 @@ def run(cfg, out=print, extras=None):
         census_tables(eng, model, cfg, known, sample, extras)
         pair_tables(eng, model, cfg, known, sample, extras)
         network_table(eng, model, cfg, known, sample, extras)
+        consensus_table(eng, model, cfg, known, extras)
     if queries is not None:
         out("partner pairs of %d genes: %s" % (len(queries), "sample %d" % sample if sample is not None
                                                else "mean of %d samples" % B))
@@ -618,6 +698,18 @@ def write_census_tsv(thresholds, counts, total, stream):
     stream.write("threshold\tcount\tfraction\n")
     for t, c in zip(thresholds, counts):
         stream.write("%r\t%d\t%r\n" % (float(t), int(c), (int(c) / total) if total else 0.0))
+
+
+def write_consensus_tsv(samples, threshold, hist, rows, stream):
+    """hist[v], v = 0..samples: the eligible triples with exactly v votes, written from the most
+    votes down."""
+    stream.write("# samples\t%d\n" % samples)
+    stream.write("# threshold\t%r\n" % float(threshold))
+    for v in range(len(hist) - 1, -1, -1):
+        stream.write("# votes\t%d\t%d\n" % (v, int(hist[v])))
+    stream.write("rank\tvotes\tprobability\tids\tnames\n")
+    for rank, votes, p, key, names in rows:
+        stream.write("%d\t%d\t%r\t%s\t%s\n" % (rank, votes, p, key, "_".join(names)))
 
 
 def write_pairs_tsv(rows, stream):
@@ -666,6 +758,9 @@ def main(argv=None, out=print):
     if "network" in extras:
         with open(cfg["network"], "w", encoding="utf-8") as f:
             write_tsv(extras["network"], f)
+    if "consensus" in extras:
+        with open(cfg["consensus"], "w", encoding="utf-8") as f:
+            write_consensus_tsv(*extras["consensus"], f)
     partners = bool(cfg["genes"] or cfg["all_genes"])
     if cfg["out"]:
         with open(cfg["out"], "w", encoding="utf-8") as f:
