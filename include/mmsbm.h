@@ -354,6 +354,46 @@ int mmsbm_scan_votes(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known,
                      int64_t *out_hist, double *out_scores, int64_t *out_keys, int32_t *out_votes,
                      int64_t *out_count, void *stream);
 
+/* Quorum scan: the exact top N of the scan's eligible triples ranked by their m-th best restart
+ * score, m = min_votes: the vote scan's consensus without a threshold chosen in advance.  order,
+ * known, n_known, theta, pr, sample, N, ws, stream, eligibility, the packed key and the total order
+ * (score descending; equal scores: smaller packed key first) are mmsbm_scan_topn's.
+ * The scored slots and a slot's own score are the vote scan's: the ns = active-prefix slots for
+ * sample = -1, that one slot (ns = 1) for sample >= 0; a slot's own score is the bits a single-sample
+ * call on that slot forms.  The quorum score q_m of a triple is the m-th largest of those ns values,
+ * 1 <= m <= ns: one of the slots' scores, bit for bit; no floating-point value is combined across
+ * slots.  votes >= m at threshold t exactly when q_m >= t, so mmsbm_scan_votes' hits at (t, m) are
+ * the triples with q_m >= t.  m = ns ranks by the minimum over the restarts, m = 1 by the maximum,
+ * m = ns / 2 + 1 by the majority score.  With ns = 1 the list is mmsbm_scan_topn's for that sample,
+ * bit for bit.
+ * Result (device), as for mmsbm_scan_topn with q_m in out_scores: the first *out_count rows of
+ * out_scores f64[N] and out_ids int32[N][3] hold the best triples under the total order;
+ * *out_count < N when fewer are eligible (P < 3: 0); the tail is NaN / -1.  The list is unique: it
+ * does not depend on the grid, the arrival order, the batch the slots sit in or the early exit below.
+ * The kernel keeps, per tile element, a sorted list of depth D = min(m, ns - m + 1) in registers (the
+ * D largest scores, or the D smallest when that list is no longer).  D <=
+ * mmsbm_scan_quorum_max_depth() (4: every m for ns <= 8; the four lowest and the four highest m for
+ * any ns); a deeper request is MMSBM_ERR_UNSUPPORTED.  Once more than ns - m slots of every element
+ * of a tile score below the pruning bound in force, the tile's remaining slots are not formed: the
+ * selection would have dropped every one of its elements.  The environment variable
+ * MMSBM_SCAN_QUORUM_EARLY=0 turns that exit off and MMSBM_SCAN_QUORUM_GRID=<workgroups> lowers the
+ * grid (measurement; the result depends on neither).
+ * Checked before any device call: a NULL ctx, order, theta, pr, out_scores, out_ids or out_count,
+ * N < 1, min_votes outside [1, ns], a bad sample, a bad known-key table or a missing, misaligned or
+ * small workspace: MMSBM_ERR_INVALID; K outside [1, MMSBM_MAX_K], N above mmsbm_scan_max_n(), P above
+ * 2 000 000, a depth above the cap or an ensemble whose W tile exceeds 64 KiB of LDS (the scan's
+ * rule): MMSBM_ERR_UNSUPPORTED.
+ * ws: mmsbm_scan_quorum_workspace_bytes(ctx, N) bytes of device scratch, 16-byte aligned, the
+ * caller's; its size follows the context's shape and N only.  theta and pr are only read; all
+ * launches go to `stream` and nothing synchronises.  Needs R >= 2.  Replaces nothing in the
+ * reference. */
+int mmsbm_scan_quorum_max_depth(void);
+int mmsbm_scan_quorum_workspace_bytes(const mmsbm_ctx *ctx, int32_t N, int64_t *bytes);
+int mmsbm_scan_quorum_topn(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known, int64_t n_known,
+                           const double *theta, const double *pr, int32_t sample, int32_t min_votes,
+                           int32_t N, void *ws, int64_t ws_bytes, double *out_scores,
+                           int32_t *out_ids, int64_t *out_count, void *stream);
+
 /* Link-sharded iteration (single sample over N ranks): each rank's context
  * holds 1/N of the train links (mmsbm_set_links) and the GLOBAL degree (mmsbm_set_degree).
  * Step 1, the accumulation half of make_iteration (:986-1012) over this rank's links:

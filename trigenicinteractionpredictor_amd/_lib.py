@@ -74,6 +74,10 @@ SIGNATURES = {
     "mmsbm_scan_votes_workspace_bytes": (_c_int, [_vp, ctypes.POINTER(_c_i64)]),
     "mmsbm_scan_votes": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_i32, _c_dbl, _c_i32, _c_i64, _vp, _c_i64, _vp,
                                   _vp, _vp, _vp, _vp, _vp]),
+    "mmsbm_scan_quorum_max_depth": (_c_int, []),
+    "mmsbm_scan_quorum_workspace_bytes": (_c_int, [_vp, _c_i32, ctypes.POINTER(_c_i64)]),
+    "mmsbm_scan_quorum_topn": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_i32, _c_i32, _c_i32, _vp, _c_i64, _vp,
+                                        _vp, _vp, _vp]),
     # include/mmsbm_pairs.h — the joint model's pair lattice
     "mmsbm_pairs_create": (_c_int, [_c_int, ctypes.POINTER(_vp)]),
     "mmsbm_pairs_destroy": (_c_int, [_vp]),

@@ -1,0 +1,418 @@
+// scan_quorum.hip — MI355X (gfx950) kernels + C ABI (include/mmsbm.h, mmsbm_scan_quorum_*) of the
+// quorum scan: the exact top N of q_m over the scan's eligible triples (rank positions a < b < c < P,
+// packed key not among the known ones), q_m = the m-th largest of the scored slots' (restarts') own
+// scores.  votes(t) >= m exactly when q_m >= t, so the list is the vote scan's consensus without a
+// threshold chosen in advance: m = ns ranks by what every restart agrees on (the minimum), m = 1 by
+// the maximum, m = ns / 2 + 1 by the majority score.
+//
+// The kernel is scan.hip's scan_kernel with another score phase: the same work items (a, a block of
+// 16 WB rows b) round-robin over the workgroups, the W rows of every slot in LDS, the same candidate
+// buffer (LDS when it fits, else workspace), wave_reserve / wg_keep_best, the published bound, the
+// seeding pass over every 61st item at P >= 200 and the fan-in-32 merge (scan_select.h, used as it
+// is; the merge kernel and the host loop are restated here, so that scan.hip's instantiations stay
+// the objects they were).  Only the tile differs (scan_score.h, Score<KS>::tile_quorum<D, SMALL>):
+// each slot's 16 x 16 tile is formed from zero with the single-sample MFMA chain, as tile_mean forms
+// it, and inserted into a per-element sorted list of depth D = min(m, ns - m + 1) in registers.  For
+// m < ns - m + 1 the list keeps the D = m largest and q_m is the smallest kept; otherwise it keeps
+// the D = ns - m + 1 smallest and q_m is the largest kept.  The direction is a template argument:
+// one "keep the D largest" body on sign-flipped values would halve the instantiations, but its flips
+// cost eight vector instructions per slot on a path that, with one workgroup per compute unit, is
+// bound by what a wave issues between two MFMA chains (measured: DESIGN.md), and the whole file
+// still compiles in seconds.  q_m is one of the slots' scores, bit for bit; nothing is combined
+// across slots.  q_m >= 0, so the integer atomic max of the published bound orders it as it orders
+// the scan's scores.
+//
+// Early exit.  With cut = max(the workgroup's N-th best, the published bound), as scan_kernel forms
+// it, a triple with q_m < cut is never appended.  q_m < cut exactly when more than ns - m slots score
+// strictly below cut.  tile_quorum reads that off its sorted list (no separate counter) and, once no
+// element of the wave's tile can still reach cut, leaves the slot loop: the remaining slots' MFMA
+// chains are not run.  The branch is wave-uniform (a ballot), equal scores stay in (the key decides
+// them later), and the exit drops only tiles whose every element the selection's first test would
+// have dropped, so the list is the same with MMSBM_SCAN_QUORUM_EARLY=0 (measurement), which turns
+// it off.
+//
+// A single slot (ns = 1: sample >= 0, or one active slot) takes scan_kernel's register-resident
+// single-sample path (load_a, load_b with the next tile's operand in flight, tile_one): its list is
+// mmsbm_scan_topn's for that sample, bit for bit.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "mmsbm.h"
+#include "scan_host.h"
+#include "scan_score.h"
+#include "scan_select.h"
+
+namespace {
+
+using namespace scan_host;
+using namespace scan_select;
+using scan_score::scan_prep_kernel;
+using scan_score::Score;
+using scan_score::W_LDS_MAX;
+
+constexpr int QUORUM_MAX_N = 4096;    // mmsbm_scan_max_n(): the scan's cap
+constexpr int QUORUM_MAX_DEPTH = 4;   // the deepest sorted list instantiated
+constexpr int SEED_STRIDE = 61;       // as scan.hip
+constexpr int SEED_MIN_P = 200;
+
+struct QuorumArgs {
+  const double* thT;          // [ns][KP][P16]
+  const double* T;            // [ns][P][K][KP]
+  const long long* known;     // sorted packed keys (null: none)
+  long long n_known;
+  double* cand_s;             // workspace candidate buffers [G][cap] (null: LDS)
+  long long* cand_k;
+  double* list_s;             // per-workgroup results [G][N]
+  long long* list_k;
+  int* list_n;                // [G]
+  unsigned long long* shared; // published threshold bits
+  int K, P, P16, ns, N, cap, WB;
+  int first;                  // the first slot after which a tile may be left: ns - min_votes; ns: never
+  int stride;                 // 1: every item; > 1: the seeding pass over every stride-th item
+};
+
+// D = 0: the single slot.  D >= 1: the ensemble with a sorted list of depth D, of the D smallest
+// scores (SMALL) or the D largest.
+template <int KS, int D, bool SMALL>
+__global__ __launch_bounds__(NT) void scan_quorum_kernel(QuorumArgs A) {
+  using Sc = Score<KS>;
+  constexpr int WS = Sc::WS;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  Sel* st = reinterpret_cast<Sel*>(smem);
+  double* W = reinterpret_cast<double*>(smem + sizeof(Sel));
+  const int RB = 16 * A.WB;
+  const int P = A.P, P16 = A.P16, K = A.K, ns = A.ns;
+  double* lcs = W + (size_t)ns * RB * WS;  // the candidate buffer when it is in LDS
+  long long* lck = reinterpret_cast<long long*>(lcs + A.cap);
+  double* cs = lcs;
+  long long* ck = lck;
+  if (A.cand_s) {
+    cs = A.cand_s + (size_t)blockIdx.x * A.cap;
+    ck = A.cand_k + (size_t)blockIdx.x * A.cap;
+  }
+  auto keep_best = [&]() {
+    if (A.cand_s) wg_keep_best(st, cs, ck, A.N, A.shared);
+    else wg_keep_best(st, lcs, lck, A.N, A.shared);
+  };
+  if (threadIdx.x == 0) sel_init(st);
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = lane & 15, kk = lane >> 4;
+  const int wb = wave % A.WB, wc = wave / A.WB, CW = 4 / A.WB;
+  const int nct = P16 / 16;
+  const int nbq = (P + RB - 1) / RB;
+  const long long PP = (long long)P;
+
+  for (long long q = (long long)blockIdx.x * A.stride; q < PP * nbq; q += (long long)gridDim.x * A.stride) {
+    const int a = (int)(q / nbq), bq = (int)(q % nbq);
+    if (a >= P - 2 || bq * RB + RB - 1 <= a || bq * RB >= P - 1) continue;  // no a < b < c here
+    __syncthreads();  // the previous item's W is read
+    if (threadIdx.x == 0) {
+      const unsigned long long g = __hip_atomic_load(A.shared, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      st->gthr = g ? __longlong_as_double((long long)g) : neg_inf();
+    }
+    if (threadIdx.x == 64 && A.n_known > 0) {  // the known keys whose first gene is a
+      st->klo = lower_bound(A.known, 0, A.n_known, (long long)a * PP * PP);
+      st->khi = lower_bound(A.known, st->klo, A.n_known, (long long)(a + 1) * PP * PP);
+    }
+    Sc::fill_w(W, A.T, A.thT, a, bq, RB, ns, K, P, P16);
+    __syncthreads();
+
+    const int btile = bq * A.WB + wb, b0 = btile * 16;
+    const bool wave_on = b0 < P - 1 && b0 + 15 > a;
+    double areg[KS];
+    if (D == 0 && wave_on) Sc::load_a(areg, W, wb, m, kk);
+    int ct = bq * A.WB + wc;
+    while (ct < btile) ct += CW;  // every c of those tiles is below every b
+    const long long klo = st->klo, khi = st->khi;
+    for (;;) {
+      // the thresholds change only when the workgroup sorts its buffer (behind a barrier)
+      const double thr_s = st->thr_s, gthr = st->gthr;
+      const long long thr_k = st->thr_k;
+      const double cut = fmax(thr_s, gthr);
+      if (wave_on) {
+        double bnext[KS];  // single slot: the next tile's Th' operand is in flight
+        if (D == 0 && ct < nct) Sc::load_b(bnext, A.thT, P16, ct * 16, m, kk);
+        for (; ct < nct; ct += CW) {
+          const int c0 = ct * 16;
+          d4v tot;
+          if constexpr (D == 0) {
+            double bcur[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) bcur[ks] = bnext[ks];
+            if (ct + CW < nct) Sc::load_b(bnext, A.thT, P16, c0 + 16 * CW, m, kk);
+            tot = Sc::tile_one(areg, bcur);
+          } else {
+            // false: no element can reach cut (left the slot loop early, wave-uniform)
+            if (!Sc::template tile_quorum<D, SMALL>(W, A.thT, ns, RB, P16, wb, c0, m, kk, cut, A.first, tot))
+              continue;
+          }
+          // lane holds q[b0 + kk + 4 i][c0 + m]; from here on scan_kernel's selection
+          if (!__ballot(tot[0] >= cut || tot[1] >= cut || tot[2] >= cut || tot[3] >= cut)) continue;
+          const int c = c0 + m;
+          bool pass[4];
+          long long key[4];
+          unsigned long long mk[4];
+          int n = 0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int b = b0 + kk + 4 * i;
+            key[i] = ((long long)a * PP + b) * PP + c;
+            pass[i] = a < b && b < c && c < P && !(tot[i] < gthr) && before(tot[i], key[i], thr_s, thr_k);
+            if (pass[i] && khi > klo) pass[i] = !is_known(A.known, klo, khi, key[i]);
+            mk[i] = __ballot(pass[i]);
+            n += __popcll(mk[i]);
+          }
+          if (!n) continue;
+          int pos = wave_reserve(st, n, A.cap);
+          if (pos < 0) break;  // the tile is redone after the workgroup made room
+          const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (pass[i]) {
+              const int at = pos + __popcll(mk[i] & below);
+              cs[at] = tot[i];
+              ck[at] = key[i];
+            }
+            pos += __popcll(mk[i]);
+          }
+        }
+      }
+      __syncthreads();
+      if (!st->overflow) break;
+      keep_best();
+    }
+  }
+  keep_best();
+  const int cnt = st->count;
+  for (int i = threadIdx.x; i < cnt; i += NT) {
+    A.list_s[(size_t)blockIdx.x * A.N + i] = cs[i];
+    A.list_k[(size_t)blockIdx.x * A.N + i] = ck[i];
+  }
+  if (threadIdx.x == 0) A.list_n[blockIdx.x] = cnt;
+}
+
+// ------------------------------------------------------------------------------------------
+// Merge, as scan.hip's scan_merge_kernel: workgroup w keeps the best N of lists [FAN w, FAN (w + 1));
+// the last level (one workgroup) writes the result: scores, gene ids in key order, count, NaN / -1
+// tail.
+// ------------------------------------------------------------------------------------------
+struct MergeArgs {
+  const double* in_s;
+  const long long* in_k;
+  const int* in_n;
+  int n_in;
+  double* out_s;      // next level's lists (null on the last level)
+  long long* out_k;
+  int* out_n;
+  const int* order;   // last level
+  double* scores;
+  int* ids;
+  long long* count;
+  unsigned long long* shared;  // last level of the seeding pass: publish the N-th score, no output
+  int N, cap, P;
+};
+
+__global__ __launch_bounds__(NT) void scan_quorum_merge_kernel(MergeArgs A) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  Sel* st = reinterpret_cast<Sel*>(smem);
+  double* cs = reinterpret_cast<double*>(smem + sizeof(Sel));
+  long long* ck = reinterpret_cast<long long*>(cs + A.cap);
+  if (threadIdx.x == 0) sel_init(st);
+  __syncthreads();
+  const int l0 = blockIdx.x * FAN, l1 = min(l0 + FAN, A.n_in);
+  wg_merge_lists(st, cs, ck, A.in_s, A.in_k, A.in_n, l0, l1, A.N, A.cap);
+  wg_keep_best(st, cs, ck, A.N, A.shared);  // seeding pass: publishes the subset's N-th score
+  if (A.shared) return;
+  const int cnt = st->count;
+  if (A.out_s) {
+    for (int i = threadIdx.x; i < cnt; i += NT) {
+      A.out_s[(size_t)blockIdx.x * A.N + i] = cs[i];
+      A.out_k[(size_t)blockIdx.x * A.N + i] = ck[i];
+    }
+    if (threadIdx.x == 0) A.out_n[blockIdx.x] = cnt;
+    return;
+  }
+  const long long PP = A.P;
+  for (int i = threadIdx.x; i < A.N; i += NT) {
+    if (i < cnt) {
+      const long long k = ck[i];
+      A.scores[i] = cs[i];
+      A.ids[3 * i] = A.order[k / (PP * PP)];
+      A.ids[3 * i + 1] = A.order[(k / PP) % PP];
+      A.ids[3 * i + 2] = A.order[k % PP];
+    } else {
+      A.scores[i] = __builtin_nan("");
+      A.ids[3 * i] = A.ids[3 * i + 1] = A.ids[3 * i + 2] = -1;
+    }
+  }
+  if (threadIdx.x == 0) *A.count = cnt;
+}
+
+// ------------------------------------------------------------------------------------------
+// Host side
+// ------------------------------------------------------------------------------------------
+struct QuorumPlan {
+  ScanShape sh;
+  int N, cap, G, G2;
+  size_t off_thT, off_T, off_cs, off_ck, off_ls[2], off_lk[2], off_ln[2], total;
+};
+
+// As scan.hip's plan: everything that sizes the workspace follows the context's shape and N only.
+int make_plan(const mmsbm_ctx* c, int N, QuorumPlan* p) {
+  ScanShape& sh = p->sh;
+  if (int rc = scan_shape(c, "the quorum scan", &sh)) return rc;
+  if (N < 1) return fail(MMSBM_ERR_INVALID, "N=%d < 1", N);
+  if (N > QUORUM_MAX_N)
+    return fail(MMSBM_ERR_UNSUPPORTED, "N=%d above the scan's cap of %d", N, QUORUM_MAX_N);
+  if (int rc = packed_keys_fit(sh)) return rc;
+  p->N = N;
+  p->cap = 512;
+  while (p->cap < 2 * N) p->cap <<= 1;
+  const long long per_cu = N <= 1024 ? 4 : N <= 2048 ? 2 : 1;
+  const long long items = std::max<long long>(1, (long long)sh.P * (sh.P16 / 16));
+  p->G = (int)std::min<long long>(per_cu * sh.ncu, items);
+  p->G2 = (p->G + FAN - 1) / FAN;
+  const size_t G = p->G, cap = p->cap;
+  size_t off = 256;  // [0, 256): the published threshold
+  score_workspace(sh, off, &p->off_thT, &p->off_T);
+  p->off_cs = off, off = align256(off + sizeof(double) * G * cap);
+  p->off_ck = off, off = align256(off + sizeof(long long) * G * cap);
+  const size_t nl[2] = {G, (size_t)p->G2};
+  for (int i = 0; i < 2; ++i) {
+    p->off_ls[i] = off, off = align256(off + sizeof(double) * nl[i] * N);
+    p->off_lk[i] = off, off = align256(off + sizeof(long long) * nl[i] * N);
+    p->off_ln[i] = off, off = align256(off + sizeof(int) * nl[i]);
+  }
+  p->total = off;
+  return MMSBM_OK;
+}
+
+// f(std::integral_constant<int, D>{}) for D in [0, QUORUM_MAX_DEPTH]
+template <class F>
+int dispatch_depth(int d, F&& f) {
+  switch (d) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmsbm_scan_quorum_max_depth(void) { return QUORUM_MAX_DEPTH; }
+
+int mmsbm_scan_quorum_workspace_bytes(const mmsbm_ctx* c, int32_t N, int64_t* bytes) {
+  if (!c || !bytes) return fail(MMSBM_ERR_INVALID, "null argument");
+  QuorumPlan p;
+  int rc = make_plan(c, N, &p);
+  if (rc) return rc;
+  *bytes = (int64_t)p.total;
+  return MMSBM_OK;
+}
+
+int mmsbm_scan_quorum_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
+                           const double* theta, const double* pr, int32_t sample, int32_t min_votes, int32_t N,
+                           void* ws, int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count,
+                           void* stream) {
+  if (!c) return fail(MMSBM_ERR_INVALID, "null context");
+  QuorumPlan p;
+  int rc = make_plan(c, N, &p);
+  if (rc) return rc;
+  if (!order || !theta || !pr || !out_scores || !out_ids || !out_count)
+    return fail(MMSBM_ERR_INVALID, "null pointer");
+  const ScanShape& sh = p.sh;
+  int ns, s0, WB;
+  size_t w_bytes;
+  if ((rc = check_call(sh, "the quorum scan", "mmsbm_scan_quorum_workspace_bytes", known, n_known, sample, ws,
+                       ws_bytes, p.total, &ns, &s0)))
+    return rc;
+  if (min_votes < 1 || min_votes > ns)
+    return fail(MMSBM_ERR_INVALID, "min_votes=%d outside [1, %d], the scored slots", min_votes, ns);
+  // the sorted list: the D smallest when that list is no longer than the D largest (its exit test is one compare)
+  const bool smallest = ns - min_votes + 1 <= min_votes;
+  const int depth = smallest ? ns - min_votes + 1 : min_votes;
+  if (depth > QUORUM_MAX_DEPTH)
+    return fail(MMSBM_ERR_UNSUPPORTED,
+                "min_votes=%d of %d slots needs a sorted list of depth %d, above the cap of %d "
+                "(mmsbm_scan_quorum_max_depth)",
+                min_votes, ns, depth, QUORUM_MAX_DEPTH);
+  if ((rc = pick_wb(sh, "the quorum scan", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
+  const size_t cand_bytes = (size_t)p.cap * 16;
+  const bool cand_lds = sizeof(Sel) + w_bytes + cand_bytes <= (size_t)LDS_MAX;
+  const int lds = (int)(sizeof(Sel) + w_bytes + (cand_lds ? cand_bytes : 0));
+  const int merge_lds = (int)(sizeof(Sel) + cand_bytes);
+  const bool early = env_override("MMSBM_SCAN_QUORUM_EARLY", 1) != 0;  // measurement
+  // measurement: fewer workgroups than planned (the lists and buffers are sized for p.G)
+  const long long g_env = env_override("MMSBM_SCAN_QUORUM_GRID", 0);
+  const int G = g_env >= 1 ? (int)std::min<long long>(g_env, p.G) : p.G;
+
+  DeviceGuard g(sh.device);
+  hipStream_t s = (hipStream_t)stream;
+  char* w = (char*)ws;
+  HIP_TRY(hipMemsetAsync(w, 0, 256, s));
+  int* ln[2] = {(int*)(w + p.off_ln[0]), (int*)(w + p.off_ln[1])};
+  double* ls[2] = {(double*)(w + p.off_ls[0]), (double*)(w + p.off_ls[1])};
+  long long* lk[2] = {(long long*)(w + p.off_lk[0]), (long long*)(w + p.off_lk[1])};
+  if (sh.P >= 3) {
+    scan_prep_kernel<<<dim3(sh.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
+                                                     (double*)(w + p.off_T), sh.K, sh.KP, sh.R, sh.P, sh.P16, s0);
+    HIP_TRY(hipGetLastError());
+  }
+  // Pass 0 (large P only) seeds the bound and pass 1 scans every item, as in mmsbm_scan_topn: the
+  // N-th best q_m of a subset is a lower bound of the whole's.  The bound only prunes.
+  for (int pass = sh.P >= SEED_MIN_P ? 0 : 1; pass < 2; ++pass) {
+    const bool seeding = pass == 0;
+    int n_lists = 0;
+    if (sh.P >= 3) {
+      QuorumArgs a{};
+      a.thT = (const double*)(w + p.off_thT);
+      a.T = (const double*)(w + p.off_T);
+      a.known = (const long long*)known;
+      a.n_known = n_known;
+      a.cand_s = cand_lds ? nullptr : (double*)(w + p.off_cs);
+      a.cand_k = cand_lds ? nullptr : (long long*)(w + p.off_ck);
+      a.list_s = ls[0];
+      a.list_k = lk[0];
+      a.list_n = ln[0];
+      a.shared = (unsigned long long*)w;
+      a.K = sh.K, a.P = sh.P, a.P16 = sh.P16, a.ns = ns, a.N = N, a.cap = p.cap, a.WB = WB;
+      a.first = early ? ns - min_votes : ns;
+      a.stride = seeding ? SEED_STRIDE : 1;
+      n_lists = seeding ? std::min(G, sh.ncu) : G;
+      rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
+        return dispatch_depth(ns > 1 ? depth : 0, [&](auto d) {
+          constexpr int KS = decltype(ks)::value, D = decltype(d)::value;
+          if (D > 0 && smallest) return launch_lds(scan_quorum_kernel<KS, D, D != 0>, n_lists, lds, s, a);
+          return launch_lds(scan_quorum_kernel<KS, D, false>, n_lists, lds, s, a);
+        });
+      });
+      if (rc) return rc;
+    }
+    int cur = 0;
+    for (;;) {
+      const bool last = n_lists <= FAN;
+      MergeArgs ma{};
+      ma.in_s = ls[cur], ma.in_k = lk[cur], ma.in_n = ln[cur], ma.n_in = n_lists;
+      if (!last) ma.out_s = ls[cur ^ 1], ma.out_k = lk[cur ^ 1], ma.out_n = ln[cur ^ 1];
+      ma.order = order, ma.scores = out_scores, ma.ids = out_ids, ma.count = (long long*)out_count;
+      ma.shared = (seeding && last) ? (unsigned long long*)w : nullptr;
+      ma.N = N, ma.cap = p.cap, ma.P = std::max(sh.P, 1);
+      const int n_out = last ? 1 : (n_lists + FAN - 1) / FAN;
+      if ((rc = launch_lds(scan_quorum_merge_kernel, n_out, merge_lds, s, ma))) return rc;
+      if (last) break;
+      n_lists = n_out;
+      cur ^= 1;
+    }
+  }
+  return MMSBM_OK;
+}
+
+}  // extern "C"

@@ -146,6 +146,68 @@ struct Score {
     votes = v;
     return tot / div;
   }
+
+  // The quorum scan (scan_quorum.hip): the m-th largest of the slots' own scores, per element.  The
+  // same operands in the same order as tile_mean, each slot's accumulator formed from zero (that
+  // slot's single-sample score, bit for bit) and inserted into a per-element sorted list of depth D
+  // by D max / min pairs with compile-time indices (the list stays in registers).  SMALL = false: the
+  // list keeps the D = m largest, descending, and q is the smallest kept.  SMALL = true: it keeps
+  // the D = ns - m + 1 smallest, ascending, and q is the largest kept: the m-th largest again.  The
+  // caller picks the shorter list; no floating-point value is combined across slots.
+  // Early exit.  A triple with q_m < cut is pruned by the selection, and q_m < cut exactly when more
+  // than ns - m slots score strictly below cut.  The list already says so: with SMALL its last
+  // entry, the (ns - m + 1)-th smallest so far, is below cut exactly then; without, the entries at
+  // or above cut plus the slots still to come fall short of m exactly then.  From slot `first` on
+  // (the first after which that can hold: ns - m, 0-based; ns or more: never) and before the last
+  // slot (after which nothing is saved) one ballot asks whether any element of the wave's tile can
+  // still reach cut; if none can, the remaining slots are not formed and the function returns false
+  // (wave-uniform).  Equal scores stay in.
+  template <int D, bool SMALL>
+  static __device__ __forceinline__ bool tile_quorum(const double* W, const double* __restrict__ thT, int ns,
+                                                     int RB, int P16, int wb, int c0, int m, int kk, double cut,
+                                                     int first, d4v& q) {
+    const double start = SMALL ? __builtin_huge_val() : -__builtin_huge_val();
+    d4v L[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) L[j] = d4v{start, start, start, start};
+    for (int s = 0; s < ns; ++s) {
+      const double* __restrict__ tc = thT + ((size_t)s * KP + kk) * P16 + c0 + m;
+      const double* wr = W + ((size_t)s * RB + wb * 16 + m) * WS + kk;
+      d4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[4 * ks], tc[(size_t)(4 * ks) * P16], acc, 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        double x = acc[i];
+#pragma unroll
+        for (int j = 0; j < D; ++j) {  // L[j] keeps the better of the two, x carries the other on
+          const double lo = fmin(L[j][i], x), hi = fmax(L[j][i], x);
+          L[j][i] = SMALL ? lo : hi;
+          x = SMALL ? hi : lo;
+        }
+      }
+      if (s >= first && s + 1 < ns) {  // wave-uniform
+        bool alive = false;
+        if (SMALL) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) alive |= !(L[D - 1][i] < cut);  // +inf until D slots are in
+        } else {
+          const int need = D - (ns - 1 - s);  // >= 1 from slot ns - D on
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            int n = 0;
+#pragma unroll
+            for (int j = 0; j < D; ++j) n += L[j][i] >= cut;
+            alive |= n >= need;
+          }
+        }
+        if (!__ballot(alive)) return false;
+      }
+    }
+    q = L[D - 1];
+    return true;
+  }
 };
 
 }  // namespace scan_score

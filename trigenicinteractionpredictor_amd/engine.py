@@ -225,7 +225,7 @@ class EMEngine:
 
     def scan_workspace(self, family: str, *size_args) -> torch.Tensor:
         """The scratch of one family ("scan", "partners", "census", "pair_census", "scan_above",
-        "scan_votes"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device."""
+        "scan_votes", "scan_quorum"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device."""
         nbytes = ctypes.c_int64()
         _lib.check(getattr(self.lib, "mmsbm_%s_workspace_bytes" % family)(self.ctx, *size_args,
                                                                           ctypes.byref(nbytes)))
@@ -531,6 +531,54 @@ class EMEngine:
             votes, scores, found = votes.cpu().numpy(), scores.cpu().numpy(), int(found.cpu()[0])
         assert found == n, "mmsbm_scan_votes found %d rows where its histogram counted %d" % (found, n)
         return votes, scores, ids
+
+    # ----------------------------------------------------------- quorum scan
+    @property
+    def quorum_max_depth(self) -> int:
+        """mmsbm_scan_quorum_max_depth(): the deepest per-element sorted list the kernel holds."""
+        return int(self.lib.mmsbm_scan_quorum_max_depth())
+
+    def quorum_depth(self, min_votes: int = None, sample: int = None) -> int:
+        """The sorted-list depth quorum_top(., min_votes, sample=sample) needs: min(m, ns - m + 1)
+        for m = min_votes (None: every scored slot) of the ns scored slots; quorum_top takes it up to
+        quorum_max_depth.  ValueError for min_votes outside [1, ns]."""
+        ns = self.active if sample is None else 1
+        m = ns if min_votes is None else int(min_votes)
+        if not 1 <= m <= ns:
+            raise ValueError("min_votes %d outside [1, %d], the scored slots" % (m, ns))
+        return min(m, ns - m + 1)
+
+    def quorum_top_async(self, n: int, min_votes: int = None, known: np.ndarray = None, sample: int = None,
+                         stream=None):
+        """quorum_top without the host copy: -> device tensors (scores f64[n], ids int32[n][3],
+        count int64[1]); rows from `count` on are NaN / -1.  Nothing synchronises."""
+        n = int(n)
+        self.quorum_depth(min_votes, sample)    # ValueError before anything is uploaded
+        m = (self.active if sample is None else 1) if min_votes is None else int(min_votes)
+        with self._scan_call(known, sample, stream) as (head, s):
+            ws = self.scan_workspace("scan_quorum", n)
+            scores = torch.empty(n, dtype=torch.float64, device=self.device)
+            ids = torch.empty((n, 3), dtype=torch.int32, device=self.device)
+            count = torch.empty(1, dtype=torch.int64, device=self.device)
+            _lib.check(self.lib.mmsbm_scan_quorum_topn(*head, m, n, _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids),
+                                                       _ptr(count), s.cuda_stream))
+        return scores, ids, count
+
+    def quorum_top(self, n: int, min_votes: int = None, known: np.ndarray = None, sample: int = None, stream=None):
+        """The n eligible triples with the highest quorum score (include/mmsbm.h
+        mmsbm_scan_quorum_topn): q_m = the m-th largest of the scored slots' own scores, m = min_votes
+        (None: every scored slot, the minimum over them; 1: the maximum).  -> (scores f64[n'],
+        ids int32[n'][3] in key order) on the host, best first under scan_top's total order, n' <= n.
+        A triple has at least m votes at threshold t (vote_census, consensus) exactly when its
+        q_m >= t.  The scored slots are the active slots for sample = None and that one slot
+        otherwise, where the list is scan_top's for that sample, bit for bit.  min_votes outside
+        [1, the scored slots] raises ValueError; a quorum_depth above quorum_max_depth raises
+        MMSBMError (MMSBM_ERR_UNSUPPORTED).  known, sample: as for scan_top."""
+        scores, ids, count = self.quorum_top_async(n, min_votes, known, sample, stream)
+        if stream is not None:
+            stream.synchronize()
+        m = int(count.cpu()[0])
+        return scores[:m].cpu().numpy(), ids[:m].cpu().numpy()
 
     # ----------------------------------------------------------- pair census
     def _pair_census_rank(self, thresholds, known, sample, stream):

@@ -69,6 +69,21 @@ different optima, and a mean of 0.5 can be eight restarts at 0.5 or four at 0.95
                            ROWS (default 10,000,000) of them is refused, with the count, before
                            anything is written.  Not with --best: one restart has nothing to vote on.
 
+One more comes from the quorum scan (`EMEngine.quorum_top`, mmsbm_scan_quorum_topn): the consensus
+without a threshold chosen in advance.
+    --quorum FILE          the --top eligible triples (under --exclude) ranked by their quorum score:
+                           the M-th largest of the -n restarts' own P(r = 1), --quorum-votes M (in
+                           [1, -n]; default -n: the minimum over the restarts, what all of them agree
+                           on; 1: the maximum; -n / 2 + 1: the majority score).  A triple has at least
+                           M votes at a threshold T (--consensus) exactly when its quorum score is
+                           >= T.  The header comments give `# samples` and `# quorum votes`; then
+                           rank, quorum, mean, min, max, ids, names rows, best first, equal quorum
+                           scores by key.  mean, min and max are the listed triple's ensemble mean and
+                           its lowest and highest restart score, from the predict kernel.  The kernel
+                           keeps min(M, -n - M + 1) scores per triple, at most MAX_QUORUM_DEPTH = 4:
+                           every M up to -n 8, the four lowest and the four highest M beyond.  Not
+                           with --best: one restart has no quorum.
+
 Exactness: the counts are exact for the scan's score bits.  A listed triple's probability comes from
 the predict kernel, which sums in another order, so a triple within rounding distance (about 1e-12
 relative) of another triple's score may be placed on either side of it.  (Listed triples are
@@ -92,6 +107,7 @@ DEFAULT_NETWORK_THRESHOLD = 0.5    # --network without --network-threshold
 DEFAULT_NETWORK_LIMIT = 10000000   # --network without --network-limit: the most rows it writes
 DEFAULT_CONSENSUS_THRESHOLD = 0.5    # --consensus without --consensus-threshold
 DEFAULT_CONSENSUS_LIMIT = 10000000   # --consensus without --consensus-limit: the most rows it writes
+MAX_QUORUM_DEPTH = 4     # mmsbm_scan_quorum_max_depth(): the deepest sorted list of the quorum scan
 DEFAULT_THRESHOLDS = (0.99, 0.95, 0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3, 0.2, 0.1, 0.05, 0.02, 0.01, 0.005,
                       0.002, 0.001)   # --census without --thresholds
 
@@ -419,6 +435,8 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [--consensus-threshold=] <T, a float in (0, 1]: a restart votes for a triple it scores >= T; default 0.5>
     [--min-votes=] <M, an integer in [1, restarts]; default: all restarts>
     [--consensus-limit=] <the most rows --consensus may write; default 10000000>
+    [--quorum=] <TSV file: the --top eligible triples by their M-th best restart score>
+    [--quorum-votes=] <M, an integer in [1, restarts]; default: all restarts (the minimum over them)>
 """
 
 
@@ -432,7 +450,7 @@ def parse(argv):
     # --network adds its three keys (network, network_threshold, network_limit, the latter two with
     # their defaults) only when one of its options is given: without them cfg is what it always was;
     # --consensus does the same with its four (consensus, consensus_threshold, min_votes,
-    # consensus_limit)
+    # consensus_limit) and --quorum with its two (quorum, quorum_votes)
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
@@ -441,7 +459,7 @@ def parse(argv):
                                                         "pair-threshold=", "gene-census=", "network=",
                                                         "network-threshold=", "network-limit=", "consensus=",
                                                         "consensus-threshold=", "min-votes=",
-                                                        "consensus-limit="])
+                                                        "consensus-limit=", "quorum=", "quorum-votes="])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -517,6 +535,13 @@ def parse(argv):
                     print("\n\nERROR: --consensus-limit should be an integer number of rows >= 1")
                     raise cli.ArgError()
                 cfg["consensus_limit"] = int(arg)
+            elif opt == "--quorum":
+                cfg["quorum"] = arg
+            elif opt == "--quorum-votes":
+                if not int(arg) >= 1:
+                    print("\n\nERROR: --quorum-votes should be an integer number in [1, restarts (-n)]")
+                    raise cli.ArgError()
+                cfg["quorum_votes"] = int(arg)
             elif opt == "--thresholds":
                 try:
                     cfg["thresholds"] = parse_thresholds(arg)
@@ -545,6 +570,19 @@ def parse(argv):
             raise cli.ArgError()
         if cfg["consensus"] and cfg["best"]:
             print("\n\nERROR: --consensus counts votes across the restarts: it does not go with --best")
+            raise cli.ArgError()
+    if any(key in cfg for key in ("quorum", "quorum_votes")):
+        cfg.setdefault("quorum", None)
+        cfg.setdefault("quorum_votes", cfg["samples"])      # every restart
+        if cfg["quorum_votes"] > cfg["samples"]:            # -n may come after --quorum-votes
+            print("\n\nERROR: --quorum-votes should be an integer number in [1, restarts (-n)]")
+            raise cli.ArgError()
+        if quorum_depth(cfg["quorum_votes"], cfg["samples"]) > MAX_QUORUM_DEPTH:
+            print("\n\nERROR: --quorum-votes %d of %d restarts: only the %d lowest and the %d highest values are "
+                  "supported" % (cfg["quorum_votes"], cfg["samples"], MAX_QUORUM_DEPTH, MAX_QUORUM_DEPTH))
+            raise cli.ArgError()
+        if cfg["quorum"] and cfg["best"]:
+            print("\n\nERROR: --quorum ranks by a score across the restarts: it does not go with --best")
             raise cli.ArgError()
     if cfg["genes"] and cfg["all_genes"]:
         print("\n\nERROR: --gene and --all-genes exclude each other")
@@ -637,6 +675,36 @@ def consensus_table(eng, model, cfg, known, extras):
     extras["consensus"] = (eng.active, T, [int(c) for c in hist], consensus_rows(model.id_gene, votes, scores, ids))
 
 
+def quorum_depth(votes: int, samples: int) -> int:
+    """The scores the quorum scan keeps per triple for the votes-th largest of `samples`
+    (EMEngine.quorum_depth): the shorter of the list from the top and the list from the bottom."""
+    return min(int(votes), int(samples) - int(votes) + 1)
+
+
+def quorum_rows(id_gene, scores, ids, probs):
+    """quorum_top's arrays and predict's probs f64[samples][n] on those ids -> rows [rank, quorum
+    score, mean, min, max, "i_j_k", names]; the mean is added in slot order."""
+    if not len(scores):
+        return []
+    probs = np.asarray(probs, dtype=np.float64).reshape(-1, len(scores))
+    mean = probs[0]
+    for b in range(1, probs.shape[0]):
+        mean = mean + probs[b]
+    mean = mean / probs.shape[0]
+    lo, hi = probs.min(axis=0), probs.max(axis=0)
+    return [[i + 1, float(q), float(mean[i]), float(lo[i]), float(hi[i]), "_".join(str(int(g)) for g in row),
+             sorted(id_gene[int(g)] for g in row)] for i, (q, row) in enumerate(zip(scores, ids))]
+
+
+def quorum_table(eng, model, cfg, known, extras):
+    """The driver's --quorum table into `extras` (see run)."""
+    if not cfg.get("quorum"):
+        return
+    scores, ids = eng.quorum_top(cfg["top"], cfg["quorum_votes"], known)
+    probs = eng.predict(ids)[:eng.active] if len(scores) else np.zeros((eng.active, 0))
+    extras["quorum"] = (eng.active, cfg["quorum_votes"], quorum_rows(model.id_gene, scores, ids, probs))
+
+
 def run(cfg, out=print, extras=None):
     """Fit the restarts as one batch, scan once, return the rows [rank, probability, ids, names]
     (with --gene / --all-genes: [query, rank, probability, ids, names], by query then rank).
@@ -644,7 +712,8 @@ def run(cfg, out=print, extras=None):
     when cfg asks for them (--census, --heldout-ranks), and "pairs" = rows [count, eligible, ids,
     names] and "gene_census" = (thresholds, names, counts int64[P][M]) for --pairs, --gene-census, and
     "network" = rows [rank, probability, ids, names] for --network, and "consensus" = (restarts,
-    threshold, hist, rows [rank, votes, probability, ids, names]) for --consensus."""
+    threshold, hist, rows [rank, votes, probability, ids, names]) for --consensus, and "quorum" =
+    (restarts, votes, rows [rank, quorum score, mean, min, max, ids, names]) for --quorum."""
     from .model import Model
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
@@ -667,6 +736,7 @@ def run(cfg, out=print, extras=None):
         pair_tables(eng, model, cfg, known, sample, extras)
         network_table(eng, model, cfg, known, sample, extras)
         consensus_table(eng, model, cfg, known, extras)
+        quorum_table(eng, model, cfg, known, extras)
     if queries is not None:
         out("partner pairs of %d genes: %s" % (len(queries), "sample %d" % sample if sample is not None
                                                else "mean of %d samples" % B))
@@ -710,6 +780,14 @@ def write_consensus_tsv(samples, threshold, hist, rows, stream):
     stream.write("rank\tvotes\tprobability\tids\tnames\n")
     for rank, votes, p, key, names in rows:
         stream.write("%d\t%d\t%r\t%s\t%s\n" % (rank, votes, p, key, "_".join(names)))
+
+
+def write_quorum_tsv(samples, votes, rows, stream):
+    stream.write("# samples\t%d\n" % samples)
+    stream.write("# quorum votes\t%d\n" % votes)
+    stream.write("rank\tquorum\tmean\tmin\tmax\tids\tnames\n")
+    for rank, q, mean, lo, hi, key, names in rows:
+        stream.write("%d\t%r\t%r\t%r\t%r\t%s\t%s\n" % (rank, q, mean, lo, hi, key, "_".join(names)))
 
 
 def write_pairs_tsv(rows, stream):
@@ -761,6 +839,9 @@ def main(argv=None, out=print):
     if "consensus" in extras:
         with open(cfg["consensus"], "w", encoding="utf-8") as f:
             write_consensus_tsv(*extras["consensus"], f)
+    if "quorum" in extras:
+        with open(cfg["quorum"], "w", encoding="utf-8") as f:
+            write_quorum_tsv(*extras["quorum"], f)
     partners = bool(cfg["genes"] or cfg["all_genes"])
     if cfg["out"]:
         with open(cfg["out"], "w", encoding="utf-8") as f:
