@@ -304,6 +304,39 @@ int mmsbm_scan_above(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known,
                      int64_t capacity, void *ws, int64_t ws_bytes, double *out_scores,
                      int64_t *out_keys, int64_t *out_count, void *stream);
 
+/* Pair-masked census and threshold scan: the two calls above with one more rule of eligibility, a
+ * predicate on PAIRS of genes.  A key table cannot carry such a rule (a blocked pair is P - 2 keys);
+ * a bit matrix can, and lets the sweep drop whole work items and tiles before any MFMA is issued.
+ * mask: device uint32[P16][MW] in RANK POSITIONS (those of `order`), P16 = P rounded up to 16 (at
+ * least 16) and MW = ceil(P16 / 32), as mmsbm_pair_mask_shape returns them (rows, words_per_row).
+ * Bit y & 31 of mask[x][y >> 5] set means the pair of rank positions (x, y) is blocked.  Only x < y
+ * is ever read: the lower triangle, the diagonal, rows >= P and bits >= P are ignored (the rows exist
+ * so that no kernel needs a row guard).  A triple a < b < c is eligible when it is eligible for the
+ * unmasked call and none of (a, b), (a, c), (b, c) is blocked.  The mask is the caller's and is only
+ * read.
+ * Everything else is the unmasked call's: the arguments, the results (out_counts[M] = the number of
+ * masked-eligible triples; the threshold scan's always-full count, its arrival-order rows, no address
+ * at or past row `capacity` formed), integer-only combination across lanes, the error codes, the
+ * workspaces (mmsbm_census_workspace_bytes, mmsbm_scan_above_workspace_bytes) and the grid variables
+ * (MMSBM_CENSUS_GRID, MMSBM_SCAN_ABOVE_GRID).  The score phase is not touched: a score carries the
+ * bits the unmasked families give that triple, so a masked call with an all-zero mask returns what
+ * the unmasked call returns, and a masked call returns what the unmasked call returns with the keys
+ * of every triple that contains a blocked pair added to `known`.
+ * P <= 16384 (the pair census's cap: a row of bits is at most 2 KiB of LDS, the mask 32 MiB); above
+ * it the three calls return MMSBM_ERR_UNSUPPORTED.  A NULL mask is MMSBM_ERR_INVALID: the unmasked
+ * call exists for that.  All checks come before any device call.  Replaces nothing in the
+ * reference. */
+int mmsbm_pair_mask_shape(const mmsbm_ctx *ctx, int32_t *rows, int32_t *words_per_row);
+int mmsbm_scan_census_masked(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known,
+                             int64_t n_known, const uint32_t *mask, const double *theta,
+                             const double *pr, int32_t sample, const double *thresholds, int32_t M,
+                             void *ws, int64_t ws_bytes, int64_t *out_counts, void *stream);
+int mmsbm_scan_above_masked(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known,
+                            int64_t n_known, const uint32_t *mask, const double *theta,
+                            const double *pr, int32_t sample, double threshold, int64_t capacity,
+                            void *ws, int64_t ws_bytes, double *out_scores, int64_t *out_keys,
+                            int64_t *out_count, void *stream);
+
 /* Vote scan: for every one of the scan's eligible triples, in how many of the scored slots (EM
  * restarts) its score is at or above one threshold; counted and listed.  A mean of 0.5 can be eight
  * restarts at 0.5 or four at 0.95 and four at 0.05: every other family reduces the batch to one score

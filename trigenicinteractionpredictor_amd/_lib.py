@@ -71,6 +71,11 @@ SIGNATURES = {
     "mmsbm_scan_above_workspace_bytes": (_c_int, [_vp, ctypes.POINTER(_c_i64)]),
     "mmsbm_scan_above": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_i32, _c_dbl, _c_i64, _vp, _c_i64, _vp, _vp,
                                   _vp, _vp]),
+    "mmsbm_pair_mask_shape": (_c_int, [_vp, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i32)]),
+    "mmsbm_scan_census_masked": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i32, _vp, _c_i32, _vp, _c_i64, _vp,
+                                          _vp]),
+    "mmsbm_scan_above_masked": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i32, _c_dbl, _c_i64, _vp, _c_i64,
+                                         _vp, _vp, _vp, _vp]),
     "mmsbm_scan_votes_workspace_bytes": (_c_int, [_vp, ctypes.POINTER(_c_i64)]),
     "mmsbm_scan_votes": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_i32, _c_dbl, _c_i32, _c_i64, _vp, _c_i64, _vp,
                                   _vp, _vp, _vp, _vp, _vp]),

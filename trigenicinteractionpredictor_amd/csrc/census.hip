@@ -53,14 +53,22 @@ struct CensusArgs : SweepArgs {
   int M;
 };
 
+// The masked census (mmsbm_scan_census_masked): the pair mask travels in the masked kernels' own
+// argument struct, so CensusArgs and the unmasked kernels are what they were.
+struct CensusMaskedArgs : CensusArgs {
+  const unsigned* mask;  // [P16][MW] (include/mmsbm.h, mmsbm_pair_mask_shape)
+  int MW;
+};
+
 // At most 4 waves per SIMD, which is what the grid is sized for (sweep_grid): aiming at a fifth, the
 // compiler issues the ensemble's operand loads one at a time (measured: 6.51 ms against 5.68 ms at
 // P = 1500, K = 10, B = 8).  The cap and sweep_grid's 4 workgroups per compute unit change together:
 // a larger default grid could not be resident under this cap, and no instantiation may take a fifth
 // wave however few registers it needs.  With a grid set through MMSBM_CENSUS_GRID the cap has not
 // been measured.
-template <int KS, bool ENS>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 4))) void census_kernel(CensusArgs A) {
+// The body of both kernels; MASK: Args is CensusMaskedArgs and row a of the mask lies behind the bitmap.
+template <int KS, bool ENS, bool MASK, class Args>
+__device__ __forceinline__ void census_body(const Args& A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Head* st = reinterpret_cast<Head*>(smem);
   double* W = reinterpret_cast<double*>(smem + sizeof(Head));
@@ -106,13 +114,27 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 4))) void
       }
     }
   };
-  sweep<KS, ENS>(A, st, W, bm, [&](int, int) { return count_tile; });
+  if constexpr (MASK)
+    sweep_masked<KS, ENS>(A, st, W, bm, A.mask, A.MW, bm + BM_WORDS, [&](int, int) { return count_tile; });
+  else
+    sweep<KS, ENS>(A, st, W, bm, [&](int, int) { return count_tile; });
   if (below) atomicAdd(&cnt[0], below);
   __syncthreads();
   for (int i = threadIdx.x; i <= M; i += NT) {
     const count_t v = cnt[i];
     if (v) __hip_atomic_fetch_add(&A.bins[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+template <int KS, bool ENS>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 4))) void census_kernel(CensusArgs A) {
+  census_body<KS, ENS, false>(A);
+}
+
+template <int KS, bool ENS>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 4))) void census_masked_kernel(
+    CensusMaskedArgs A) {
+  census_body<KS, ENS, true>(A);
 }
 
 // out[m] = sum of bins[m + 1 .. M] for m < M (the eligible scores at or above thresholds[m]);
@@ -154,24 +176,10 @@ int make_plan(const mmsbm_ctx* c, int M, CensusPlan* p) {
   return MMSBM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mmsbm_census_max_m(void) { return CENSUS_MAX_M; }
-
-int mmsbm_census_workspace_bytes(const mmsbm_ctx* c, int32_t M, int64_t* bytes) {
-  if (!c || !bytes) return fail(MMSBM_ERR_INVALID, "null argument");
-  CensusPlan p;
-  int rc = make_plan(c, M, &p);
-  if (rc) return rc;
-  *bytes = (int64_t)p.total;
-  return MMSBM_OK;
-}
-
-int mmsbm_scan_census(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
-                      const double* theta, const double* pr, int32_t sample, const double* thresholds,
-                      int32_t M, void* ws, int64_t ws_bytes, int64_t* out_counts, void* stream) {
+// Both entry points; `masked`: mmsbm_scan_census_masked, whose mask must not be null.
+int census_call(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known, const uint32_t* mask,
+                bool masked, const double* theta, const double* pr, int32_t sample, const double* thresholds,
+                int32_t M, void* ws, int64_t ws_bytes, int64_t* out_counts, void* stream) {
   if (!c) return fail(MMSBM_ERR_INVALID, "null context");
   CensusPlan p;
   int rc = make_plan(c, M, &p);
@@ -179,6 +187,8 @@ int mmsbm_scan_census(mmsbm_ctx* c, const int32_t* order, const int64_t* known, 
   const ScanShape& sh = p.sh;
   if (!order || !theta || !pr || !out_counts || (M > 0 && !thresholds))
     return fail(MMSBM_ERR_INVALID, "null pointer");
+  int MW = 0;
+  if (masked && (rc = check_pair_mask(sh, "census", mask, &MW))) return rc;
   int ns, s0, WB;
   size_t w_bytes;
   if ((rc = check_call(sh, "census", "mmsbm_census_workspace_bytes", known, n_known, sample, ws, ws_bytes, p.total,
@@ -186,7 +196,7 @@ int mmsbm_scan_census(mmsbm_ctx* c, const int32_t* order, const int64_t* known, 
     return rc;
   if ((rc = pick_wb(sh, "census", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
   const int lds = (int)(sizeof(Head) + w_bytes + sizeof(double) * M + sizeof(count_t) * (M + 1) +
-                        sizeof(unsigned) * BM_WORDS);
+                        sizeof(unsigned) * (BM_WORDS + MW));
   const int G = sweep_grid(sh, WB, "MMSBM_CENSUS_GRID");
 
   DeviceGuard g(sh.device);
@@ -201,8 +211,12 @@ int mmsbm_scan_census(mmsbm_ctx* c, const int32_t* order, const int64_t* known, 
     const CensusArgs a{{(const double*)(w + p.off_thT), (const double*)(w + p.off_T), (const long long*)known,
                         n_known, sh.K, sh.P, sh.P16, ns, WB},
                        thresholds, bins, M};
+    const CensusMaskedArgs am{a, mask, MW};
     rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
       constexpr int KS = decltype(ks)::value;
+      if (masked)
+        return ns > 1 ? launch_lds(census_masked_kernel<KS, true>, G, lds, s, am)
+                      : launch_lds(census_masked_kernel<KS, false>, G, lds, s, am);
       return ns > 1 ? launch_lds(census_kernel<KS, true>, G, lds, s, a) : launch_lds(census_kernel<KS, false>, G, lds, s, a);
     });
     if (rc) return rc;
@@ -210,6 +224,46 @@ int mmsbm_scan_census(mmsbm_ctx* c, const int32_t* order, const int64_t* known, 
   census_finish_kernel<<<1, NT, 0, s>>>(bins, M, (long long*)out_counts);
   HIP_TRY(hipGetLastError());
   return MMSBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmsbm_census_max_m(void) { return CENSUS_MAX_M; }
+
+int mmsbm_pair_mask_shape(const mmsbm_ctx* c, int32_t* rows, int32_t* words_per_row) {
+  if (!c || !rows || !words_per_row) return fail(MMSBM_ERR_INVALID, "null argument");
+  ScanShape sh;
+  int MW;
+  if (int rc = scan_shape(c, "the pair mask", &sh)) return rc;
+  if (int rc = pair_mask_words(sh, "the pair mask", &MW)) return rc;
+  *rows = sh.P16, *words_per_row = MW;
+  return MMSBM_OK;
+}
+
+int mmsbm_census_workspace_bytes(const mmsbm_ctx* c, int32_t M, int64_t* bytes) {
+  if (!c || !bytes) return fail(MMSBM_ERR_INVALID, "null argument");
+  CensusPlan p;
+  int rc = make_plan(c, M, &p);
+  if (rc) return rc;
+  *bytes = (int64_t)p.total;
+  return MMSBM_OK;
+}
+
+int mmsbm_scan_census(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
+                      const double* theta, const double* pr, int32_t sample, const double* thresholds,
+                      int32_t M, void* ws, int64_t ws_bytes, int64_t* out_counts, void* stream) {
+  return census_call(c, order, known, n_known, nullptr, false, theta, pr, sample, thresholds, M, ws, ws_bytes,
+                     out_counts, stream);
+}
+
+int mmsbm_scan_census_masked(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
+                             const uint32_t* mask, const double* theta, const double* pr, int32_t sample,
+                             const double* thresholds, int32_t M, void* ws, int64_t ws_bytes,
+                             int64_t* out_counts, void* stream) {
+  return census_call(c, order, known, n_known, mask, true, theta, pr, sample, thresholds, M, ws, ws_bytes,
+                     out_counts, stream);
 }
 
 }  // extern "C"

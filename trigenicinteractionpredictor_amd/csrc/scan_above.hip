@@ -60,6 +60,13 @@ struct AboveArgs : SweepArgs {
   long long* out_keys;  // [capacity]
 };
 
+// The masked threshold scan (mmsbm_scan_above_masked): the pair mask travels in the masked kernels'
+// own argument struct, so AboveArgs and the unmasked kernels are what they were.
+struct AboveMaskedArgs : AboveArgs {
+  const unsigned* mask;  // [P16][MW] (include/mmsbm.h, mmsbm_pair_mask_shape)
+  int MW;
+};
+
 constexpr int STAGE = 256;  // rows of a wave's staging buffer: the most one tile can hold
 constexpr int STAGE_BYTES = (NT / 64) * STAGE * (int)(sizeof(double) + sizeof(long long));  // per workgroup
 
@@ -69,9 +76,10 @@ constexpr int STAGE_BYTES = (NT / 64) * STAGE * (int)(sizeof(double) + sizeof(lo
 // the K = 30 call with no hit ran at 2.96 ms against the census's 2.00 ms (P = 1500); with the
 // floor they take 1.98 ms and no instantiation spills a VGPR or takes scratch.  The ensemble keeps
 // the cap alone: under the floor its K = 10, B = 8 call with no hit ran at 6.98 ms against 5.51 ms.
-template <int KS, bool ENS>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENS ? 1 : 4, 4))) void scan_above_kernel(
-    AboveArgs A) {
+// The body of both kernels; MASK: Args is AboveMaskedArgs and row a of the mask lies behind the
+// staging buffers.
+template <int KS, bool ENS, bool MASK, class Args>
+__device__ __forceinline__ void scan_above_body(const Args& A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Head* st = reinterpret_cast<Head*>(smem);
   double* W = reinterpret_cast<double*>(smem + sizeof(Head));
@@ -107,7 +115,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENS ? 1 : 4,
     fill = 0;
   };
 
-  sweep<KS, ENS>(A, st, W, bm, [&](int a, int b0) {
+  auto begin_item = [&](int a, int b0) {
     // once per item: the key of (a, b0, column 0), the same for the whole wave.  A lane adds its
     // (kk + 4 i) P + c < 16 P + P16 <= 3.4 10^7 (packed_keys_fit: P <= 2 10^6) in 32 bits.
     const long long key0 = ((long long)a * P + b0) * P;
@@ -141,8 +149,29 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENS ? 1 : 4,
       }
       fill += n;
     };
-  });
+  };
+  if constexpr (MASK)
+    sweep_masked<KS, ENS>(A, st, W, bm, A.mask, A.MW,
+                          reinterpret_cast<unsigned*>(reinterpret_cast<char*>(bm + BM_WORDS) + STAGE_BYTES), begin_item);
+  else
+    sweep<KS, ENS>(A, st, W, bm, begin_item);
   if (fill) flush();  // wave-uniform
+}
+
+template <int KS, bool ENS>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENS ? 1 : 4, 4))) void scan_above_kernel(
+    AboveArgs A) {
+  scan_above_body<KS, ENS, false>(A);
+}
+
+// The masked single sample keeps the floor of 4 waves up to K = 16 only: above, the mask's registers
+// (the four (b, c) halfwords in flight, the blocked bits of two tiles, the bases of the four rows) do
+// not fit 128 VGPRs beside the operands and the floor would spill them to scratch; under the cap
+// alone those kernels take a 3-wave budget and no scratch.
+template <int KS, bool ENS>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENS || KS > 4 ? 1 : 4, 4))) void scan_above_masked_kernel(
+    AboveMaskedArgs A) {
+  scan_above_body<KS, ENS, true>(A);
 }
 
 __global__ void scan_above_finish_kernel(const count_t* __restrict__ cursor, long long* __restrict__ out_count) {
@@ -165,6 +194,59 @@ int make_plan(const mmsbm_ctx* c, AbovePlan* p) {
   return MMSBM_OK;
 }
 
+// Both entry points; `masked`: mmsbm_scan_above_masked, whose mask must not be null.
+int above_call(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known, const uint32_t* mask,
+               bool masked, const double* theta, const double* pr, int32_t sample, double threshold, int64_t capacity,
+               void* ws, int64_t ws_bytes, double* out_scores, int64_t* out_keys, int64_t* out_count, void* stream) {
+  if (!c) return fail(MMSBM_ERR_INVALID, "null context");
+  AbovePlan p;
+  int rc = make_plan(c, &p);
+  if (rc) return rc;
+  const ScanShape& sh = p.sh;
+  if (!order || !theta || !pr || !out_count) return fail(MMSBM_ERR_INVALID, "null pointer");
+  if (!std::isfinite(threshold)) return fail(MMSBM_ERR_INVALID, "the threshold must be a finite number");
+  if (capacity < 0) return fail(MMSBM_ERR_INVALID, "capacity=%lld < 0", (long long)capacity);
+  if (capacity > 0 && (!out_scores || !out_keys))
+    return fail(MMSBM_ERR_INVALID, "null output array with capacity > 0");
+  int MW = 0;
+  if (masked && (rc = check_pair_mask(sh, "the threshold scan", mask, &MW))) return rc;
+  int ns, s0, WB;
+  size_t w_bytes;
+  if ((rc = check_call(sh, "the threshold scan", "mmsbm_scan_above_workspace_bytes", known, n_known, sample, ws,
+                       ws_bytes, p.total, &ns, &s0)))
+    return rc;
+  if ((rc = pick_wb(sh, "the threshold scan", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
+  const int lds = (int)(sizeof(Head) + w_bytes + sizeof(unsigned) * (BM_WORDS + MW)) + STAGE_BYTES;
+  const int G = sweep_grid(sh, WB, "MMSBM_SCAN_ABOVE_GRID");
+
+  DeviceGuard g(sh.device);
+  hipStream_t s = (hipStream_t)stream;
+  char* w = (char*)ws;
+  count_t* cursor = (count_t*)(w + p.off_cursor);
+  HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(count_t), s));
+  if (sh.P >= 3) {
+    scan_prep_kernel<<<dim3(sh.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
+                                                     (double*)(w + p.off_T), sh.K, sh.KP, sh.R, sh.P, sh.P16, s0);
+    HIP_TRY(hipGetLastError());
+    const AboveArgs a{{(const double*)(w + p.off_thT), (const double*)(w + p.off_T), (const long long*)known,
+                       n_known, sh.K, sh.P, sh.P16, ns, WB},
+                      threshold, (count_t)capacity, cursor, out_scores, (long long*)out_keys};
+    const AboveMaskedArgs am{a, mask, MW};
+    rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
+      constexpr int KS = decltype(ks)::value;
+      if (masked)
+        return ns > 1 ? launch_lds(scan_above_masked_kernel<KS, true>, G, lds, s, am)
+                      : launch_lds(scan_above_masked_kernel<KS, false>, G, lds, s, am);
+      return ns > 1 ? launch_lds(scan_above_kernel<KS, true>, G, lds, s, a)
+                    : launch_lds(scan_above_kernel<KS, false>, G, lds, s, a);
+    });
+    if (rc) return rc;
+  }
+  scan_above_finish_kernel<<<1, 1, 0, s>>>(cursor, (long long*)out_count);
+  HIP_TRY(hipGetLastError());
+  return MMSBM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -182,47 +264,16 @@ int mmsbm_scan_above(mmsbm_ctx* c, const int32_t* order, const int64_t* known, i
                      const double* theta, const double* pr, int32_t sample, double threshold,
                      int64_t capacity, void* ws, int64_t ws_bytes, double* out_scores, int64_t* out_keys,
                      int64_t* out_count, void* stream) {
-  if (!c) return fail(MMSBM_ERR_INVALID, "null context");
-  AbovePlan p;
-  int rc = make_plan(c, &p);
-  if (rc) return rc;
-  const ScanShape& sh = p.sh;
-  if (!order || !theta || !pr || !out_count) return fail(MMSBM_ERR_INVALID, "null pointer");
-  if (!std::isfinite(threshold)) return fail(MMSBM_ERR_INVALID, "the threshold must be a finite number");
-  if (capacity < 0) return fail(MMSBM_ERR_INVALID, "capacity=%lld < 0", (long long)capacity);
-  if (capacity > 0 && (!out_scores || !out_keys))
-    return fail(MMSBM_ERR_INVALID, "null output array with capacity > 0");
-  int ns, s0, WB;
-  size_t w_bytes;
-  if ((rc = check_call(sh, "the threshold scan", "mmsbm_scan_above_workspace_bytes", known, n_known, sample, ws,
-                       ws_bytes, p.total, &ns, &s0)))
-    return rc;
-  if ((rc = pick_wb(sh, "the threshold scan", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
-  const int lds = (int)(sizeof(Head) + w_bytes + sizeof(unsigned) * BM_WORDS) + STAGE_BYTES;
-  const int G = sweep_grid(sh, WB, "MMSBM_SCAN_ABOVE_GRID");
+  return above_call(c, order, known, n_known, nullptr, false, theta, pr, sample, threshold, capacity, ws, ws_bytes,
+                    out_scores, out_keys, out_count, stream);
+}
 
-  DeviceGuard g(sh.device);
-  hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  count_t* cursor = (count_t*)(w + p.off_cursor);
-  HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(count_t), s));
-  if (sh.P >= 3) {
-    scan_prep_kernel<<<dim3(sh.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
-                                                     (double*)(w + p.off_T), sh.K, sh.KP, sh.R, sh.P, sh.P16, s0);
-    HIP_TRY(hipGetLastError());
-    const AboveArgs a{{(const double*)(w + p.off_thT), (const double*)(w + p.off_T), (const long long*)known,
-                       n_known, sh.K, sh.P, sh.P16, ns, WB},
-                      threshold, (count_t)capacity, cursor, out_scores, (long long*)out_keys};
-    rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
-      constexpr int KS = decltype(ks)::value;
-      return ns > 1 ? launch_lds(scan_above_kernel<KS, true>, G, lds, s, a)
-                    : launch_lds(scan_above_kernel<KS, false>, G, lds, s, a);
-    });
-    if (rc) return rc;
-  }
-  scan_above_finish_kernel<<<1, 1, 0, s>>>(cursor, (long long*)out_count);
-  HIP_TRY(hipGetLastError());
-  return MMSBM_OK;
+int mmsbm_scan_above_masked(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
+                            const uint32_t* mask, const double* theta, const double* pr, int32_t sample,
+                            double threshold, int64_t capacity, void* ws, int64_t ws_bytes, double* out_scores,
+                            int64_t* out_keys, int64_t* out_count, void* stream) {
+  return above_call(c, order, known, n_known, mask, true, theta, pr, sample, threshold, capacity, ws, ws_bytes,
+                    out_scores, out_keys, out_count, stream);
 }
 
 }  // extern "C"

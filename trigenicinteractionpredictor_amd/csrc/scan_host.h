@@ -82,6 +82,24 @@ inline int packed_keys_fit(const ScanShape& sh) {
   return MMSBM_OK;
 }
 
+// The pair mask of the masked families (include/mmsbm.h): uint32[P16][MW], MW = ceil(P16 / 32) words
+// per row, for P up to the pair census's cap (a row is at most 2 KiB of LDS, the mask 32 MiB).
+constexpr int PAIR_MASK_MAX_P = 16384;
+inline int pair_mask_words(const ScanShape& sh, const char* what, int* MW) {
+  if (sh.P > PAIR_MASK_MAX_P)
+    return fail(MMSBM_ERR_UNSUPPORTED, "%s: P=%d above the pair mask's cap of %d", what, sh.P, PAIR_MASK_MAX_P);
+  *MW = (sh.P16 + 31) / 32;
+  return MMSBM_OK;
+}
+
+// A masked call's mask: the cap on P, then the pointer (the unmasked call exists for "no mask").
+inline int check_pair_mask(const ScanShape& sh, const char* what, const uint32_t* mask, int* MW) {
+  if (int rc = pair_mask_words(sh, what, MW)) return rc;
+  if (!mask) return fail(MMSBM_ERR_INVALID, "%s: null pair mask (the unmasked call takes none)", what);
+  if ((uintptr_t)mask & 3) return fail(MMSBM_ERR_INVALID, "%s: misaligned pair mask", what);
+  return MMSBM_OK;
+}
+
 // thT[B][KP][P16] and T[B][P][K][KP] (scan_score.h) from `off` on, each 256-byte aligned.
 inline void score_workspace(const ScanShape& sh, size_t& off, size_t* off_thT, size_t* off_T) {
   const size_t B = sh.B, P = sh.P, K = sh.K, KP = sh.KP, P16 = sh.P16;

@@ -65,8 +65,23 @@ __device__ __forceinline__ void sweep_begin(Head* st) {
 // consume(ct, tot, votes, el), votes holding in byte i the number of slots whose element i is at or
 // above vthr, for eligible and other elements alike.  sweep() itself is the instantiation without
 // it, which holds nothing of the votes.
-template <int KS, bool ENS, bool VOTES, class BeginItem>
+//
+// MASK (sweep_masked, for the masked census and threshold scan): a triple is eligible only if none of
+// its three pairs is set in the pair mask (include/mmsbm.h: mask[P16][MW] in rank positions, bit
+// y & 31 of mask[x][y >> 5] blocks the pair x < y).  Per item the workgroup first reads the bits
+// (a, the item's rows) through the scalar cache and skips the item when every row b with a < b < P is
+// blocked: before the barrier, the known-key searches and fill_w.  Otherwise row a goes to mrow (MW
+// words of LDS, the kernel's) with the bitmap, and a lane keeps its four (a, b) bits for the item.
+// Per tile the (a, c) bits are halfword ct of mrow: at 0xFFFF the tile's MFMA chain is not issued and
+// the consumer is not called (wave-uniform).  The (b, c) bits of a lane's four rows are halfword ct of
+// mask rows b0 + kk + 4 i, loaded one tile ahead with the Th' operand.  The lane's blocked elements
+// travel with the tile as four bits and are taken out of el after the interior test, which stays as
+// it is.  Every index stays inside the mask: rows a < P and b <= b0 + 15 < P16, halfwords ct < P16 / 16
+// <= 2 MW.  The instantiations without MASK hold nothing of it.
+template <int KS, bool ENS, bool VOTES, bool MASK, class BeginItem>
 __device__ __forceinline__ void sweep_impl(const SweepArgs& A, Head* st, double* W, unsigned* bm, double vthr,
+                                           [[maybe_unused]] const unsigned* __restrict__ mask,
+                                           [[maybe_unused]] int MW, [[maybe_unused]] unsigned* mrow,
                                            BeginItem&& begin_item) {
   using namespace scan_select;
   using Sc = scan_score::Score<KS>;
@@ -85,7 +100,19 @@ __device__ __forceinline__ void sweep_impl(const SweepArgs& A, Head* st, double*
   for (long long q = blockIdx.x; q < PP * nbq; q += gridDim.x) {
     const int a = (int)(q / nbq), bq = (int)(q % nbq);
     if (a >= P - 2 || bq * RB + RB - 1 <= a || bq * RB >= P - 1) continue;  // no a < b < c here
+    if constexpr (MASK) {
+      // the (a, b) bits of the item's rows: RB = 16, 32 or 64 bits from bit bq RB of row a on
+      const int r0 = bq * RB, w0 = r0 >> 5;
+      const unsigned* __restrict__ ra = mask + (size_t)a * MW;
+      unsigned long long bits = (unsigned long long)ra[w0] >> (r0 & 31);  // w0 < MW: r0 < P - 1
+      if (RB == 64 && w0 + 1 < MW) bits |= (unsigned long long)ra[w0 + 1] << 32;
+      const int lo = max(a + 1, r0) - r0, hi = min(P, r0 + RB) - r0;  // 0 <= lo < hi <= RB, bits inside row a
+      const unsigned long long need = (hi >= 64 ? ~0ull : (1ull << hi) - 1) & ~((1ull << lo) - 1);
+      if ((bits & need) == need) continue;  // workgroup-uniform: every pair (a, b) of the item is blocked
+    }
     __syncthreads();  // the previous item's W, bitmap and range are read
+    if constexpr (MASK)
+      for (int i = threadIdx.x; i < MW; i += NT) mrow[i] = mask[(size_t)a * MW + i];
     if (has_known) {
       // the known keys whose first position is a and whose second falls into the item's rows
       if (threadIdx.x == 64) st->lo = lower_bound(A.known, 0, A.n_known, ((long long)a * PP + (long long)bq * RB) * PP);
@@ -116,8 +143,28 @@ __device__ __forceinline__ void sweep_impl(const SweepArgs& A, Head* st, double*
     double bnext[KS];  // single sample: the next tile's Th' operand is in flight
     if (!ENS && ct < nct) Sc::load_b(bnext, A.thT, P16, ct * 16, m, kk);
     auto consume = begin_item(a, b0);
+    [[maybe_unused]] unsigned abm = 0;  // bit i: the pair (a, b0 + kk + 4 i) is blocked
+    [[maybe_unused]] unsigned bcn[4] = {0, 0, 0, 0};  // the next tile's (b, c) halfwords, in flight
+    [[maybe_unused]] const unsigned short* mrow16 = reinterpret_cast<const unsigned short*>(mrow);
+    // halfword ct of the lane's four mask rows: one 32-bit lane offset (row b0 + kk; the mask is at
+    // most 32 MiB) on four wave-uniform bases, the rows 4 i below it
+    [[maybe_unused]] const unsigned bc_off = (unsigned)(b0 + kk) * (unsigned)MW * 4u;
+    [[maybe_unused]] auto load_bc = [&](unsigned (&h)[4], int ct) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        h[i] = *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(mask) + (size_t)(16 * i) * MW +
+                                                        (bc_off + 2u * (unsigned)ct));
+    };
+    if constexpr (MASK) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + kk + 4 * i;
+        abm |= ((mrow[b >> 5] >> (b & 31)) & 1u) << i;
+      }
+      if (ct < nct) load_bc(bcn, ct);
+    }
     // Resolve a finished tile's eligibility and hand it over.
-    auto finish = [&](const d4v& tot, [[maybe_unused]] unsigned votes, int ct) {
+    auto finish = [&](const d4v& tot, [[maybe_unused]] unsigned votes, [[maybe_unused]] unsigned blk, int ct) {
       const int c0 = ct * 16, c = c0 + m;
       bool el[4];
       if (b0 > a && c0 > b0 + 15 && c0 + 16 <= P) {  // an interior tile: a < b < c < P everywhere
@@ -128,6 +175,10 @@ __device__ __forceinline__ void sweep_impl(const SweepArgs& A, Head* st, double*
           const int b = b0 + kk + 4 * i;
           el[i] = a < b && b < c && c < P;
         }
+      }
+      if constexpr (MASK) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) el[i] = el[i] && !((blk >> i) & 1u);
       }
       if (khi > klo && ((bm[wb * (CT_BITS / 32) + ((ct & (CT_BITS - 1)) >> 5)] >> (ct & 31)) & 1u)) {
 #pragma unroll
@@ -147,39 +198,63 @@ __device__ __forceinline__ void sweep_impl(const SweepArgs& A, Head* st, double*
     d4v prev = {0.0, 0.0, 0.0, 0.0};
     int prev_ct = -1;
     [[maybe_unused]] unsigned votes = 0, prev_votes = 0;
+    [[maybe_unused]] unsigned blk = 0, prev_blk = 0;  // bit i: element i of the tile is blocked
     for (; ct < nct; ct += CW) {
       const int c0 = ct * 16;
       d4v tot;
+      [[maybe_unused]] bool dead = false;  // every pair (a, c) of the tile is blocked (wave-uniform)
+      if constexpr (MASK) {
+        const unsigned ac = mrow16[ct];
+        dead = ac == 0xFFFFu;
+        blk = abm | (((ac >> m) & 1u) ? 0xFu : 0u);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) blk |= ((bcn[i] >> m) & 1u) << i;
+        if (ct + CW < nct) load_bc(bcn, ct + CW);
+      }
       if (!ENS) {
         double bcur[KS];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) bcur[ks] = bnext[ks];
         if (ct + CW < nct) Sc::load_b(bnext, A.thT, P16, c0 + 16 * CW, m, kk);
+        if constexpr (MASK) {
+          if (dead) continue;  // the finished tile waits for the next live one
+        }
         tot = Sc::tile_one(areg, bcur);
       } else if constexpr (VOTES) {
         tot = Sc::tile_votes(W, A.thT, ns, RB, P16, wb, c0, m, kk, div, vthr, votes);
       } else {
+        if constexpr (MASK) {
+          if (dead) continue;
+        }
         tot = Sc::tile_mean(W, A.thT, ns, RB, P16, wb, c0, m, kk, div);
       }
-      if (prev_ct >= 0) finish(prev, prev_votes, prev_ct);
+      if (prev_ct >= 0) finish(prev, prev_votes, prev_blk, prev_ct);
       prev = tot;
       prev_ct = ct;
       if constexpr (VOTES && ENS) prev_votes = votes;
+      if constexpr (MASK) prev_blk = blk;
     }
-    if (prev_ct >= 0) finish(prev, prev_votes, prev_ct);
+    if (prev_ct >= 0) finish(prev, prev_votes, prev_blk, prev_ct);
   }
 }
 
 template <int KS, bool ENS, class BeginItem>
 __device__ __forceinline__ void sweep(const SweepArgs& A, Head* st, double* W, unsigned* bm,
                                       BeginItem&& begin_item) {
-  sweep_impl<KS, ENS, false>(A, st, W, bm, 0.0, static_cast<BeginItem&&>(begin_item));
+  sweep_impl<KS, ENS, false, false>(A, st, W, bm, 0.0, nullptr, 0, nullptr, static_cast<BeginItem&&>(begin_item));
 }
 
 template <int KS, bool ENS, class BeginItem>
 __device__ __forceinline__ void sweep_votes(const SweepArgs& A, Head* st, double* W, unsigned* bm, double vthr,
                                             BeginItem&& begin_item) {
-  sweep_impl<KS, ENS, true>(A, st, W, bm, vthr, static_cast<BeginItem&&>(begin_item));
+  sweep_impl<KS, ENS, true, false>(A, st, W, bm, vthr, nullptr, 0, nullptr, static_cast<BeginItem&&>(begin_item));
+}
+
+// mask: [P16][MW] words, never null; mrow: MW words of the kernel's LDS.
+template <int KS, bool ENS, class BeginItem>
+__device__ __forceinline__ void sweep_masked(const SweepArgs& A, Head* st, double* W, unsigned* bm,
+                                             const unsigned* mask, int MW, unsigned* mrow, BeginItem&& begin_item) {
+  sweep_impl<KS, ENS, false, true>(A, st, W, bm, 0.0, mask, MW, mrow, static_cast<BeginItem&&>(begin_item));
 }
 
 }  // namespace scan_sweep

@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .scan import (LimitError, bracket_threshold, census_chunks, check_known_keys, check_partner_known,
-                   pair_eligible, rank_of, rank_order)
+from .scan import (LimitError, bracket_threshold, census_chunks, check_known_keys, check_pair_mask,
+                   check_partner_known, pair_eligible, rank_of, rank_order)
 
 _CURRENT_STREAM = contextlib.nullcontext()     # a scan call without a stream: nothing to make current
 
@@ -235,18 +235,26 @@ class EMEngine:
         return ws
 
     @contextlib.contextmanager
-    def _scan_call(self, known, sample, stream):
+    def _scan_call(self, known, sample, stream, mask=None):
         """One call of a scan family: checks `known` and `sample`, makes the launch stream current
         and uploads the keys; -> (head, the stream), head = the C calls' (ctx, order, known or NULL,
         n_known, theta, pr, sample).  Whatever the call uploads or allocates it creates inside, so
-        every tensor belongs to the stream its kernels run on."""
+        every tensor belongs to the stream its kernels run on.  mask: a pair mask (scan.pair_mask) for
+        the masked entries, checked and uploaded here too; the head then is theirs, the mask behind
+        n_known."""
         known = check_known_keys(known)
         sample = self._sample(sample)
+        if mask is not None:
+            mask = check_pair_mask(mask, self.P)
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         with torch.cuda.stream(s) if stream is not None else _CURRENT_STREAM:
             known_d = torch.from_numpy(known).to(self.device) if known.size else None
-            yield (self.ctx, _ptr(self.scan_order), _ptr(known_d) if known.size else None, int(known.size),
-                   _ptr(self.theta), _ptr(self.pr), sample), s
+            head = (self.ctx, _ptr(self.scan_order), _ptr(known_d) if known.size else None, int(known.size))
+            if mask is not None:
+                words = mask if mask.flags.writeable else mask.copy()   # torch takes no read-only array
+                mask_d = torch.from_numpy(words.view(np.int32)).to(self.device)   # the same 32-bit words
+                head += (_ptr(mask_d),)
+            yield head + (_ptr(self.theta), _ptr(self.pr), sample), s
 
     def _per_threshold(self, family, entry, plan, call, shape, dtype, axis):
         """The census families' loop inside a _scan_call: one call of `entry` per chunk of `plan`
@@ -328,55 +336,60 @@ class EMEngine:
         counts, scores, ids = counts.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
         return [(scores[i, :int(m)].copy(), ids[i, :int(m)].copy()) for i, m in enumerate(counts)]
 
-    def census_async(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None):
+    def census_async(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None, mask=None):
         """census without the host copy: -> device tensors (counts int64[len(thresholds)] in the
         caller's order, total int64[1]).  Nothing synchronises."""
         plan = self._census_plan(thresholds)
-        with self._scan_call(known, sample, stream) as call:
-            return self._census(plan, call)
+        with self._scan_call(known, sample, stream, mask) as call:
+            return self._census(plan, call, mask is not None)
 
     def _census_plan(self, thresholds):
         return census_chunks(thresholds, int(self.lib.mmsbm_census_max_m()))   # ValueError on a NaN or infinite one
 
-    def _census(self, plan, call):
+    def _census(self, plan, call, masked=False):
         """census_async inside a _scan_call: every chunk's output is its counts and then the total
-        of the eligible triples (an empty chunk: the call that returns the total)."""
-        counts, last = self._per_threshold("census", self.lib.mmsbm_scan_census, plan, call,
-                                           lambda m: (m + 1,), torch.int64, 0)
+        of the eligible triples (an empty chunk: the call that returns the total).  masked: the
+        _scan_call took a mask, so the entry is the masked one."""
+        entry = self.lib.mmsbm_scan_census_masked if masked else self.lib.mmsbm_scan_census
+        counts, last = self._per_threshold("census", entry, plan, call, lambda m: (m + 1,), torch.int64, 0)
         return counts, last[-1:]
 
-    def census(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None):
+    def census(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None, mask=None):
         """The score census (include/mmsbm.h mmsbm_scan_census): -> (counts int64[len(thresholds)],
         total int) on the host; counts[i] = the eligible triples (those scan_top ranks: distinct
         genes, key not in `known`) whose score is >= thresholds[i], total = the eligible triples.
         The thresholds may come in any order, with duplicates, in any number or none; a NaN or an
         infinite one raises ValueError.  known, sample: as for scan_top.  The scores are scan_top's
-        bit for bit, so census(scan_top(n)[0]) numbers that list's entries."""
-        counts, total = self.census_async(thresholds, known, sample, stream)
+        bit for bit, so census(scan_top(n)[0]) numbers that list's entries.
+        mask: a pair mask (scan.pair_mask; include/mmsbm.h mmsbm_scan_census_masked): a triple that
+        contains a blocked pair of genes is not eligible either; None: the unmasked call."""
+        counts, total = self.census_async(thresholds, known, sample, stream, mask)
         if stream is not None:
             stream.synchronize()
         return counts.cpu().numpy(), int(total.cpu()[0])
 
     # -------------------------------------------------------- threshold scan
-    def _scan_above(self, threshold, known, sample, stream, limit):
+    def _scan_above(self, threshold, known, sample, stream, limit, mask=None):
         """-> (scores f64[n] and packed keys int64[n] on the device, sorted by the scan's total
         order; the kernel's count int64[1] on the device; the census's count n; the launch stream)."""
         threshold = float(threshold)
         if not np.isfinite(threshold):
             raise ValueError("the threshold must be a finite number")
         plan = self._census_plan([threshold])
-        with self._scan_call(known, sample, stream) as call:    # one upload of the keys for both kernels
+        with self._scan_call(known, sample, stream, mask) as call:    # one upload of the keys for both kernels
             head, s = call
-            n = int(self._census(plan, call)[0].cpu()[0])   # the same score bits: exactly the rows the kernel will find
+            masked = mask is not None
+            # the same score bits: exactly the rows the kernel will find
+            n = int(self._census(plan, call, masked)[0].cpu()[0])
             if n > int(limit):
                 raise LimitError(n, int(limit))
             ws = self.scan_workspace("scan_above")
             scores = torch.empty(n, dtype=torch.float64, device=self.device)
             keys = torch.empty(n, dtype=torch.int64, device=self.device)
             found = torch.empty(1, dtype=torch.int64, device=self.device)
-            _lib.check(self.lib.mmsbm_scan_above(*head, threshold, n, _ptr(ws), ws.numel(),
-                                                 _ptr(scores) if n else None, _ptr(keys) if n else None,
-                                                 _ptr(found), s.cuda_stream))
+            entry = self.lib.mmsbm_scan_above_masked if masked else self.lib.mmsbm_scan_above
+            _lib.check(entry(*head, threshold, n, _ptr(ws), ws.numel(), _ptr(scores) if n else None,
+                             _ptr(keys) if n else None, _ptr(found), s.cuda_stream))
             # the rows arrive in any order; two stable sorts give the scan's: score descending,
             # equal scores by key ascending
             keys, at = torch.sort(keys, stable=True)
@@ -392,40 +405,48 @@ class EMEngine:
         return torch.stack([order[keys // (P * P)], order[(keys // P) % P], order[keys % P]], dim=1)
 
     def scan_above_async(self, threshold, known: np.ndarray = None, sample: int = None, stream=None,
-                         limit: int = 1 << 26):
+                         limit: int = 1 << 26, mask=None):
         """scan_above without the host copy: -> device tensors (scores f64[n], ids int32[n][3]) on
         the launch stream.  The number of rows comes from the census first (one host read of one
         integer); a count above `limit` raises before anything is launched for the list."""
-        scores, keys, _, _, s = self._scan_above(threshold, known, sample, stream, limit)
+        scores, keys, _, _, s = self._scan_above(threshold, known, sample, stream, limit, mask)
         with torch.cuda.stream(s):
             return scores, self._keys_to_ids(keys)
 
     def scan_above(self, threshold, known: np.ndarray = None, sample: int = None, stream=None,
-                   limit: int = 1 << 26):
+                   limit: int = 1 << 26, mask=None):
         """Every eligible triple (those scan_top ranks: distinct genes, key not in `known`) whose
         score is >= threshold (include/mmsbm.h mmsbm_scan_above): -> (scores f64[n], ids int32[n][3]
         in key order) on the host, sorted by the scan's total order (score descending, equal scores
         by packed key ascending), n = census([threshold]).  The scores are scan_top's bit for bit, so
         the first rows are scan_top's list.  A NaN or infinite threshold raises ValueError, as does a
         count above `limit` (scan.LimitError, with the count and the limit): 16 bytes per row on the
-        device, twice that while sorting.  known, sample: as for scan_top."""
-        scores, keys, found, n, s = self._scan_above(threshold, known, sample, stream, limit)
+        device, twice that while sorting.  known, sample: as for scan_top.  mask: as for census
+        (mmsbm_scan_above_masked); n = census([threshold], mask=mask) then."""
+        scores, keys, found, n, s = self._scan_above(threshold, known, sample, stream, limit, mask)
         with torch.cuda.stream(s):
             ids = self._keys_to_ids(keys).cpu().numpy()
             scores, found = scores.cpu().numpy(), int(found.cpu()[0])
-        assert found == n, "mmsbm_scan_above found %d rows where the census counted %d" % (found, n)
+        assert found == n, "the threshold scan found %d rows where the census counted %d" % (found, n)
         return scores, ids
 
-    def scan_top_any(self, n: int, known: np.ndarray = None, sample: int = None, limit: int = 1 << 26):
+    def scan_top_any(self, n: int, known: np.ndarray = None, sample: int = None, limit: int = 1 << 26, mask=None):
         """scan_top for any n >= 1: -> (scores f64[n'], ids int32[n'][3]) on the host, best first,
         n' <= n.  Up to mmsbm_scan_max_n() it is scan_top; above, censuses bracket a threshold
         between the eligible total and the last score of scan_top(max) (scan.bracket_threshold),
         scan_above fetches what lies at or above it and the list is cut to n.  Exact: the three
         kernels see the same score bits under the same total order.  `limit`: as for scan_above
-        (reached only when more than that many triples tie around rank n)."""
+        (reached only when more than that many triples tie around rank n).
+        mask: a pair mask (scan.pair_mask).  The top-N kernel takes none, so with a mask scan_top is
+        never called: masked censuses bracket the threshold between 0 and 1 (scores are
+        probabilities), the masked scan_above fetches the rows and the list is cut to n."""
         n = int(n)
         if n < 1:
             raise ValueError("scan_top_any needs n >= 1")
+        if mask is not None:
+            lo = bracket_threshold(n, 1.0, lambda t: self.census(t, known, sample, mask=mask)[0])
+            scores, ids = self.scan_above(lo, known, sample, limit=limit, mask=mask)
+            return scores[:n], ids[:n]
         max_n = int(self.lib.mmsbm_scan_max_n())
         if n <= max_n:
             return self.scan_top(n, known, sample)

@@ -598,6 +598,53 @@ class Model:
             ids[n] = g % self.P
         return float(self._push().predict(np.array([ids], dtype=np.int32))[0, 0])
 
+    # ------------------------------------------------- trigenic interactions proper
+    # A triple whose genes already interact pairwise is no trigenic candidate.  The digenic side of
+    # the model says which pairs do; as a pair mask (scan.pair_mask) it restricts the trigenic scans,
+    # which run on the triplet engine (JointEngine.tri) under the masked census and threshold scan.
+    def digenic_mask(self, threshold=0.5, measured=True):
+        """The pair mask of the digenic side: blocks every pair of genes whose digenic prediction
+        (do_prediction of the pair, its ids in key order) is >= threshold and, with `measured`, every pair of `dlinks` /
+        `dtest_links` measured with rating 1.  The predictions are one JointEngine.predict over all
+        P (P - 1) / 2 pairs."""
+        from .scan import pair_mask, rank_order
+        P = self.P
+        order = rank_order(P)
+        x, y = np.triu_indices(P, 1)
+        pairs = np.stack([order[x], order[y]], axis=1).astype(np.int32)     # each pair as `dlinks` keys it
+        blocked = pairs[self._push().predict(pairs)[0] >= float(threshold)] if len(pairs) else pairs
+        if measured:
+            seen = [[int(g) for g in key.split("_")] for table in (self.dlinks, self.dtest_links)
+                    for key, n in table.items() if n[1]]
+            seen = [p for p in seen if p[0] != p[1]]
+            if seen:
+                blocked = np.concatenate([blocked, np.asarray(seen, dtype=np.int32)], axis=0)
+        return pair_mask(P, pairs=blocked)
+
+    def _trigenic_known(self, exclude):
+        """The measured triples of the `exclude`d tables as sorted packed keys (scan.known_keys);
+        `test_links` holds the test pairs too (:511-533), which are no triples."""
+        from .scan import known_keys
+        tables = [np.array([[int(g) for g in key.split("_")] for key in table if key.count("_") == 2],
+                           dtype=np.int64).reshape(-1, 3) for table in (self.links, self.test_links)]
+        return known_keys((self.P, *tables), exclude)
+
+    def predict_novel_trigenic(self, n, threshold=0.5, exclude=("train", "test")):
+        """The n most probable triples of distinct genes outside the `exclude`d triplet tables none
+        of whose three pairs the digenic side blocks (digenic_mask(threshold)), best first:
+        [probability, "i_j_k", [name1, name2, name3]] rows, the key as `links` spells it and the
+        names sorted.  Any n >= 1 (EMEngine.scan_top_any with the mask)."""
+        scores, ids = self._push().tri.scan_top_any(int(n), self._trigenic_known(exclude), sample=0,
+                                                    mask=self.digenic_mask(threshold))
+        return [[float(p), "_".join(str(int(g)) for g in row), sorted(self.id_gene[int(g)] for g in row)]
+                for p, row in zip(scores, ids)]
+
+    def novel_trigenic_census(self, thresholds, threshold=0.5, exclude=("train", "test")):
+        """-> (counts int64[len(thresholds)], total): the triples predict_novel_trigenic ranks with
+        P(r = 1) >= thresholds[i], and all of them (EMEngine.census with the mask)."""
+        return self._push().tri.census(thresholds, self._trigenic_known(exclude), sample=0,
+                                       mask=self.digenic_mask(threshold))
+
     def calculate_test_set_results(self):
         rows = []
         for table in (self.test_links, self.dtest_links):

@@ -29,6 +29,12 @@ from .tracked import TrackedLinks, tracked, version_of
 NATIVE_INGEST = True   # get_traintest's native reader for canonical files (ingest.py)
 
 
+def _masked(mask):
+    """The mask keyword of an engine call: nothing without a mask, so the unmasked calls are made
+    as they always were."""
+    return {} if mask is None else {"mask": mask}
+
+
 class Model:
     def __init__(self, device=None):
         self._links_version = 0
@@ -425,24 +431,38 @@ class Model:
         scores, ids = eng.scan_top(int(n), known_keys(self, exclude), sample=0)
         return self._rows(scores, ids)
 
-    def predict_novel_any(self, n, exclude=("train", "test")):
+    def predict_novel_any(self, n, exclude=("train", "test"), mask=None):
         """predict_novel for any n >= 1: above the scan's cap of 4096 rows, censuses bracket the
         score of rank n and one threshold scan fetches what lies at or above it
-        (engine.scan_top_any).  Up to the cap it is predict_novel."""
+        (engine.scan_top_any).  Up to the cap it is predict_novel.  mask: a pair mask
+        (Model.pair_mask): no triple that contains a blocked pair of genes is listed; every n then
+        goes through the masked censuses and the masked threshold scan."""
         from .scan import known_keys
-        scores, ids = self._push().scan_top_any(int(n), known_keys(self, exclude), sample=0)
+        scores, ids = self._push().scan_top_any(int(n), known_keys(self, exclude), sample=0, **_masked(mask))
         return self._rows(scores, ids)
 
-    def predict_network(self, threshold=0.5, exclude=("train", "test"), limit=1 << 26):
+    def pair_mask(self, genes=None, pairs=None):
+        """The pair mask of the `mask=` keywords (scan.pair_mask): genes = the allowed genes (every
+        pair that touches another gene is blocked), pairs = pairs of genes to block; ids or names as
+        do_prediction takes them (KeyError on an unknown name, IndexError on an id outside the
+        table).  Both None: the mask that blocks nothing."""
+        from .scan import pair_mask, resolve_genes
+        if genes is not None:
+            genes = resolve_genes(self, list(genes))
+        if pairs is not None:
+            pairs = np.asarray(resolve_genes(self, [g for pair in pairs for g in pair]), dtype=np.int64).reshape(-1, 2)
+        return pair_mask(self.P, pairs=pairs, genes=genes)
+
+    def predict_network(self, threshold=0.5, exclude=("train", "test"), limit=1 << 26, mask=None):
         """Every triple of distinct genes outside the `exclude`d link tables with
         P(r = 1) >= threshold, best first, equal probabilities by key: the predicted trigenic
         network at that cut, in predict_novel's row format.  novel_census([threshold]) is its
         length; more than `limit` rows raise ValueError (scan.LimitError) before the list is
         formed.  One census and one threshold scan of all C(P, 3) triples on the GPU
-        (engine.scan_above)."""
+        (engine.scan_above).  mask: as for predict_novel_any."""
         from .scan import known_keys
         scores, ids = self._push().scan_above(float(threshold), known_keys(self, exclude), sample=0,
-                                              limit=limit)
+                                              limit=limit, **_masked(mask))
         return self._rows(scores, ids)
 
     def _gene_arg(self, gene):
@@ -498,13 +518,13 @@ class Model:
     # Exactness: the counts are exact for the scan's score bits; a listed triple's probability comes
     # from the predict kernel, which sums in another order, so a triple within rounding distance
     # (about 1e-12 relative) of another triple's score may be placed on either side of it.
-    def novel_census(self, thresholds, exclude=("train", "test")):
+    def novel_census(self, thresholds, exclude=("train", "test"), mask=None):
         """-> (counts int64[len(thresholds)], total): counts[i] = the triples of distinct genes
         outside the `exclude`d link tables with P(r = 1) >= thresholds[i], total = all of them.
         Stands to engine.census as predict_novel stands to scan_top: one pass over all C(P, 3)
-        triples on the GPU per 1024 thresholds."""
+        triples on the GPU per 1024 thresholds.  mask: as for predict_novel_any."""
         from .scan import known_keys
-        return self._push().census(thresholds, known_keys(self, exclude), sample=0)
+        return self._push().census(thresholds, known_keys(self, exclude), sample=0, **_masked(mask))
 
     def _ranked(self, ids, exclude):
         from .scan import known_keys, ranks_of

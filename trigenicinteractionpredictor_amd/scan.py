@@ -84,6 +84,18 @@ without a threshold chosen in advance.
                            every M up to -n 8, the four lowest and the four highest M beyond.  Not
                            with --best: one restart has no quorum.
 
+Two options restrict every table they apply to by PAIRS of genes (scan.pair_mask, the masked census
+and threshold scan, mmsbm_scan_census_masked / mmsbm_scan_above_masked): a triple that contains a
+blocked pair is not eligible.
+    --allow-genes FILE     one gene name or id per line: the gene universe, such as the strains of an
+                           array.  Every pair that touches another gene is blocked.
+    --block-pairs FILE     two gene names or ids per line, tab or space separated: these pairs are
+                           blocked, such as the pairs known to interact digenically.
+They apply to the main table (which then goes through `EMEngine.scan_top_any`: masked censuses find
+the cut, the masked threshold scan lists above it), --census and --network, and combine by OR.  With
+--gene / --all-genes, --pairs, --gene-census, --consensus and --quorum, whose kernels take no mask,
+they are refused.  --heldout-ranks is not restricted by them.
+
 Exactness: the counts are exact for the scan's score bits.  A listed triple's probability comes from
 the predict kernel, which sums in another order, so a triple within rounding distance (about 1e-12
 relative) of another triple's score may be placed on either side of it.  (Listed triples are
@@ -222,6 +234,106 @@ def check_partner_known(known, Q: int):
         raise ValueError("each query's known pair keys must be sorted and unique "
                          "(scan.partner_known)")
     return off, pairs
+
+
+# ---------------------------------------------------------------------------------- pair mask
+MAX_MASK_P = 16384   # the pair mask's cap on P (include/mmsbm.h, mmsbm_pair_mask_shape)
+
+
+def pair_mask_shape(P: int):
+    """(rows P16, words per row MW) of the pair mask of P genes, as mmsbm_pair_mask_shape returns
+    them: P rounded up to 16 (at least 16) and ceil(P16 / 32); ValueError above MAX_MASK_P."""
+    P = int(P)
+    if not 0 <= P <= MAX_MASK_P:
+        raise ValueError("pair mask: P=%d outside [0, %d]" % (P, MAX_MASK_P))
+    P16 = max(16, (P + 15) // 16 * 16)
+    return P16, (P16 + 31) // 32
+
+
+def pair_mask(P: int, pairs=None, genes=None, matrix=None) -> np.ndarray:
+    """The pair mask the masked scans take (include/mmsbm.h mmsbm_scan_census_masked): uint32
+    [P16][MW] in RANK positions, bit y & 31 of mask[x][y >> 5] set = the pair of positions (x, y)
+    is blocked, and a triple that contains a blocked pair is not eligible.  Three sources in GENE
+    ids, combined by OR:
+        pairs   int[n][2]: these pairs are blocked;
+        genes   the allowed gene ids: every pair that touches another gene is blocked;
+        matrix  bool[P][P]: an entry set on either side blocks the pair.
+    Both triangles are written (the kernels read x < y only); the diagonal, rows >= P and bits >= P
+    stay zero.  ValueError on an id outside [0, P) or a pair of one gene.  Goes through a bool
+    [P16][P16] on the host."""
+    P = int(P)
+    P16, MW = pair_mask_shape(P)
+    rank = rank_of(rank_order(P))
+    blocked = np.zeros((P16, MW * 32), dtype=bool)
+
+    def ids_of(a, what):
+        a = np.asarray(a)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("pair mask: %s must be integer gene ids" % what)
+        a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= P):
+            raise ValueError("pair mask: %s hold a gene id outside [0, %d)" % (what, P))
+        return a
+
+    if pairs is not None:
+        pairs = ids_of(pairs, "pairs").reshape(-1, 2)
+        if (pairs[:, 0] == pairs[:, 1]).any():
+            raise ValueError("pair mask: a pair of one gene")
+        x, y = rank[pairs[:, 0]], rank[pairs[:, 1]]
+        blocked[x, y] = True
+        blocked[y, x] = True
+    if genes is not None:
+        out = np.ones(P, dtype=bool)
+        out[rank[ids_of(genes, "genes").reshape(-1)]] = False    # in rank positions
+        blocked[:P, :P] |= out[:, None] | out[None, :]
+    if matrix is not None:
+        matrix = np.asarray(matrix)
+        if matrix.shape != (P, P):
+            raise ValueError("pair mask: matrix must be bool[%d][%d]" % (P, P))
+        m = matrix.astype(bool)
+        m = m | m.T
+        order = rank_order(P)
+        blocked[:P, :P] |= m[order][:, order]      # position (x, y) <- genes (order[x], order[y])
+    if P:
+        blocked[np.arange(P), np.arange(P)] = False
+    words = np.packbits(blocked, axis=1, bitorder="little").view("<u4")
+    return np.ascontiguousarray(words.astype(np.uint32, copy=False))
+
+
+def check_pair_mask(mask, P: int) -> np.ndarray:
+    """The pair mask as the engine's masked calls take it -> the same contiguous uint32 array;
+    ValueError unless it is uint32[P16][MW] (pair_mask_shape(P)) and C-contiguous, as pair_mask
+    gives it.  Nothing is converted: a mask of another type or layout is a mistake."""
+    P16, MW = pair_mask_shape(P)
+    if not isinstance(mask, np.ndarray) or mask.dtype != np.uint32:
+        raise ValueError("the pair mask must be a numpy uint32 array (scan.pair_mask)")
+    if mask.shape != (P16, MW):
+        raise ValueError("the pair mask must be uint32[%d][%d] for P=%d, not %r (scan.pair_mask)"
+                         % (P16, MW, int(P), mask.shape))
+    if not mask.flags.c_contiguous:
+        raise ValueError("the pair mask must be C-contiguous (scan.pair_mask)")
+    return mask
+
+
+def read_allow_genes(path):
+    """--allow-genes FILE -> the tokens, one name or id per line (blank lines and # comments skipped)."""
+    with open(path, encoding="utf-8") as f:
+        return [line.split()[0] for line in f if line.strip() and not line.lstrip().startswith("#")]
+
+
+def read_block_pairs(path):
+    """--block-pairs FILE -> [(token, token)], two names or ids per line, tab or space separated
+    (blank lines and # comments skipped); ValueError on a line without exactly two."""
+    out = []
+    with open(path, encoding="utf-8") as f:
+        for n, line in enumerate(f, 1):
+            if not line.strip() or line.lstrip().startswith("#"):
+                continue
+            t = line.split()
+            if len(t) != 2:
+                raise ValueError("%s line %d: expected two genes" % (path, n))
+            out.append((t[0], t[1]))
+    return out
 
 
 # ------------------------------------------------------------------------------------- census
@@ -437,6 +549,8 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [--consensus-limit=] <the most rows --consensus may write; default 10000000>
     [--quorum=] <TSV file: the --top eligible triples by their M-th best restart score>
     [--quorum-votes=] <M, an integer in [1, restarts]; default: all restarts (the minimum over them)>
+    [--allow-genes=] <file, one gene name or id per line: only triples of these genes>
+    [--block-pairs=] <file, two gene names or ids per line: no triple that contains such a pair>
 """
 
 
@@ -450,7 +564,8 @@ def parse(argv):
     # --network adds its three keys (network, network_threshold, network_limit, the latter two with
     # their defaults) only when one of its options is given: without them cfg is what it always was;
     # --consensus does the same with its four (consensus, consensus_threshold, min_votes,
-    # consensus_limit) and --quorum with its two (quorum, quorum_votes)
+    # consensus_limit) and --quorum with its two (quorum, quorum_votes); --allow-genes and
+    # --block-pairs add their two (allow_genes, block_pairs) when one of them is given
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
@@ -459,7 +574,8 @@ def parse(argv):
                                                         "pair-threshold=", "gene-census=", "network=",
                                                         "network-threshold=", "network-limit=", "consensus=",
                                                         "consensus-threshold=", "min-votes=",
-                                                        "consensus-limit=", "quorum=", "quorum-votes="])
+                                                        "consensus-limit=", "quorum=", "quorum-votes=",
+                                                        "allow-genes=", "block-pairs="])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -542,6 +658,10 @@ def parse(argv):
                     print("\n\nERROR: --quorum-votes should be an integer number in [1, restarts (-n)]")
                     raise cli.ArgError()
                 cfg["quorum_votes"] = int(arg)
+            elif opt == "--allow-genes":
+                cfg["allow_genes"] = arg
+            elif opt == "--block-pairs":
+                cfg["block_pairs"] = arg
             elif opt == "--thresholds":
                 try:
                     cfg["thresholds"] = parse_thresholds(arg)
@@ -584,6 +704,16 @@ def parse(argv):
         if cfg["quorum"] and cfg["best"]:
             print("\n\nERROR: --quorum ranks by a score across the restarts: it does not go with --best")
             raise cli.ArgError()
+    if any(key in cfg for key in ("allow_genes", "block_pairs")):
+        cfg.setdefault("allow_genes", None)
+        cfg.setdefault("block_pairs", None)
+        for on, name in ((cfg["genes"], "--gene"), (cfg["all_genes"], "--all-genes"), (cfg["pairs"], "--pairs"),
+                         (cfg["gene_census"], "--gene-census"), (cfg.get("consensus"), "--consensus"),
+                         (cfg.get("quorum"), "--quorum")):
+            if on:
+                print("\n\nERROR: --allow-genes / --block-pairs restrict the main table, --census and --network: "
+                      "they do not go with %s, whose kernel takes no pair mask" % name)
+                raise cli.ArgError()
     if cfg["genes"] and cfg["all_genes"]:
         print("\n\nERROR: --gene and --all-genes exclude each other")
         raise cli.ArgError()
@@ -610,12 +740,40 @@ def partner_queries(model, cfg):
         raise cli.ArgError()
 
 
-def census_tables(eng, model, cfg, known, sample, extras):
+def driver_mask(model, cfg):
+    """The driver's pair mask from --allow-genes / --block-pairs (None without them); cli.ArgError
+    on a file that does not read or a gene the fold does not hold."""
+    from . import cli
+    if not (cfg.get("allow_genes") or cfg.get("block_pairs")):
+        return None
+    try:
+        genes = pairs = None
+        if cfg.get("allow_genes"):
+            genes = resolve_genes(model, read_allow_genes(cfg["allow_genes"]))
+        if cfg.get("block_pairs"):
+            tokens = read_block_pairs(cfg["block_pairs"])
+            flat = resolve_genes(model, [t for pair in tokens for t in pair])
+            pairs = np.asarray(flat, dtype=np.int64).reshape(-1, 2)
+        return pair_mask(model.P, pairs=pairs, genes=genes)
+    except (KeyError, IndexError) as e:
+        print("\n\nERROR: --allow-genes / --block-pairs: unknown gene %s" % (e,))
+    except (OSError, ValueError) as e:
+        print("\n\nERROR: --allow-genes / --block-pairs: %s" % (e,))
+    raise cli.ArgError()
+
+
+def _masked(mask):
+    """The mask keyword of an engine call: nothing without a mask, so the unmasked calls are made
+    as they always were."""
+    return {} if mask is None else {"mask": mask}
+
+
+def census_tables(eng, model, cfg, known, sample, extras, mask=None):
     """The driver's --census and --heldout-ranks tables into `extras` (see run); `known`: the
-    keys --exclude names."""
+    keys --exclude names; `mask`: the pair mask of --allow-genes / --block-pairs (the census only)."""
     if cfg.get("census"):
         thresholds = sorted(cfg.get("thresholds") or DEFAULT_THRESHOLDS, reverse=True)
-        counts, total = eng.census(thresholds, known, sample)
+        counts, total = eng.census(thresholds, known, sample, **_masked(mask))
         extras["census"] = (thresholds, [int(c) for c in counts], total)
     if cfg.get("heldout_ranks"):
         ids, link_counts = model._link_arrays(1)
@@ -634,14 +792,15 @@ def pair_tables(eng, model, cfg, known, sample, extras):
         extras["gene_census"] = (thresholds, [model.id_gene[g] for g in range(model.P)], counts)
 
 
-def network_table(eng, model, cfg, known, sample, extras):
+def network_table(eng, model, cfg, known, sample, extras, mask=None):
     """The driver's --network table into `extras` (see run); cli.ArgError when it would hold more
     rows than --network-limit."""
     from . import cli
     if not cfg.get("network"):
         return
     try:
-        scores, ids = eng.scan_above(cfg["network_threshold"], known, sample, limit=cfg["network_limit"])
+        scores, ids = eng.scan_above(cfg["network_threshold"], known, sample, limit=cfg["network_limit"],
+                                     **_masked(mask))
     except LimitError as e:
         eng.close()
         print("\n\nERROR: --network: %d triples have a probability of %r or more, above --network-limit %d: "
@@ -718,6 +877,7 @@ def run(cfg, out=print, extras=None):
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
     queries = partner_queries(model, cfg)     # before anything touches a GPU
+    mask = driver_mask(model, cfg)
     from . import _lib
     from .engine import EMEngine
     from .restarts import stream_states
@@ -732,9 +892,9 @@ def run(cfg, out=print, extras=None):
     sample = int(np.argmax(eng.loglik(_lib.SET_TRAIN))) if cfg["best"] else None
     known = known_keys(model, cfg["exclude"])
     if extras is not None:
-        census_tables(eng, model, cfg, known, sample, extras)
+        census_tables(eng, model, cfg, known, sample, extras, mask)
         pair_tables(eng, model, cfg, known, sample, extras)
-        network_table(eng, model, cfg, known, sample, extras)
+        network_table(eng, model, cfg, known, sample, extras, mask)
         consensus_table(eng, model, cfg, known, extras)
         quorum_table(eng, model, cfg, known, extras)
     if queries is not None:
@@ -747,7 +907,10 @@ def run(cfg, out=print, extras=None):
                 for g, (scores, ids) in zip(queries, lists) for i, (p, row) in enumerate(zip(scores, ids))]
     out("scanning %d genes: %s" % (model.P, "sample %d" % sample if sample is not None
                                    else "mean of %d samples" % B))
-    scores, ids = eng.scan_top(cfg["top"], known, sample)
+    if mask is not None:    # the top-N kernel takes no mask: masked censuses and the masked threshold scan
+        scores, ids = eng.scan_top_any(cfg["top"], known, sample, mask=mask)
+    else:
+        scores, ids = eng.scan_top(cfg["top"], known, sample)
     eng.close()
     return network_rows(model.id_gene, scores, ids)
 
