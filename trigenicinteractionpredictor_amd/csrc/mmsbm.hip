@@ -222,7 +222,8 @@ __device__ __forceinline__ double dpp(double v) {
 }
 
 // Sum over the 16 lanes of a row; every lane gets the same bits (each step adds a lane pair
-// that is symmetric under the step's permutation).
+// that is symmetric under the step's permutation) unless the argument is a product that the
+// compiler contracts into step 1 (row16_pair below).
 // n / d by v_rcp_f64 and two Newton steps plus a residual correction (within an ulp or two of the
 // IEEE quotient; d > 0 here): 8 FP64 instructions instead of the IEEE division's 11 (scale / fixup
 // sequence), in the chunk loops of sk.h and (round 5: pass A -0.6 % at K=30, -1 % at K=20 x 8,
@@ -241,6 +242,34 @@ __device__ __forceinline__ double row16_sum(double v) {
   v += dpp<0x141>(v);
   v += dpp<0x140>(v);
   return v;
+}
+
+// row16_sum(a * b) for several vectors in one butterfly (sk_pass_kernel, phase 1), to the bits
+// that row16_sum(a * b) stores.  The compiler contracts row16_sum's first step into an fma, so a
+// lane adds its own unrounded product to its neighbour's rounded one and the two lanes of a pair
+// differ in the last bit; steps 2-4 are plain adds of operands that commute.  The 16 lanes of a
+// row therefore end with two values: one in the lanes whose position in the quad, mirrored in
+// quads 1 and 3, is even (0, 2, 5, 7, 8, 10, 13, 15: the first and the last lane of the row, so
+// the word that 16 lanes storing to one address leave), the other in the rest.  Only the first
+// set is wanted, and after step 1 each further step needs half the lanes of the one before:
+//   row16_pair   step 1 of one vector, written out as that fma;
+//   row16_merge  one later step for two vectors: lanes with k clear form x's sum, lanes with k
+//                set y's (CTRL pairs a lane with one of the other k), so the steps after it run
+//                once for both.
+__device__ __forceinline__ double row16_pair(double a, double b) {
+  return fma(a, b, dpp<0xB1>(a * b));
+}
+template <int CTRL>
+__device__ __forceinline__ double row16_merge(double x, double y, bool k) {
+  return (k ? y : x) + dpp<CTRL>(k ? x : y);
+}
+
+// A register pair as it stands (no instruction): the value of a variable that is read only
+// where nothing depends on it.
+__device__ __forceinline__ double any_bits() {
+  double x;
+  asm volatile("" : "=v"(x));  // (volatile: one pair per use, so none is copied)
+  return x;
 }
 
 enum { PASS_A = 0, PASS_LL = 1, PASS_B = 2 };  // (PASS_B: the small-K family's stream-1/2 pass)

@@ -314,6 +314,17 @@ __global__ __launch_bounds__(NT, 4) void sk_pass_kernel(
 #pragma unroll
       for (int hs = 0; hs < NG; ++hs) vb[hs] = smem[voff[hs] + tv_ * vstr[hs]];
     };
+    // The d sums of DG = 4 chunks share one butterfly (row16_merge, mmsbm.hip; two chunks would
+    // save less, and four fit the 128 VGPRs at every K and mode).  cm = the lane's position in its
+    // quad, mirrored in quads 1 and 3: the lanes with cm even hold the wanted sums, chunk + k2 of
+    // the pair from step 2 on and pair + k3 from step 3 on.  Those lanes store d at dw[4 q] for
+    // the group's first chunk q; the others put their word into the Z transpose (its first 8
+    // words + 4 q stay below the zeroed half), which the next chunk rewrites before it reads it.
+    constexpr int DG = 4;
+    static_assert(LC % DG == 0 && 7 + 4 * (LC - DG) < 64, "d groups of a block");
+    const int cm = col ^ ((col & 4) ? 3 : 0);
+    const bool k2 = (cm & 2) != 0, k3 = (((col >> 2) ^ (col >> 3)) & 1) != 0;
+    double* dw = (cm & 1) ? TRl + (col & 7) : DL + 4 * ((k2 ? 1 : 0) + (k3 ? 2 : 0)) + hi;
     int vt = 0;  // the running stretch (phase 1: its V operand)
     if constexpr (MODE != SK_B) load_v(0);
     for (int b0 = 0; b0 < c1; b0 += LC) {  // (uniform; one block for units of <= LC chunks)
@@ -341,29 +352,44 @@ __global__ __launch_bounds__(NT, 4) void sk_pass_kernel(
         // b >= K and h >= K), d = eps + sum_b theta_u[b] Z[b], parked at DL[4 q + obs] (one word per
         // observation = per lane of the wave).  A chunk past the end has zero theta (never used).
         // d by a DPP row sum per chunk (r03s same-box A/B: 38.2k iter/s vs 37.4k with the sum over b
-        // on MFMA, four chunks at a time)
+        // on MFMA, four chunks at a time); nothing reads d before the c batch, so steps 2-4 of the
+        // sum run once per DG chunks (row16_merge)
 #pragma unroll
-        for (int q = 0; q < LC; ++q) {
-          if (q < nb) {
-            // column swizzle c ^ 4 o (o = the observation row; r03u A/B: 38.5k vs 38.1k iter/s
-            // unswizzled): the compiler pairs the reads of hs = 0, 2 into ds_read2_b64, whose
-            // 16-lane groups bank on (a/4) mod 32, where the 4 rows (16 doubles apart) coincide;
-            // c ^ 4 o moves each row to its own 8 banks (round 3's c ^ 4 (o >> 1) left rows 0 / 1
-            // and 2 / 3 sharing: 56 % of the kernel's LDS conflict cycles,
-            // profiles/r05h_lds_attribution.txt)
-            TRl[16 * hi + (col ^ (4 * hi))] = gv[q];
-            wave_lds_sync();
-            double z = 0.0;
+        for (int q0 = 0; q0 < LC; q0 += DG) {
+          if (q0 < nb) {
+            // (a chunk past the unit's end leaves its dv as it is: its d words are rows >= 4 nb,
+            // which the c batch masks)
+            double dv[DG];
 #pragma unroll
-            for (int hs = 0; hs < NG; ++hs)
-              z = mfma4(TRl[16 * lo + ((4 * hs + hi) ^ (4 * lo))], vb[hs], z);
-            // (the 16 lanes of a row hold the same bits and store the same word; storing from one
-            // lane per row measured no faster, r03u)
-            DL[q * 4 + hi] = row16_sum(ga[q] * z) + eps;
-            if ((endm >> q) & 1u) {  // the next stretch's V operand
-              ++vt;
-              load_v(vt);
+            for (int j = 1; j < DG; ++j) dv[j] = any_bits();
+#pragma unroll
+            for (int j = 0; j < DG; ++j) {
+              const int q = q0 + j;
+              if (j == 0 || q < nb) {
+                // column swizzle c ^ 4 o (o = the observation row; r03u A/B: 38.5k vs 38.1k iter/s
+                // unswizzled): the compiler pairs the reads of hs = 0, 2 into ds_read2_b64, whose
+                // 16-lane groups bank on (a/4) mod 32, where the 4 rows (16 doubles apart)
+                // coincide; c ^ 4 o moves each row to its own 8 banks (round 3's c ^ 4 (o >> 1)
+                // left rows 0 / 1 and 2 / 3 sharing: 56 % of the kernel's LDS conflict cycles,
+                // profiles/r05h_lds_attribution.txt)
+                TRl[16 * hi + (col ^ (4 * hi))] = gv[q];
+                wave_lds_sync();
+                double z = 0.0;
+#pragma unroll
+                for (int hs = 0; hs < NG; ++hs)
+                  z = mfma4(TRl[16 * lo + ((4 * hs + hi) ^ (4 * lo))], vb[hs], z);
+                dv[j] = row16_pair(ga[q], z);
+                if ((endm >> q) & 1u) {  // the next stretch's V operand
+                  ++vt;
+                  load_v(vt);
+                }
+              }
             }
+            // lanes (k3, k2) of the wanted set hold d of chunk q0 + 2 k3 + k2
+            double v = row16_merge<0x141>(row16_merge<0x4E>(dv[0], dv[1], k2),
+                                          row16_merge<0x4E>(dv[2], dv[3], k2), k3);
+            v += dpp<0x140>(v);
+            dw[q0 * 4] = v + eps;
           }
         }
         wave_lds_sync();
