@@ -427,6 +427,52 @@ int mmsbm_scan_quorum_topn(mmsbm_ctx *ctx, const int32_t *order, const int64_t *
                            int32_t N, void *ws, int64_t ws_bytes, double *out_scores,
                            int32_t *out_ids, int64_t *out_count, void *stream);
 
+/* Pair-masked pair census, vote scan and quorum scan: mmsbm_pair_census, mmsbm_scan_votes and
+ * mmsbm_scan_quorum_topn with the pair mask of mmsbm_scan_census_masked behind n_known, under that
+ * call's contract word for word.  mask: device uint32[P16][MW] in RANK POSITIONS, as
+ * mmsbm_pair_mask_shape returns the shape; bit y & 31 of mask[x][y >> 5] set blocks the pair of rank
+ * positions (x, y); only x < y is ever read; the mask is the caller's and is only read.  A triple
+ * a < b < c is eligible when it is eligible for the unmasked call and none of (a, b), (a, c), (b, c)
+ * is blocked.
+ * Everything else is the unmasked call's: the arguments, the results (the pair matrix; out_hist, the
+ * always-full *out_count, the arrival-order rows of which only the SET is defined, no address at or
+ * past row `capacity` formed, rows from min(*out_count, capacity) on untouched; the quorum list under
+ * the scan's total order with its NaN / -1 tail), integer-only combination across lanes, the error
+ * codes, the grid and early-exit variables (MMSBM_PAIR_CENSUS_GRID, MMSBM_SCAN_VOTES_GRID,
+ * MMSBM_SCAN_QUORUM_GRID, MMSBM_SCAN_QUORUM_EARLY) and the workspaces: the unmasked
+ * mmsbm_pair_census_workspace_bytes, mmsbm_scan_votes_workspace_bytes and
+ * mmsbm_scan_quorum_workspace_bytes size them, and none has grown.  The score phase is not touched: a
+ * row's score, a slot's vote and q_m carry the bits the unmasked family gives that triple, so a masked
+ * call with an all-zero mask returns what the unmasked call returns, and a masked call returns what
+ * the unmasked call returns with the keys of every triple that contains a blocked pair added to
+ * `known`.  What follows from that definition:
+ *   - a blocked pair's row out_counts[x][y][.] of the pair matrix is zero (no eligible triple holds
+ *     it), and for every m the sum of out_counts[x][y][m] over x < y is still three times
+ *     mmsbm_scan_census_masked's count at thresholds[m] under the same mask;
+ *   - out_hist sums to mmsbm_scan_census_masked's total (out_counts[M]) under the same mask;
+ *   - votes >= m at threshold t exactly when the masked q_m >= t: mmsbm_scan_votes_masked's hits at
+ *     (t, m) are the masked-eligible triples with q_m >= t, and the masked quorum list is the exact
+ *     top N of q_m over the masked-eligible triples: its pruning bounds, the seeding pass's included,
+ *     are formed from masked-eligible candidates only.
+ * P <= 16384 (a row of bits is at most 2 KiB of LDS, the mask 32 MiB); above it the three calls
+ * return MMSBM_ERR_UNSUPPORTED.  A NULL mask is MMSBM_ERR_INVALID: the unmasked call exists for that.
+ * All checks come before any device call.  Replaces nothing in the reference. */
+int mmsbm_pair_census_masked(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known,
+                             int64_t n_known, const uint32_t *mask, const double *theta,
+                             const double *pr, int32_t sample, const double *thresholds, int32_t M,
+                             void *ws, int64_t ws_bytes, int32_t *out_counts, void *stream);
+int mmsbm_scan_votes_masked(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known,
+                            int64_t n_known, const uint32_t *mask, const double *theta,
+                            const double *pr, int32_t sample, double threshold, int32_t min_votes,
+                            int64_t capacity, void *ws, int64_t ws_bytes, int64_t *out_hist,
+                            double *out_scores, int64_t *out_keys, int32_t *out_votes,
+                            int64_t *out_count, void *stream);
+int mmsbm_scan_quorum_topn_masked(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known,
+                                  int64_t n_known, const uint32_t *mask, const double *theta,
+                                  const double *pr, int32_t sample, int32_t min_votes, int32_t N,
+                                  void *ws, int64_t ws_bytes, double *out_scores, int32_t *out_ids,
+                                  int64_t *out_count, void *stream);
+
 /* Link-sharded iteration (single sample over N ranks): each rank's context
  * holds 1/N of the train links (mmsbm_set_links) and the GLOBAL degree (mmsbm_set_degree).
  * Step 1, the accumulation half of make_iteration (:986-1012) over this rank's links:

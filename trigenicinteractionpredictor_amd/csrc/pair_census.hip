@@ -64,6 +64,19 @@ struct PairArgs {
   int K, P, P16, ns, M, WB;
 };
 
+// The masked pair census (mmsbm_pair_census_masked): the pair mask travels in the masked kernels' own
+// argument struct, flat as PairArgs is, so PairArgs and the unmasked kernels are what they were.
+struct PairMaskedArgs {
+  const double* thT;
+  const double* T;
+  const long long* known;
+  long long n_known;
+  const double* thresholds;
+  int* out;
+  const unsigned* mask;     // [P16][MW] (include/mmsbm.h, mmsbm_pair_mask_shape)
+  int K, P, P16, ns, M, WB, MW;
+};
+
 __device__ __forceinline__ void add(int* p, int v) {
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -72,8 +85,10 @@ __device__ __forceinline__ void add(int* p, int v) {
 // so that neither path holds the other's registers: one kernel for both took 132 VGPRs at
 // K = 10 against the census's 120, which leaves 3 workgroups per CU of the 4 the grid is sized for;
 // split, the single-sample kernel takes 108 and the ensemble's 120.
-template <int KS, bool ENS>
-__global__ __launch_bounds__(NT) void pair_census_kernel(PairArgs A) {
+// The body of both kernels; MASK: Args is PairMaskedArgs and row a of the mask lies behind the
+// thresholds in LDS.  A blocked element has left el before the binning sees it, so the binning is one.
+template <int KS, bool ENS, bool MASK, class Args>
+__device__ __forceinline__ void pair_census_body(const Args& A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Head* st = reinterpret_cast<Head*>(smem);
   double* W = reinterpret_cast<double*>(smem + sizeof(Head));
@@ -89,7 +104,7 @@ __global__ __launch_bounds__(NT) void pair_census_kernel(PairArgs A) {
   const double thr0 = A.thresholds[0];  // M >= 1
   int* const out = A.out;
 
-  sweep<KS, ENS>(S, st, W, bm, [&](int a, int b0) {
+  auto begin_item = [&](int a, int b0) {
     // once per item, not per tile with hits: the 64-bit product stays out of the binning
     const size_t rowa = (size_t)a * P;  // out[a][.][.]
     // Bin one finished tile.
@@ -121,7 +136,21 @@ __global__ __launch_bounds__(NT) void pair_census_kernel(PairArgs A) {
         if (kk == 0 && col) add(&out[(rowa + c) * M + t], col);  // (a, c): col > 0 only where c < P
       }
     };
-  });
+  };
+  if constexpr (MASK)
+    sweep_masked<KS, ENS>(S, st, W, bm, A.mask, A.MW, reinterpret_cast<unsigned*>(thr + PAIR_MAX_M), begin_item);
+  else
+    sweep<KS, ENS>(S, st, W, bm, begin_item);
+}
+
+template <int KS, bool ENS>
+__global__ __launch_bounds__(NT) void pair_census_kernel(PairArgs A) {
+  pair_census_body<KS, ENS, false>(A);
+}
+
+template <int KS, bool ENS>
+__global__ __launch_bounds__(NT) void pair_census_masked_kernel(PairMaskedArgs A) {
+  pair_census_body<KS, ENS, true>(A);
 }
 
 struct PairPlan {
@@ -143,6 +172,51 @@ int make_plan(const mmsbm_ctx* c, int M, PairPlan* p) {
   return MMSBM_OK;
 }
 
+// Both entry points; `masked`: mmsbm_pair_census_masked, whose mask must not be null.
+int pair_census_call(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known, const uint32_t* mask,
+                     bool masked, const double* theta, const double* pr, int32_t sample, const double* thresholds,
+                     int32_t M, void* ws, int64_t ws_bytes, int32_t* out_counts, void* stream) {
+  if (!c) return fail(MMSBM_ERR_INVALID, "null context");
+  PairPlan p;
+  int rc = make_plan(c, M, &p);
+  if (rc) return rc;
+  const ScanShape& sh = p.sh;
+  if (!order || !theta || !pr || (M > 0 && (!thresholds || !out_counts)))
+    return fail(MMSBM_ERR_INVALID, "null pointer");
+  int MW = 0;
+  if (masked && (rc = check_pair_mask(sh, "pair census", mask, &MW))) return rc;
+  int ns, s0, WB;
+  size_t w_bytes;
+  if ((rc = check_call(sh, "pair census", "mmsbm_pair_census_workspace_bytes", known, n_known, sample, ws, ws_bytes,
+                       p.total, &ns, &s0)))
+    return rc;
+  if ((rc = pick_wb(sh, "pair census", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
+  if (M == 0) return MMSBM_OK;  // an empty matrix
+  const int lds = (int)(sizeof(Head) + w_bytes + sizeof(unsigned) * (BM_WORDS + MW) + sizeof(double) * PAIR_MAX_M);
+  const int G = sweep_grid(sh, WB, "MMSBM_PAIR_CENSUS_GRID");
+
+  DeviceGuard g(sh.device);
+  hipStream_t s = (hipStream_t)stream;
+  char* w = (char*)ws;
+  HIP_TRY(hipMemsetAsync(out_counts, 0, sizeof(int32_t) * (size_t)sh.P * sh.P * M, s));
+  if (sh.P < 3) return MMSBM_OK;
+  scan_prep_kernel<<<dim3(sh.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
+                                                   (double*)(w + p.off_T), sh.K, sh.KP, sh.R, sh.P, sh.P16, s0);
+  HIP_TRY(hipGetLastError());
+  const PairArgs a{(const double*)(w + p.off_thT), (const double*)(w + p.off_T), (const long long*)known, n_known,
+                   thresholds, out_counts, sh.K, sh.P, sh.P16, ns, M, WB};
+  const PairMaskedArgs am{a.thT, a.T,  a.known, n_known, thresholds, out_counts, mask,
+                          sh.K,  sh.P, sh.P16,  ns,      M,          WB,         MW};
+  return dispatch_ks(sh.KP / 4, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    if (masked)
+      return ns > 1 ? launch_lds(pair_census_masked_kernel<KS, true>, G, lds, s, am)
+                    : launch_lds(pair_census_masked_kernel<KS, false>, G, lds, s, am);
+    return ns > 1 ? launch_lds(pair_census_kernel<KS, true>, G, lds, s, a)
+                  : launch_lds(pair_census_kernel<KS, false>, G, lds, s, a);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -161,38 +235,16 @@ int mmsbm_pair_census_workspace_bytes(const mmsbm_ctx* c, int32_t M, int64_t* by
 int mmsbm_pair_census(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
                       const double* theta, const double* pr, int32_t sample, const double* thresholds,
                       int32_t M, void* ws, int64_t ws_bytes, int32_t* out_counts, void* stream) {
-  if (!c) return fail(MMSBM_ERR_INVALID, "null context");
-  PairPlan p;
-  int rc = make_plan(c, M, &p);
-  if (rc) return rc;
-  const ScanShape& sh = p.sh;
-  if (!order || !theta || !pr || (M > 0 && (!thresholds || !out_counts)))
-    return fail(MMSBM_ERR_INVALID, "null pointer");
-  int ns, s0, WB;
-  size_t w_bytes;
-  if ((rc = check_call(sh, "pair census", "mmsbm_pair_census_workspace_bytes", known, n_known, sample, ws, ws_bytes,
-                       p.total, &ns, &s0)))
-    return rc;
-  if ((rc = pick_wb(sh, "pair census", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
-  if (M == 0) return MMSBM_OK;  // an empty matrix
-  const int lds = (int)(sizeof(Head) + w_bytes + sizeof(unsigned) * BM_WORDS + sizeof(double) * PAIR_MAX_M);
-  const int G = sweep_grid(sh, WB, "MMSBM_PAIR_CENSUS_GRID");
+  return pair_census_call(c, order, known, n_known, nullptr, false, theta, pr, sample, thresholds, M, ws, ws_bytes,
+                          out_counts, stream);
+}
 
-  DeviceGuard g(sh.device);
-  hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  HIP_TRY(hipMemsetAsync(out_counts, 0, sizeof(int32_t) * (size_t)sh.P * sh.P * M, s));
-  if (sh.P < 3) return MMSBM_OK;
-  scan_prep_kernel<<<dim3(sh.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
-                                                   (double*)(w + p.off_T), sh.K, sh.KP, sh.R, sh.P, sh.P16, s0);
-  HIP_TRY(hipGetLastError());
-  const PairArgs a{(const double*)(w + p.off_thT), (const double*)(w + p.off_T), (const long long*)known, n_known,
-                   thresholds, out_counts, sh.K, sh.P, sh.P16, ns, M, WB};
-  return dispatch_ks(sh.KP / 4, [&](auto ks) {
-    constexpr int KS = decltype(ks)::value;
-    return ns > 1 ? launch_lds(pair_census_kernel<KS, true>, G, lds, s, a)
-                  : launch_lds(pair_census_kernel<KS, false>, G, lds, s, a);
-  });
+int mmsbm_pair_census_masked(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
+                             const uint32_t* mask, const double* theta, const double* pr, int32_t sample,
+                             const double* thresholds, int32_t M, void* ws, int64_t ws_bytes, int32_t* out_counts,
+                             void* stream) {
+  return pair_census_call(c, order, known, n_known, mask, true, theta, pr, sample, thresholds, M, ws, ws_bytes,
+                          out_counts, stream);
 }
 
 }  // extern "C"

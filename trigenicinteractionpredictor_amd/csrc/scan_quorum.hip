@@ -195,6 +195,190 @@ __global__ __launch_bounds__(NT) void scan_quorum_kernel(QuorumArgs A) {
   if (threadIdx.x == 0) A.list_n[blockIdx.x] = cnt;
 }
 
+// The masked quorum scan (mmsbm_scan_quorum_topn_masked): the pair mask travels in the masked
+// kernels' own argument struct, so QuorumArgs and the unmasked kernels are what they were.
+struct QuorumMaskedArgs : QuorumArgs {
+  const unsigned* mask;  // [P16][MW] (include/mmsbm.h, mmsbm_pair_mask_shape)
+  int MW;
+};
+
+// scan_quorum_kernel's masked twin, restated and not a shared body: with the body shared, however the
+// mask's parts were compiled out, the unmasked instantiations came out with other scalar spill counts
+// (and D = 0 at K > 20 with other vector registers) than they have had.
+//
+// A triple is eligible only if none of its three pairs is set in the pair mask, as in scan_sweep.h
+// (whose tests are restated here: this kernel does not sweep through it).  Per item the workgroup
+// reads the bits (a, the item's rows) and skips the item when every row b with a < b < P is
+// blocked, before the barrier, the known-key search and fill_w;
+// otherwise row a goes to LDS behind W (MW words, rounded up to 2 so that the candidate buffer stays
+// 8-byte aligned).  Per tile the (a, c) bits are halfword ct of that row: at 0xFFFF neither the slot
+// loop nor the selection runs.  The (b, c) halfwords of the lane's four rows are loaded one tile
+// ahead (and again for a tile that is redone) and the blocked bits are folded into pass[i], so no
+// blocked triple ever enters a candidate buffer: the workgroup's N-th best and the published bound,
+// the seeding pass's included, are formed from masked-eligible candidates only and stay lower
+// bounds of the masked N-th best.  The early exit and the cut ballot look at scores alone: pure
+// pruning, as without a mask.
+template <int KS, int D, bool SMALL>
+__global__ __launch_bounds__(NT) void scan_quorum_masked_kernel(QuorumMaskedArgs A) {
+  using Sc = Score<KS>;
+  constexpr int WS = Sc::WS;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  Sel* st = reinterpret_cast<Sel*>(smem);
+  double* W = reinterpret_cast<double*>(smem + sizeof(Sel));
+  const int RB = 16 * A.WB;
+  const int P = A.P, P16 = A.P16, K = A.K, ns = A.ns;
+  double* lcs = W + (size_t)ns * RB * WS;  // the candidate buffer when it is in LDS
+  unsigned* mrow = reinterpret_cast<unsigned*>(lcs);  // row a of the mask, before the candidate buffer
+  lcs += (A.MW + 1) >> 1;
+  long long* lck = reinterpret_cast<long long*>(lcs + A.cap);
+  double* cs = lcs;
+  long long* ck = lck;
+  if (A.cand_s) {
+    cs = A.cand_s + (size_t)blockIdx.x * A.cap;
+    ck = A.cand_k + (size_t)blockIdx.x * A.cap;
+  }
+  auto keep_best = [&]() {
+    if (A.cand_s) wg_keep_best(st, cs, ck, A.N, A.shared);
+    else wg_keep_best(st, lcs, lck, A.N, A.shared);
+  };
+  if (threadIdx.x == 0) sel_init(st);
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = lane & 15, kk = lane >> 4;
+  const int wb = wave % A.WB, wc = wave / A.WB, CW = 4 / A.WB;
+  const int nct = P16 / 16;
+  const int nbq = (P + RB - 1) / RB;
+  const long long PP = (long long)P;
+
+  for (long long q = (long long)blockIdx.x * A.stride; q < PP * nbq; q += (long long)gridDim.x * A.stride) {
+    const int a = (int)(q / nbq), bq = (int)(q % nbq);
+    if (a >= P - 2 || bq * RB + RB - 1 <= a || bq * RB >= P - 1) continue;  // no a < b < c here
+    {
+      // the (a, b) bits of the item's rows: RB = 16, 32 or 64 bits from bit bq RB of row a on
+      const int MW = A.MW, r0 = bq * RB, w0 = r0 >> 5;
+      const unsigned* __restrict__ ra = A.mask + (size_t)a * MW;
+      unsigned long long bits = (unsigned long long)ra[w0] >> (r0 & 31);  // w0 < MW: r0 < P - 1
+      if (RB == 64 && w0 + 1 < MW) bits |= (unsigned long long)ra[w0 + 1] << 32;
+      const int lo = max(a + 1, r0) - r0, hi = min(P, r0 + RB) - r0;  // 0 <= lo < hi <= RB, bits inside row a
+      const unsigned long long need = (hi >= 64 ? ~0ull : (1ull << hi) - 1) & ~((1ull << lo) - 1);
+      if ((bits & need) == need) continue;  // workgroup-uniform: every pair (a, b) of the item is blocked
+    }
+    __syncthreads();  // the previous item's W (and mask row) is read
+    for (int i = threadIdx.x; i < A.MW; i += NT) mrow[i] = A.mask[(size_t)a * A.MW + i];
+    if (threadIdx.x == 0) {
+      const unsigned long long g = __hip_atomic_load(A.shared, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      st->gthr = g ? __longlong_as_double((long long)g) : neg_inf();
+    }
+    if (threadIdx.x == 64 && A.n_known > 0) {  // the known keys whose first gene is a
+      st->klo = lower_bound(A.known, 0, A.n_known, (long long)a * PP * PP);
+      st->khi = lower_bound(A.known, st->klo, A.n_known, (long long)(a + 1) * PP * PP);
+    }
+    Sc::fill_w(W, A.T, A.thT, a, bq, RB, ns, K, P, P16);
+    __syncthreads();
+
+    const int btile = bq * A.WB + wb, b0 = btile * 16;
+    const bool wave_on = b0 < P - 1 && b0 + 15 > a;
+    double areg[KS];
+    if (D == 0 && wave_on) Sc::load_a(areg, W, wb, m, kk);
+    int ct = bq * A.WB + wc;
+    while (ct < btile) ct += CW;  // every c of those tiles is below every b
+    const long long klo = st->klo, khi = st->khi;
+    unsigned abm = 0;                // bit i: the pair (a, b0 + kk + 4 i) is blocked
+    unsigned bcn[4] = {0, 0, 0, 0};  // the next tile's (b, c) halfwords, in flight
+    const unsigned short* mrow16 = reinterpret_cast<const unsigned short*>(mrow);
+    // halfword ct of mask rows b0 + kk + 4 i: inside the mask for a wave that is on (rows <= b0 + 15 <
+    // P16, halfwords ct < P16 / 16 <= 2 MW)
+    const unsigned bc_off = (unsigned)(b0 + kk) * (unsigned)A.MW * 4u;
+    auto load_bc = [&](unsigned (&h)[4], int ct) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        h[i] = *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(A.mask) +
+                                                        (size_t)(16 * i) * A.MW + (bc_off + 2u * (unsigned)ct));
+    };
+    if (wave_on) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + kk + 4 * i;
+        abm |= ((mrow[b >> 5] >> (b & 31)) & 1u) << i;
+      }
+    }
+    for (;;) {
+      // the thresholds change only when the workgroup sorts its buffer (behind a barrier)
+      const double thr_s = st->thr_s, gthr = st->gthr;
+      const long long thr_k = st->thr_k;
+      const double cut = fmax(thr_s, gthr);
+      if (wave_on) {
+        double bnext[KS];  // single slot: the next tile's Th' operand is in flight
+        if (D == 0 && ct < nct) Sc::load_b(bnext, A.thT, P16, ct * 16, m, kk);
+        if (ct < nct) load_bc(bcn, ct);  // also for a tile that is redone
+        for (; ct < nct; ct += CW) {
+          const int c0 = ct * 16;
+          d4v tot;
+          const unsigned ac = mrow16[ct];
+          const bool dead = ac == 0xFFFFu;  // every pair (a, c) of the tile is blocked (wave-uniform)
+          unsigned blk = abm | (((ac >> m) & 1u) ? 0xFu : 0u);  // bit i: element i of the tile is blocked
+#pragma unroll
+          for (int i = 0; i < 4; ++i) blk |= ((bcn[i] >> m) & 1u) << i;
+          if (ct + CW < nct) load_bc(bcn, ct + CW);
+          if constexpr (D == 0) {
+            double bcur[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) bcur[ks] = bnext[ks];
+            if (ct + CW < nct) Sc::load_b(bnext, A.thT, P16, c0 + 16 * CW, m, kk);
+            if (dead) continue;
+            tot = Sc::tile_one(areg, bcur);
+          } else {
+            if (dead) continue;  // no slot loop, no selection
+            // false: no element can reach cut (left the slot loop early, wave-uniform)
+            if (!Sc::template tile_quorum<D, SMALL>(W, A.thT, ns, RB, P16, wb, c0, m, kk, cut, A.first, tot))
+              continue;
+          }
+          // lane holds q[b0 + kk + 4 i][c0 + m]; from here on scan_kernel's selection
+          if (!__ballot(tot[0] >= cut || tot[1] >= cut || tot[2] >= cut || tot[3] >= cut)) continue;
+          const int c = c0 + m;
+          bool pass[4];
+          long long key[4];
+          unsigned long long mk[4];
+          int n = 0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int b = b0 + kk + 4 * i;
+            key[i] = ((long long)a * PP + b) * PP + c;
+            pass[i] = a < b && b < c && c < P && !(tot[i] < gthr) && before(tot[i], key[i], thr_s, thr_k);
+            pass[i] = pass[i] && !((blk >> i) & 1u);
+            if (pass[i] && khi > klo) pass[i] = !is_known(A.known, klo, khi, key[i]);
+            mk[i] = __ballot(pass[i]);
+            n += __popcll(mk[i]);
+          }
+          if (!n) continue;
+          int pos = wave_reserve(st, n, A.cap);
+          if (pos < 0) break;  // the tile is redone after the workgroup made room
+          const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (pass[i]) {
+              const int at = pos + __popcll(mk[i] & below);
+              cs[at] = tot[i];
+              ck[at] = key[i];
+            }
+            pos += __popcll(mk[i]);
+          }
+        }
+      }
+      __syncthreads();
+      if (!st->overflow) break;
+      keep_best();
+    }
+  }
+  keep_best();
+  const int cnt = st->count;
+  for (int i = threadIdx.x; i < cnt; i += NT) {
+    A.list_s[(size_t)blockIdx.x * A.N + i] = cs[i];
+    A.list_k[(size_t)blockIdx.x * A.N + i] = ck[i];
+  }
+  if (threadIdx.x == 0) A.list_n[blockIdx.x] = cnt;
+}
+
 // ------------------------------------------------------------------------------------------
 // Merge, as scan.hip's scan_merge_kernel: workgroup w keeps the best N of lists [FAN w, FAN (w + 1));
 // the last level (one workgroup) writes the result: scores, gene ids in key order, count, NaN / -1
@@ -303,25 +487,11 @@ int dispatch_depth(int d, F&& f) {
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-int mmsbm_scan_quorum_max_depth(void) { return QUORUM_MAX_DEPTH; }
-
-int mmsbm_scan_quorum_workspace_bytes(const mmsbm_ctx* c, int32_t N, int64_t* bytes) {
-  if (!c || !bytes) return fail(MMSBM_ERR_INVALID, "null argument");
-  QuorumPlan p;
-  int rc = make_plan(c, N, &p);
-  if (rc) return rc;
-  *bytes = (int64_t)p.total;
-  return MMSBM_OK;
-}
-
-int mmsbm_scan_quorum_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
-                           const double* theta, const double* pr, int32_t sample, int32_t min_votes, int32_t N,
-                           void* ws, int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count,
-                           void* stream) {
+// Both entry points; `masked`: mmsbm_scan_quorum_topn_masked, whose mask must not be null.
+int quorum_call(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known, const uint32_t* mask,
+                bool masked, const double* theta, const double* pr, int32_t sample, int32_t min_votes, int32_t N,
+                void* ws, int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count,
+                void* stream) {
   if (!c) return fail(MMSBM_ERR_INVALID, "null context");
   QuorumPlan p;
   int rc = make_plan(c, N, &p);
@@ -329,6 +499,8 @@ int mmsbm_scan_quorum_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* kn
   if (!order || !theta || !pr || !out_scores || !out_ids || !out_count)
     return fail(MMSBM_ERR_INVALID, "null pointer");
   const ScanShape& sh = p.sh;
+  int MW = 0;
+  if (masked && (rc = check_pair_mask(sh, "the quorum scan", mask, &MW))) return rc;
   int ns, s0, WB;
   size_t w_bytes;
   if ((rc = check_call(sh, "the quorum scan", "mmsbm_scan_quorum_workspace_bytes", known, n_known, sample, ws,
@@ -346,8 +518,10 @@ int mmsbm_scan_quorum_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* kn
                 min_votes, ns, depth, QUORUM_MAX_DEPTH);
   if ((rc = pick_wb(sh, "the quorum scan", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
   const size_t cand_bytes = (size_t)p.cap * 16;
-  const bool cand_lds = sizeof(Sel) + w_bytes + cand_bytes <= (size_t)LDS_MAX;
-  const int lds = (int)(sizeof(Sel) + w_bytes + (cand_lds ? cand_bytes : 0));
+  // the masked kernel's mask row may move the candidate buffer to the workspace, which holds it anyway
+  const size_t mrow_bytes = sizeof(unsigned) * (size_t)((MW + 1) & ~1);
+  const bool cand_lds = sizeof(Sel) + w_bytes + mrow_bytes + cand_bytes <= (size_t)LDS_MAX;
+  const int lds = (int)(sizeof(Sel) + w_bytes + mrow_bytes + (cand_lds ? cand_bytes : 0));
   const int merge_lds = (int)(sizeof(Sel) + cand_bytes);
   const bool early = env_override("MMSBM_SCAN_QUORUM_EARLY", 1) != 0;  // measurement
   // measurement: fewer workgroups than planned (the lists and buffers are sized for p.G)
@@ -387,9 +561,16 @@ int mmsbm_scan_quorum_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* kn
       a.first = early ? ns - min_votes : ns;
       a.stride = seeding ? SEED_STRIDE : 1;
       n_lists = seeding ? std::min(G, sh.ncu) : G;
+      QuorumMaskedArgs am{};
+      static_cast<QuorumArgs&>(am) = a;
+      am.mask = mask, am.MW = MW;
       rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
         return dispatch_depth(ns > 1 ? depth : 0, [&](auto d) {
           constexpr int KS = decltype(ks)::value, D = decltype(d)::value;
+          if (masked) {
+            if (D > 0 && smallest) return launch_lds(scan_quorum_masked_kernel<KS, D, D != 0>, n_lists, lds, s, am);
+            return launch_lds(scan_quorum_masked_kernel<KS, D, false>, n_lists, lds, s, am);
+          }
           if (D > 0 && smallest) return launch_lds(scan_quorum_kernel<KS, D, D != 0>, n_lists, lds, s, a);
           return launch_lds(scan_quorum_kernel<KS, D, false>, n_lists, lds, s, a);
         });
@@ -413,6 +594,36 @@ int mmsbm_scan_quorum_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* kn
     }
   }
   return MMSBM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mmsbm_scan_quorum_max_depth(void) { return QUORUM_MAX_DEPTH; }
+
+int mmsbm_scan_quorum_workspace_bytes(const mmsbm_ctx* c, int32_t N, int64_t* bytes) {
+  if (!c || !bytes) return fail(MMSBM_ERR_INVALID, "null argument");
+  QuorumPlan p;
+  int rc = make_plan(c, N, &p);
+  if (rc) return rc;
+  *bytes = (int64_t)p.total;
+  return MMSBM_OK;
+}
+
+int mmsbm_scan_quorum_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
+                           const double* theta, const double* pr, int32_t sample, int32_t min_votes, int32_t N,
+                           void* ws, int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count,
+                           void* stream) {
+  return quorum_call(c, order, known, n_known, nullptr, false, theta, pr, sample, min_votes, N, ws, ws_bytes,
+                     out_scores, out_ids, out_count, stream);
+}
+
+int mmsbm_scan_quorum_topn_masked(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
+                                  const uint32_t* mask, const double* theta, const double* pr, int32_t sample,
+                                  int32_t min_votes, int32_t N, void* ws, int64_t ws_bytes, double* out_scores,
+                                  int32_t* out_ids, int64_t* out_count, void* stream) {
+  return quorum_call(c, order, known, n_known, mask, true, theta, pr, sample, min_votes, N, ws, ws_bytes,
+                     out_scores, out_ids, out_count, stream);
 }
 
 }  // extern "C"

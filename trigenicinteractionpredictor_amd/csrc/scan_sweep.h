@@ -66,7 +66,8 @@ __device__ __forceinline__ void sweep_begin(Head* st) {
 // above vthr, for eligible and other elements alike.  sweep() itself is the instantiation without
 // it, which holds nothing of the votes.
 //
-// MASK (sweep_masked, for the masked census and threshold scan): a triple is eligible only if none of
+// MASK (sweep_masked, for the masked census, pair census and threshold scan; sweep_votes_masked with
+// VOTES, for the masked vote scan): a triple is eligible only if none of
 // its three pairs is set in the pair mask (include/mmsbm.h: mask[P16][MW] in rank positions, bit
 // y & 31 of mask[x][y >> 5] blocks the pair x < y).  Per item the workgroup first reads the bits
 // (a, the item's rows) through the scalar cache and skips the item when every row b with a < b < P is
@@ -221,6 +222,9 @@ __device__ __forceinline__ void sweep_impl(const SweepArgs& A, Head* st, double*
         }
         tot = Sc::tile_one(areg, bcur);
       } else if constexpr (VOTES) {
+        if constexpr (MASK) {
+          if (dead) continue;  // before tile_votes: votes and blk stay the finished tile's
+        }
         tot = Sc::tile_votes(W, A.thT, ns, RB, P16, wb, c0, m, kk, div, vthr, votes);
       } else {
         if constexpr (MASK) {
@@ -255,6 +259,15 @@ template <int KS, bool ENS, class BeginItem>
 __device__ __forceinline__ void sweep_masked(const SweepArgs& A, Head* st, double* W, unsigned* bm,
                                              const unsigned* mask, int MW, unsigned* mrow, BeginItem&& begin_item) {
   sweep_impl<KS, ENS, false, true>(A, st, W, bm, 0.0, mask, MW, mrow, static_cast<BeginItem&&>(begin_item));
+}
+
+// Both: the masked vote scan.  The votes byte and the blocked bits of a tile are kept and handed over
+// together, one tile late; a dead tile is left before tile_votes, so it touches neither.
+template <int KS, bool ENS, class BeginItem>
+__device__ __forceinline__ void sweep_votes_masked(const SweepArgs& A, Head* st, double* W, unsigned* bm, double vthr,
+                                                   const unsigned* mask, int MW, unsigned* mrow,
+                                                   BeginItem&& begin_item) {
+  sweep_impl<KS, ENS, true, true>(A, st, W, bm, vthr, mask, MW, mrow, static_cast<BeginItem&&>(begin_item));
 }
 
 }  // namespace scan_sweep

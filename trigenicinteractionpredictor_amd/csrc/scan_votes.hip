@@ -68,18 +68,21 @@ struct VotesArgs : SweepArgs {
   int* out_votes;       // [capacity]
 };
 
+// The masked vote scan (mmsbm_scan_votes_masked): the pair mask travels in the masked kernels' own
+// argument struct, so VotesArgs and the unmasked kernels are what they were.
+struct VotesMaskedArgs : VotesArgs {
+  const unsigned* mask;  // [P16][MW] (include/mmsbm.h, mmsbm_pair_mask_shape)
+  int MW;
+};
+
 constexpr int STAGE = 256;  // rows of a wave's staging buffer: the most one tile can hold
 constexpr int ROW_BYTES = (int)(sizeof(double) + sizeof(long long) + sizeof(int));
 constexpr int STAGE_BYTES = (NT / 64) * STAGE * ROW_BYTES;  // per workgroup: 20 KiB
 
-// The occupancy bounds are the threshold scan's (scan_above.hip), for its reasons: at most 4 waves
-// per SIMD, which sweep_grid's 4 workgroups per compute unit are sized for, and for the single
-// sample 4 as the floor too.  LIST: the call has rows to write (capacity > 0).  The histogram-only
-// call is the instantiation without the staging, which holds 11 to 35 registers fewer (the ensemble
-// of K = 13..16 and 25..28 then keeps 4 waves per SIMD where the listing kernel keeps 3).
-template <int KS, bool ENS, bool LIST>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENS ? 1 : 4, 4))) void scan_votes_kernel(
-    VotesArgs A) {
+// The body of both kernels; MASK: Args is VotesMaskedArgs and row a of the mask lies behind the
+// bitmap, before the staging buffers (MW rounded up to 2 words, so that they stay 8-byte aligned).
+template <int KS, bool ENS, bool LIST, bool MASK, class Args>
+__device__ __forceinline__ void scan_votes_body(const Args& A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Head* st = reinterpret_cast<Head*>(smem);
   double* W = reinterpret_cast<double*>(smem + sizeof(Head));
@@ -88,7 +91,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENS ? 1 : 4,
   unsigned* bm = reinterpret_cast<unsigned*>(cnt + ns + 1);                                // [BM_WORDS]
   // this wave's staging buffer: [STAGE] scores, [STAGE] keys, then [STAGE] votes.  The offset from
   // smem is a multiple of 8: Head 64, W and cnt whole doublewords, the bitmap 1 KiB, a wave 5 KiB.
-  char* stage = reinterpret_cast<char*>(bm + BM_WORDS) + (size_t)(threadIdx.x >> 6) * STAGE * ROW_BYTES;
+  int mrow_words = 0;
+  if constexpr (MASK) mrow_words = (A.MW + 1) & ~1;
+  char* stage =
+      reinterpret_cast<char*>(bm + BM_WORDS + mrow_words) + (size_t)(threadIdx.x >> 6) * STAGE * ROW_BYTES;
   double* ssc = reinterpret_cast<double*>(stage);
   long long* sky = reinterpret_cast<long long*>(ssc + STAGE);
   int* svt = reinterpret_cast<int*>(sky + STAGE);
@@ -125,7 +131,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENS ? 1 : 4,
     fill = 0;
   };
 
-  sweep_votes<KS, ENS>(A, st, W, bm, A.threshold, [&](int a, int b0) {
+  auto begin_item = [&](int a, int b0) {
     // once per item: the key of (a, b0, column 0), the same for the whole wave.  A lane adds its
     // (kk + 4 i) P + c < 16 P + P16 <= 3.4 10^7 (packed_keys_fit: P <= 2 10^6) in 32 bits.
     // b0 comes from the wave's index, which the compiler takes for a vector value: read back through
@@ -189,7 +195,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENS ? 1 : 4,
         }
       }
     };
-  });
+  };
+  if constexpr (MASK)
+    sweep_votes_masked<KS, ENS>(A, st, W, bm, A.threshold, A.mask, A.MW, bm + BM_WORDS, begin_item);
+  else
+    sweep_votes<KS, ENS>(A, st, W, bm, A.threshold, begin_item);
   if (LIST && fill) flush();  // wave-uniform
   if (zero && lane == 0) atomicAdd(&cnt[0], zero);
   __syncthreads();
@@ -197,6 +207,29 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENS ? 1 : 4,
     const count_t c = cnt[i];
     if (c) __hip_atomic_fetch_add(&A.hist[i], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+// The occupancy bounds are the threshold scan's (scan_above.hip), for its reasons: at most 4 waves
+// per SIMD, which sweep_grid's 4 workgroups per compute unit are sized for, and for the single
+// sample 4 as the floor too.  LIST: the call has rows to write (capacity > 0).  The histogram-only
+// call is the instantiation without the staging, which holds 11 to 35 registers fewer (the ensemble
+// of K = 13..16 and 25..28 then keeps 4 waves per SIMD where the listing kernel keeps 3).
+template <int KS, bool ENS, bool LIST>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENS ? 1 : 4, 4))) void scan_votes_kernel(
+    VotesArgs A) {
+  scan_votes_body<KS, ENS, LIST, false>(A);
+}
+
+// The masked single sample keeps the floor of 4 waves up to K = 16 only (the listing kernel, which
+// spilled one VGPR under it at K = 13..16: up to K = 12), as scan_above_masked_kernel does and for its
+// reason: above, the mask's registers do not fit 128 VGPRs beside the operands and
+// the floor would spill them; under the cap alone those kernels take a 3-wave budget and no scratch
+// (profiles/scan_masked_families_resources.txt).
+template <int KS, bool ENS, bool LIST>
+__global__ __launch_bounds__(NT)
+    __attribute__((amdgpu_waves_per_eu(ENS || KS > (LIST ? 3 : 4) ? 1 : 4, 4))) void scan_votes_masked_kernel(
+        VotesMaskedArgs A) {
+  scan_votes_body<KS, ENS, LIST, true>(A);
 }
 
 // The number of hits: the cursor of a listing call; a histogram-only call reserved no row, and its
@@ -229,6 +262,75 @@ int make_plan(const mmsbm_ctx* c, VotesPlan* p) {
   return MMSBM_OK;
 }
 
+// Both entry points; `masked`: mmsbm_scan_votes_masked, whose mask must not be null.
+int votes_call(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known, const uint32_t* mask,
+               bool masked, const double* theta, const double* pr, int32_t sample, double threshold,
+               int32_t min_votes, int64_t capacity, void* ws, int64_t ws_bytes, int64_t* out_hist,
+               double* out_scores, int64_t* out_keys, int32_t* out_votes, int64_t* out_count, void* stream) {
+  if (!c) return fail(MMSBM_ERR_INVALID, "null context");
+  VotesPlan p;
+  int rc = make_plan(c, &p);
+  if (rc) return rc;
+  const ScanShape& sh = p.sh;
+  if (!order || !theta || !pr || !out_hist || !out_count) return fail(MMSBM_ERR_INVALID, "null pointer");
+  if (!std::isfinite(threshold)) return fail(MMSBM_ERR_INVALID, "the threshold must be a finite number");
+  if (capacity < 0) return fail(MMSBM_ERR_INVALID, "capacity=%lld < 0", (long long)capacity);
+  if (capacity > 0 && (!out_scores || !out_keys || !out_votes))
+    return fail(MMSBM_ERR_INVALID, "null output array with capacity > 0");
+  int MW = 0;
+  if (masked && (rc = check_pair_mask(sh, "the vote scan", mask, &MW))) return rc;
+  int ns, s0, WB;
+  size_t w_bytes;
+  if ((rc = check_call(sh, "the vote scan", "mmsbm_scan_votes_workspace_bytes", known, n_known, sample, ws, ws_bytes,
+                       p.total, &ns, &s0)))
+    return rc;
+  if (min_votes < 1 || min_votes > ns)
+    return fail(MMSBM_ERR_INVALID, "min_votes=%d outside [1, %d], the scored slots", min_votes, ns);
+  if ((rc = pick_wb(sh, "the vote scan", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
+  const int mrow_words = (MW + 1) & ~1;  // the masked kernel's mask row, before the staging buffers
+  const int lds =
+      (int)(sizeof(Head) + w_bytes + sizeof(count_t) * (ns + 1) + sizeof(unsigned) * (BM_WORDS + mrow_words)) +
+      (capacity > 0 ? STAGE_BYTES : 0);  // a histogram-only call stages nothing
+  const int G = sweep_grid(sh, WB, "MMSBM_SCAN_VOTES_GRID");
+
+  DeviceGuard g(sh.device);
+  hipStream_t s = (hipStream_t)stream;
+  char* w = (char*)ws;
+  count_t* cursor = (count_t*)(w + p.off_cursor);
+  HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(count_t), s));
+  HIP_TRY(hipMemsetAsync(out_hist, 0, sizeof(count_t) * ((size_t)ns + 1), s));
+  if (sh.P >= 3) {
+    scan_prep_kernel<<<dim3(sh.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
+                                                     (double*)(w + p.off_T), sh.K, sh.KP, sh.R, sh.P, sh.P16, s0);
+    HIP_TRY(hipGetLastError());
+    const VotesArgs a{{(const double*)(w + p.off_thT), (const double*)(w + p.off_T), (const long long*)known,
+                       n_known, sh.K, sh.P, sh.P16, ns, WB},
+                      threshold, min_votes, (count_t)capacity, (count_t*)out_hist, cursor, out_scores,
+                      (long long*)out_keys, out_votes};
+    const VotesMaskedArgs am{a, mask, MW};
+    rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
+      constexpr int KS = decltype(ks)::value;
+      if (masked) {
+        if (capacity > 0)
+          return ns > 1 ? launch_lds(scan_votes_masked_kernel<KS, true, true>, G, lds, s, am)
+                        : launch_lds(scan_votes_masked_kernel<KS, false, true>, G, lds, s, am);
+        return ns > 1 ? launch_lds(scan_votes_masked_kernel<KS, true, false>, G, lds, s, am)
+                      : launch_lds(scan_votes_masked_kernel<KS, false, false>, G, lds, s, am);
+      }
+      if (capacity > 0)
+        return ns > 1 ? launch_lds(scan_votes_kernel<KS, true, true>, G, lds, s, a)
+                      : launch_lds(scan_votes_kernel<KS, false, true>, G, lds, s, a);
+      return ns > 1 ? launch_lds(scan_votes_kernel<KS, true, false>, G, lds, s, a)
+                    : launch_lds(scan_votes_kernel<KS, false, false>, G, lds, s, a);
+    });
+    if (rc) return rc;
+  }
+  scan_votes_finish_kernel<<<1, 1, 0, s>>>(cursor, (const count_t*)out_hist, ns, min_votes, capacity > 0,
+                                           (long long*)out_count);
+  HIP_TRY(hipGetLastError());
+  return MMSBM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -246,56 +348,17 @@ int mmsbm_scan_votes(mmsbm_ctx* c, const int32_t* order, const int64_t* known, i
                      const double* theta, const double* pr, int32_t sample, double threshold, int32_t min_votes,
                      int64_t capacity, void* ws, int64_t ws_bytes, int64_t* out_hist, double* out_scores,
                      int64_t* out_keys, int32_t* out_votes, int64_t* out_count, void* stream) {
-  if (!c) return fail(MMSBM_ERR_INVALID, "null context");
-  VotesPlan p;
-  int rc = make_plan(c, &p);
-  if (rc) return rc;
-  const ScanShape& sh = p.sh;
-  if (!order || !theta || !pr || !out_hist || !out_count) return fail(MMSBM_ERR_INVALID, "null pointer");
-  if (!std::isfinite(threshold)) return fail(MMSBM_ERR_INVALID, "the threshold must be a finite number");
-  if (capacity < 0) return fail(MMSBM_ERR_INVALID, "capacity=%lld < 0", (long long)capacity);
-  if (capacity > 0 && (!out_scores || !out_keys || !out_votes))
-    return fail(MMSBM_ERR_INVALID, "null output array with capacity > 0");
-  int ns, s0, WB;
-  size_t w_bytes;
-  if ((rc = check_call(sh, "the vote scan", "mmsbm_scan_votes_workspace_bytes", known, n_known, sample, ws, ws_bytes,
-                       p.total, &ns, &s0)))
-    return rc;
-  if (min_votes < 1 || min_votes > ns)
-    return fail(MMSBM_ERR_INVALID, "min_votes=%d outside [1, %d], the scored slots", min_votes, ns);
-  if ((rc = pick_wb(sh, "the vote scan", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
-  const int lds = (int)(sizeof(Head) + w_bytes + sizeof(count_t) * (ns + 1) + sizeof(unsigned) * BM_WORDS) +
-                  (capacity > 0 ? STAGE_BYTES : 0);  // a histogram-only call stages nothing
-  const int G = sweep_grid(sh, WB, "MMSBM_SCAN_VOTES_GRID");
+  return votes_call(c, order, known, n_known, nullptr, false, theta, pr, sample, threshold, min_votes, capacity, ws,
+                    ws_bytes, out_hist, out_scores, out_keys, out_votes, out_count, stream);
+}
 
-  DeviceGuard g(sh.device);
-  hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  count_t* cursor = (count_t*)(w + p.off_cursor);
-  HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(count_t), s));
-  HIP_TRY(hipMemsetAsync(out_hist, 0, sizeof(count_t) * ((size_t)ns + 1), s));
-  if (sh.P >= 3) {
-    scan_prep_kernel<<<dim3(sh.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
-                                                     (double*)(w + p.off_T), sh.K, sh.KP, sh.R, sh.P, sh.P16, s0);
-    HIP_TRY(hipGetLastError());
-    const VotesArgs a{{(const double*)(w + p.off_thT), (const double*)(w + p.off_T), (const long long*)known,
-                       n_known, sh.K, sh.P, sh.P16, ns, WB},
-                      threshold, min_votes, (count_t)capacity, (count_t*)out_hist, cursor, out_scores,
-                      (long long*)out_keys, out_votes};
-    rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
-      constexpr int KS = decltype(ks)::value;
-      if (capacity > 0)
-        return ns > 1 ? launch_lds(scan_votes_kernel<KS, true, true>, G, lds, s, a)
-                      : launch_lds(scan_votes_kernel<KS, false, true>, G, lds, s, a);
-      return ns > 1 ? launch_lds(scan_votes_kernel<KS, true, false>, G, lds, s, a)
-                    : launch_lds(scan_votes_kernel<KS, false, false>, G, lds, s, a);
-    });
-    if (rc) return rc;
-  }
-  scan_votes_finish_kernel<<<1, 1, 0, s>>>(cursor, (const count_t*)out_hist, ns, min_votes, capacity > 0,
-                                           (long long*)out_count);
-  HIP_TRY(hipGetLastError());
-  return MMSBM_OK;
+int mmsbm_scan_votes_masked(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
+                            const uint32_t* mask, const double* theta, const double* pr, int32_t sample,
+                            double threshold, int32_t min_votes, int64_t capacity, void* ws, int64_t ws_bytes,
+                            int64_t* out_hist, double* out_scores, int64_t* out_keys, int32_t* out_votes,
+                            int64_t* out_count, void* stream) {
+  return votes_call(c, order, known, n_known, mask, true, theta, pr, sample, threshold, min_votes, capacity, ws,
+                    ws_bytes, out_hist, out_scores, out_keys, out_votes, out_count, stream);
 }
 
 }  // extern "C"

@@ -458,11 +458,13 @@ class EMEngine:
         return scores[:n], ids[:n]
 
     # ------------------------------------------------------------- vote scan
-    def _votes_call(self, call, threshold, min_votes, capacity):
+    def _votes_call(self, call, threshold, min_votes, capacity, masked=False):
         """One mmsbm_scan_votes inside a _scan_call: -> device tensors (hist int64[ns + 1],
         votes int32[capacity], scores f64[capacity], keys int64[capacity], count int64[1]); the rows
-        in arrival order.  capacity = 0: the histogram-only call, the row arrays NULL."""
+        in arrival order.  capacity = 0: the histogram-only call, the row arrays NULL.  masked: the
+        _scan_call took a mask, so the entry is the masked one."""
         head, s = call
+        entry = self.lib.mmsbm_scan_votes_masked if masked else self.lib.mmsbm_scan_votes
         ns = self.active if head[-1] < 0 else 1
         ws = self.scan_workspace("scan_votes")
         hist = torch.empty(ns + 1, dtype=torch.int64, device=self.device)
@@ -470,9 +472,8 @@ class EMEngine:
         scores = torch.empty(capacity, dtype=torch.float64, device=self.device)
         keys = torch.empty(capacity, dtype=torch.int64, device=self.device)
         count = torch.empty(1, dtype=torch.int64, device=self.device)
-        _lib.check(self.lib.mmsbm_scan_votes(*head, threshold, int(min_votes), int(capacity), _ptr(ws), ws.numel(),
-                                             _ptr(hist), *(_ptr(t) if capacity else None for t in (scores, keys, votes)),
-                                             _ptr(count), s.cuda_stream))
+        _lib.check(entry(*head, threshold, int(min_votes), int(capacity), _ptr(ws), ws.numel(), _ptr(hist),
+                         *(_ptr(t) if capacity else None for t in (scores, keys, votes)), _ptr(count), s.cuda_stream))
         return hist, votes, scores, keys, count
 
     def _vote_args(self, threshold, min_votes, sample):
@@ -487,37 +488,39 @@ class EMEngine:
             raise ValueError("min_votes %d outside [1, %d], the scored slots" % (min_votes, ns))
         return threshold, min_votes
 
-    def vote_census_async(self, threshold, known: np.ndarray = None, sample: int = None, stream=None):
+    def vote_census_async(self, threshold, known: np.ndarray = None, sample: int = None, stream=None, mask=None):
         """vote_census without the host copy: -> the device tensor hist int64[ns + 1].  Nothing
         synchronises."""
         threshold, _ = self._vote_args(threshold, None, sample)
-        with self._scan_call(known, sample, stream) as call:
-            return self._votes_call(call, threshold, 1, 0)[0]
+        with self._scan_call(known, sample, stream, mask) as call:
+            return self._votes_call(call, threshold, 1, 0, mask is not None)[0]
 
-    def vote_census(self, threshold, known: np.ndarray = None, sample: int = None, stream=None):
+    def vote_census(self, threshold, known: np.ndarray = None, sample: int = None, stream=None, mask=None):
         """The vote histogram (include/mmsbm.h mmsbm_scan_votes): -> hist int64[ns + 1] on the host,
         hist[v] = the eligible triples (those scan_top ranks: distinct genes, key not in `known`)
         that exactly v of the scored slots score >= threshold.  The scored slots are the ns = active
         slots for sample = None and that one slot (ns = 1) otherwise; a slot's score carries the bits
         census(sample=slot) sees, so hist.sum() is the census's total and sum(v * hist[v]) the sum
         of the slots' census counts at the threshold.  A NaN or infinite threshold raises
-        ValueError.  known, sample: as for scan_top."""
-        hist = self.vote_census_async(threshold, known, sample, stream)
+        ValueError.  known, sample: as for scan_top.  mask: as for census (mmsbm_scan_votes_masked);
+        hist.sum() then is census([], mask=mask)'s total."""
+        hist = self.vote_census_async(threshold, known, sample, stream, mask)
         if stream is not None:
             stream.synchronize()
         return hist.cpu().numpy()
 
-    def _consensus(self, threshold, min_votes, known, sample, stream, limit):
+    def _consensus(self, threshold, min_votes, known, sample, stream, limit, mask=None):
         """-> (hist, votes int32[n], scores f64[n] and packed keys int64[n] on the device, sorted by
         votes descending, then score descending, then key ascending; the list call's count int64[1]
         on the device; the histogram's count n; the launch stream)."""
         threshold, min_votes = self._vote_args(threshold, min_votes, sample)
-        with self._scan_call(known, sample, stream) as call:    # one upload of the keys for both calls
-            hist = self._votes_call(call, threshold, min_votes, 0)[0]
+        masked = mask is not None
+        with self._scan_call(known, sample, stream, mask) as call:    # one upload of the keys for both calls
+            hist = self._votes_call(call, threshold, min_votes, 0, masked)[0]
             n = int(hist[min_votes:].sum().cpu())   # the same votes: exactly the rows the list call will find
             if n > int(limit):
                 raise LimitError(n, int(limit))
-            _, votes, scores, keys, found = self._votes_call(call, threshold, min_votes, n)
+            _, votes, scores, keys, found = self._votes_call(call, threshold, min_votes, n, masked)
             # the rows arrive in any order; three stable sorts, the last key first
             keys, at = torch.sort(keys, stable=True)
             votes, scores = votes[at], scores[at]
@@ -528,16 +531,16 @@ class EMEngine:
         return hist, votes, scores, keys, found, n, call[1]
 
     def consensus_async(self, threshold, min_votes: int = None, known: np.ndarray = None, sample: int = None,
-                        stream=None, limit: int = 1 << 26):
+                        stream=None, limit: int = 1 << 26, mask=None):
         """consensus without the host copy: -> device tensors (votes int32[n], scores f64[n],
         ids int32[n][3]) on the launch stream.  The number of rows comes from a histogram-only call
         first (one host read of one integer); a count above `limit` raises before the list call."""
-        _, votes, scores, keys, _, _, s = self._consensus(threshold, min_votes, known, sample, stream, limit)
+        _, votes, scores, keys, _, _, s = self._consensus(threshold, min_votes, known, sample, stream, limit, mask)
         with torch.cuda.stream(s):
             return votes, scores, self._keys_to_ids(keys)
 
     def consensus(self, threshold, min_votes: int = None, known: np.ndarray = None, sample: int = None,
-                  stream=None, limit: int = 1 << 26):
+                  stream=None, limit: int = 1 << 26, mask=None):
         """Every eligible triple that at least min_votes of the scored slots score >= threshold
         (include/mmsbm.h mmsbm_scan_votes; min_votes = None: all of them): -> (votes int32[n],
         scores f64[n], ids int32[n][3] in key order) on the host, sorted by votes descending, then
@@ -545,8 +548,10 @@ class EMEngine:
         A row's score is the ensemble score, scan_top's and scan_above's bits for the same `sample`.
         A NaN or infinite threshold and min_votes outside [1, the scored slots] raise ValueError, as
         does a count above `limit` (scan.LimitError, with the count and the limit): 20 bytes per row
-        on the device, twice that while sorting.  known, sample: as for scan_top."""
-        _, votes, scores, keys, found, n, s = self._consensus(threshold, min_votes, known, sample, stream, limit)
+        on the device, twice that while sorting.  known, sample: as for scan_top.  mask: as for census
+        (mmsbm_scan_votes_masked)."""
+        _, votes, scores, keys, found, n, s = self._consensus(threshold, min_votes, known, sample, stream, limit,
+                                                              mask)
         with torch.cuda.stream(s):
             ids = self._keys_to_ids(keys).cpu().numpy()
             votes, scores, found = votes.cpu().numpy(), scores.cpu().numpy(), int(found.cpu()[0])
@@ -570,22 +575,23 @@ class EMEngine:
         return min(m, ns - m + 1)
 
     def quorum_top_async(self, n: int, min_votes: int = None, known: np.ndarray = None, sample: int = None,
-                         stream=None):
+                         stream=None, mask=None):
         """quorum_top without the host copy: -> device tensors (scores f64[n], ids int32[n][3],
         count int64[1]); rows from `count` on are NaN / -1.  Nothing synchronises."""
         n = int(n)
         self.quorum_depth(min_votes, sample)    # ValueError before anything is uploaded
         m = (self.active if sample is None else 1) if min_votes is None else int(min_votes)
-        with self._scan_call(known, sample, stream) as (head, s):
+        entry = self.lib.mmsbm_scan_quorum_topn if mask is None else self.lib.mmsbm_scan_quorum_topn_masked
+        with self._scan_call(known, sample, stream, mask) as (head, s):
             ws = self.scan_workspace("scan_quorum", n)
             scores = torch.empty(n, dtype=torch.float64, device=self.device)
             ids = torch.empty((n, 3), dtype=torch.int32, device=self.device)
             count = torch.empty(1, dtype=torch.int64, device=self.device)
-            _lib.check(self.lib.mmsbm_scan_quorum_topn(*head, m, n, _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids),
-                                                       _ptr(count), s.cuda_stream))
+            _lib.check(entry(*head, m, n, _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids), _ptr(count), s.cuda_stream))
         return scores, ids, count
 
-    def quorum_top(self, n: int, min_votes: int = None, known: np.ndarray = None, sample: int = None, stream=None):
+    def quorum_top(self, n: int, min_votes: int = None, known: np.ndarray = None, sample: int = None, stream=None,
+                   mask=None):
         """The n eligible triples with the highest quorum score (include/mmsbm.h
         mmsbm_scan_quorum_topn): q_m = the m-th largest of the scored slots' own scores, m = min_votes
         (None: every scored slot, the minimum over them; 1: the maximum).  -> (scores f64[n'],
@@ -594,54 +600,60 @@ class EMEngine:
         q_m >= t.  The scored slots are the active slots for sample = None and that one slot
         otherwise, where the list is scan_top's for that sample, bit for bit.  min_votes outside
         [1, the scored slots] raises ValueError; a quorum_depth above quorum_max_depth raises
-        MMSBMError (MMSBM_ERR_UNSUPPORTED).  known, sample: as for scan_top."""
-        scores, ids, count = self.quorum_top_async(n, min_votes, known, sample, stream)
+        MMSBMError (MMSBM_ERR_UNSUPPORTED).  known, sample: as for scan_top.  mask: as for census
+        (mmsbm_scan_quorum_topn_masked): the exact top n over the triples without a blocked pair."""
+        scores, ids, count = self.quorum_top_async(n, min_votes, known, sample, stream, mask)
         if stream is not None:
             stream.synchronize()
         m = int(count.cpu()[0])
         return scores[:m].cpu().numpy(), ids[:m].cpu().numpy()
 
     # ----------------------------------------------------------- pair census
-    def _pair_census_rank(self, thresholds, known, sample, stream):
+    def _pair_census_rank(self, thresholds, known, sample, stream, mask=None):
         """The pair census in rank positions: -> (device int32 [P][P][len(thresholds)], filled for
         x < y only, thresholds in the caller's order; the launch stream).  One call of
-        mmsbm_pair_census per mmsbm_pair_census_max_m() thresholds."""
+        mmsbm_pair_census (with a mask: mmsbm_pair_census_masked) per mmsbm_pair_census_max_m()
+        thresholds."""
         plan = census_chunks(thresholds, int(self.lib.mmsbm_pair_census_max_m()))   # ValueError on a NaN or infinite one
-        with self._scan_call(known, sample, stream) as call:
-            mat, _ = self._per_threshold("pair_census", self.lib.mmsbm_pair_census, plan, call,
+        entry = self.lib.mmsbm_pair_census if mask is None else self.lib.mmsbm_pair_census_masked
+        with self._scan_call(known, sample, stream, mask) as call:
+            mat, _ = self._per_threshold("pair_census", entry, plan, call,
                                          lambda m: (self.P, self.P, m), torch.int32, 2)
         return mat, call[1]
 
-    def pair_census_async(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None):
+    def pair_census_async(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None, mask=None):
         """pair_census without the host copy: -> a device tensor int32 [P][P][len(thresholds)] in
         gene ids, symmetric with a zero diagonal, thresholds in the caller's order.  Nothing
         synchronises."""
-        mat, s = self._pair_census_rank(thresholds, known, sample, stream)
+        mat, s = self._pair_census_rank(thresholds, known, sample, stream, mask)
         with torch.cuda.stream(s):
             rank = torch.from_numpy(rank_of(rank_order(self.P))).to(self.device)
             mat = mat + mat.transpose(0, 1)             # x < y was filled, the rest is zero
             return mat[rank][:, rank].contiguous()      # [g1][g2] = [rank[g1]][rank[g2]]
 
-    def pair_census(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None):
+    def pair_census(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None, mask=None):
         """The pair census (include/mmsbm.h mmsbm_pair_census): -> int32 [P][P][len(thresholds)] on
         the host; [g1][g2][i] = the eligible triples (those scan_top ranks: distinct genes, key not
         in `known`) that contain the genes g1 and g2 and score >= thresholds[i]: the predicted,
         unmeasured interactions of the double-mutant query (g1, g2).  Symmetric, zero diagonal.
         The thresholds may come in any order, with duplicates, in any number or none; a NaN or an
         infinite one raises ValueError.  known, sample: as for census; the scores are the census's
-        bit for bit, so the sum over g1 < g2 is three times census(thresholds)."""
-        mat = self.pair_census_async(thresholds, known, sample, stream)
+        bit for bit, so the sum over g1 < g2 is three times census(thresholds).  mask: as for census
+        (mmsbm_pair_census_masked): a blocked pair's entries are zero and the sum is three times
+        census(thresholds, mask=mask)."""
+        mat = self.pair_census_async(thresholds, known, sample, stream, mask)
         if stream is not None:
             stream.synchronize()
         return mat.cpu().numpy()
 
-    def pairs_top(self, n: int, threshold: float, known: np.ndarray = None, sample: int = None):
+    def pairs_top(self, n: int, threshold: float, known: np.ndarray = None, sample: int = None, mask=None):
         """The n pairs with the most eligible triples scoring >= threshold: -> (counts int64[n'],
         eligible int64[n'] = the pair's eligible triples in all (scan.pair_eligible), ids
         int32[n'][2] in key order) on the host, n' = min(n, C(P, 2)).  Ordered by count descending,
         equal counts by the pair's rank-position key x P + y ascending.  The selection is one
-        torch.topk on the device over count * P^2 + (P^2 - 1 - key)."""
-        mat, s = self._pair_census_rank([float(threshold)], known, sample, None)
+        torch.topk on the device over count * P^2 + (P^2 - 1 - key).  mask: as for census; counts and
+        eligible then are the masked ones (a blocked pair: 0 and 0)."""
+        mat, s = self._pair_census_rank([float(threshold)], known, sample, None, mask)
         P = self.P
         n = max(0, min(int(n), P * (P - 1) // 2))
         with torch.cuda.stream(s):
@@ -655,14 +667,14 @@ class EMEngine:
         key = P * P - 1 - best % (P * P)
         order = rank_order(max(P, 1))
         ids = np.stack([order[key // P], order[key % P]], axis=1).astype(np.int32).reshape(-1, 2)
-        eligible = pair_eligible(P, known)[ids[:, 0], ids[:, 1]].astype(np.int64)
+        eligible = pair_eligible(P, known, mask)[ids[:, 0], ids[:, 1]].astype(np.int64)
         return counts.astype(np.int64), eligible, ids
 
-    def gene_census(self, thresholds, known: np.ndarray = None, sample: int = None):
+    def gene_census(self, thresholds, known: np.ndarray = None, sample: int = None, mask=None):
         """-> int64 [P][len(thresholds)] on the host: the eligible triples that contain each gene
         and score >= each threshold.  The row sums of the pair matrix halved: every triple of a gene
-        sits in two of the gene's pairs."""
-        mat = self.pair_census_async(thresholds, known, sample)
+        sits in two of the gene's pairs.  mask: as for pair_census."""
+        mat = self.pair_census_async(thresholds, known, sample, mask=mask)
         return (mat.sum(dim=1, dtype=torch.int64) // 2).cpu().numpy()
 
     # ---------------------------------------------------------- measurement

@@ -601,7 +601,8 @@ class Model:
     # ------------------------------------------------- trigenic interactions proper
     # A triple whose genes already interact pairwise is no trigenic candidate.  The digenic side of
     # the model says which pairs do; as a pair mask (scan.pair_mask) it restricts the trigenic scans,
-    # which run on the triplet engine (JointEngine.tri) under the masked census and threshold scan.
+    # which run on the triplet engine (JointEngine.tri) under the masked census, threshold scan and
+    # pair census.
     def digenic_mask(self, threshold=0.5, measured=True):
         """The pair mask of the digenic side: blocks every pair of genes whose digenic prediction
         (do_prediction of the pair, its ids in key order) is >= threshold and, with `measured`, every pair of `dlinks` /
@@ -644,6 +645,18 @@ class Model:
         P(r = 1) >= thresholds[i], and all of them (EMEngine.census with the mask)."""
         return self._push().tri.census(thresholds, self._trigenic_known(exclude), sample=0,
                                        mask=self.digenic_mask(threshold))
+
+    def predict_trigenic_query_pairs(self, n, pair_threshold=0.5, threshold=0.5, exclude=("train", "test")):
+        """The n pairs of genes with the most of the triples predict_novel_trigenic ranks (none of
+        whose three pairs the digenic side blocks: digenic_mask(threshold)) at P(r = 1) >=
+        pair_threshold, best first: rows [count, eligible, "i_j", [name1, name2]] as
+        Model.predict_query_pairs gives them, eligible = the pair's such triples in all
+        (EMEngine.pairs_top with the mask).  A pair the digenic side blocks has count and eligible 0."""
+        from .scan import pair_rows
+        counts, eligible, ids = self._push().tri.pairs_top(int(n), float(pair_threshold),
+                                                           self._trigenic_known(exclude), sample=0,
+                                                           mask=self.digenic_mask(threshold))
+        return pair_rows(self.id_gene, counts, eligible, ids)
 
     def calculate_test_set_results(self):
         rows = []

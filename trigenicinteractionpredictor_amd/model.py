@@ -559,29 +559,33 @@ class Model:
     # The question of a trigenic screen: its unit of work is a double-mutant query (a pair of genes
     # crossed against the whole array), so the pair to build next is the one with the most
     # predicted, unmeasured interactions.
-    def novel_pair_counts(self, thresholds, exclude=("train", "test")):
+    def novel_pair_counts(self, thresholds, exclude=("train", "test"), mask=None):
         """-> int32 [P][P][len(thresholds)] in gene ids: [i][j][m] = the triples of distinct genes
         outside the `exclude`d link tables that contain genes i and j with P(r = 1) >= thresholds[m].
         Symmetric, zero diagonal.  One pass over all C(P, 3) triples on the GPU per 8 thresholds
-        (engine.pair_census)."""
+        (engine.pair_census).  mask: as for predict_novel_any; a blocked pair's counts are zero."""
         from .scan import known_keys
-        return self._push().pair_census(thresholds, known_keys(self, exclude), sample=0)
+        return self._push().pair_census(thresholds, known_keys(self, exclude), sample=0, **_masked(mask))
 
-    def predict_query_pairs(self, n, threshold=0.5, exclude=("train", "test")):
+    def predict_query_pairs(self, n, threshold=0.5, exclude=("train", "test"), mask=None):
         """The n pairs of genes with the most such triples at or above `threshold`, best first
         (equal counts by the pair's key): rows [count, eligible, "i_j", [name1, name2]] with the
         key as `links` spells keys (:349-358), the names sorted as in predict_novel, and eligible =
-        the pair's triples outside the `exclude`d tables in all (engine.pairs_top)."""
+        the pair's triples outside the `exclude`d tables in all (engine.pairs_top).  mask: as for
+        predict_novel_any: count and eligible then leave out the triples with a blocked pair, so with
+        the genes of a strain array allowed (Model.pair_mask(genes=...)) the ranking is that of the
+        double-mutant queries over the triples the array can build."""
         from .scan import known_keys, pair_rows
         counts, eligible, ids = self._push().pairs_top(int(n), float(threshold), known_keys(self, exclude),
-                                                       sample=0)
+                                                       sample=0, **_masked(mask))
         return pair_rows(self.id_gene, counts, eligible, ids)
 
-    def novel_gene_counts(self, thresholds, exclude=("train", "test")):
+    def novel_gene_counts(self, thresholds, exclude=("train", "test"), mask=None):
         """-> int64 [P][len(thresholds)]: per gene id, the triples of distinct genes outside the
-        `exclude`d link tables that contain it with P(r = 1) >= each threshold (engine.gene_census)."""
+        `exclude`d link tables that contain it with P(r = 1) >= each threshold (engine.gene_census).
+        mask: as for predict_novel_any."""
         from .scan import known_keys
-        return self._push().gene_census(thresholds, known_keys(self, exclude), sample=0)
+        return self._push().gene_census(thresholds, known_keys(self, exclude), sample=0, **_masked(mask))
 
     def calculate_test_set_results(self):
         tids, _ = self._link_arrays(1)

@@ -434,18 +434,33 @@ def network_rows(id_gene, scores, ids):
             for i, (p, row) in enumerate(zip(scores, ids))]
 
 
-def pair_eligible(P: int, known=None) -> np.ndarray:
+def pair_eligible(P: int, known=None, mask=None) -> np.ndarray:
     """int32 [P][P] in gene ids: the eligible triples of every pair of genes, P - 2 minus the number
     of `known` keys (sorted packed keys of rank positions, scan.known_keys) that contain the pair;
     the diagonal is zero.  Keys that pack no triple a < b < c < P are ignored, as the kernels ignore
-    them.  Pure numpy: the pair census never counts eligibility (an add per triple)."""
+    them.  mask: a pair mask (scan.pair_mask), read for x < y only as the kernels read it: a pair's
+    eligible triples then are the third genes whose two pairs with it are unblocked (the product of
+    the allowed matrix with itself), minus the known triples that the mask does not block already; a
+    blocked pair has 0.  Pure numpy: the pair census never counts eligibility (an add per triple)."""
     P = int(P)
-    pos = np.full((P, P), max(P - 2, 0), dtype=np.int64)       # in rank positions
+    allowed = None
+    if mask is not None:
+        bits = np.unpackbits(check_pair_mask(mask, P).view(np.uint8), axis=1, bitorder="little")[:P, :P]
+        blocked = np.triu(bits.astype(bool), 1)
+        allowed = ~(blocked | blocked.T)
+        np.fill_diagonal(allowed, False)
+        # float64 holds the counts exactly (at most P - 2) and multiplies through the BLAS
+        count = allowed.astype(np.float64)
+        pos = np.where(allowed, np.rint(count @ count).astype(np.int64), 0)     # in rank positions
+    else:
+        pos = np.full((P, P), max(P - 2, 0), dtype=np.int64)   # in rank positions
     if known is not None and len(known) and P >= 3:
         k = np.unique(np.asarray(known, dtype=np.int64).reshape(-1))
         k = k[(k >= 0) & (k < P ** 3)]
         a, b, c = k // (P * P), (k // P) % P, k % P
         ok = (a < b) & (b < c)
+        if allowed is not None:     # a known triple with a blocked pair is gone already
+            ok &= allowed[a, b] & allowed[a, c] & allowed[b, c]
         a, b, c = a[ok], b[ok], c[ok]
         for x, y in ((a, b), (a, c), (b, c)):
             np.subtract.at(pos, (x, y), 1)
