@@ -473,6 +473,74 @@ int mmsbm_scan_quorum_topn_masked(mmsbm_ctx *ctx, const int32_t *order, const in
                                   void *ws, int64_t ws_bytes, double *out_scores, int32_t *out_ids,
                                   int64_t *out_count, void *stream);
 
+/* Screen scan: for each query PAIR of genes, the score of Model.do_prediction (:530-547, no eps) of
+ * every third gene, and the exact top N of them: what crossing the double-mutant query against the
+ * array is predicted to find.  Notation as for mmsbm_partners_topn: order[P] (device) = the gene ids
+ * sorted by str(id), Th' = theta in that order, p_1 the rating-1 lattice, a triple three rank
+ * positions sorted ascending with the packed key (a P + b) P + c.
+ * A query is two different gene ids; its rank positions are sorted to x < y (the order in which the
+ * two ids are given does not matter).  A candidate is a third position c not in {x, y}; the triple is
+ * {x, y, c} sorted, and its score factors through the two slots of p_1 the query fills:
+ *   c < x:      S = v1 . Th'[c],  v1[i] = sum_j sum_k p_1[i][j][k] Th'[x][j] Th'[y][k]
+ *   x < c < y:  S = v2 . Th'[c],  v2[j] = sum_i sum_k p_1[i][j][k] Th'[x][i] Th'[y][k]
+ *   y < c:      S = v3 . Th'[c],  v3[k] = sum_i sum_j p_1[i][j][k] Th'[x][i] Th'[y][j]
+ * (each v with the y slot contracted first, then the x slot, each contraction one fma chain over
+ * ascending index: about 3 K^3 fma per query and sample; then a [Q][P] GEMM of inner size K).  The
+ * triple's packed key increases with c across the three regions, so equal scores of one query order
+ * by smaller c.
+ * pairs_host int32[Q][2] (HOST) = gene ids in [0, P), the two of a row different; rows may repeat and
+ * every row is answered on its own.  Q <= 65535; Q = 0 returns MMSBM_OK and writes nothing.  The ids
+ * are copied to the workspace on `stream`.
+ * Eligibility of c for the query (x, y): c < P and c not in {x, y}; c not in the query's known slice;
+ * and, with a mask, none of (x, y), (x, c), (y, c) blocked (a query whose own pair is blocked has no
+ * candidate).  Exclusion, per query in CSR form: known_off int64[Q + 1] (device) offsets into
+ * known_thirds int32 (device), query i's slice holding the sorted, unique rank positions of the third
+ * genes to skip; positions equal to x or y, or >= P, are ignored.  known_off = NULL: none.  mask: the
+ * device uint32[P16][MW] bit matrix of mmsbm_pair_mask_shape in rank positions (bit y & 31 of
+ * mask[x][y >> 5] blocks the pair x < y; only x < y is read), or NULL for none: this family has one
+ * entry for both.  P <= 16384 when a mask is given.
+ * sample >= 0 scores that slot of the active prefix; -1 the ensemble, formed as the scan forms it:
+ * each slot's tile accumulated from zero, the tiles added in slot order, divided by n_active.
+ * Nothing of a slot sits in LDS, so no ensemble size is refused.
+ * mmsbm_screen_topn, result (device), row i for query i: the first out_count[i] rows of out_scores
+ * f64[Q][N] and out_ids int32[Q][N][3] hold the query's best candidates under the scan's total order
+ * (score descending; equal scores: the smaller packed key of the triple first); out_ids are the whole
+ * triple's gene ids in key order, so a row can go straight into mmsbm_predict.  out_count int64[Q],
+ * out_count[i] = min(N, the query's eligible candidates); the tail of a row is NaN / -1.  P < 3:
+ * counts 0 and rows of NaN.  One workgroup sees a query's whole row: no merge, no published bound.
+ * mmsbm_screen_scores, result (device): out f64[Q][P], out[i][c] = the score of query i with the
+ * gene at RANK POSITION c, or NaN at every ineligible position (x and y included); otherwise exactly
+ * the bits mmsbm_screen_topn ranks.
+ * Every sum has a fixed order and no score is formed by an atomic: a query's scores and list depend
+ * on (x, y), the sample and the eligibility only, not on Q, on the other queries, on the order in
+ * which the pair's two ids were given, on the pass size or on the grid.  The scores need not equal
+ * mmsbm_scan_topn's or mmsbm_partners_topn's bit for bit (the contraction order differs); they agree
+ * to 1e-9 relative.
+ * Refusals, all before any device call and with the outputs untouched.  MMSBM_ERR_INVALID: null
+ * pointers; a bad sample; an id outside [0, P); a pair of equal ids; Q < 0 or Q > 65535; a missing,
+ * misaligned or small workspace.  MMSBM_ERR_UNSUPPORTED: N outside [1, mmsbm_screen_max_n()] (1024: a
+ * workgroup's candidate buffer stays in the LDS); K outside [1, MMSBM_MAX_K]; R < 2; P > 2 000 000
+ * (the packed key); P > 16384 with a mask.
+ * ws: mmsbm_screen_workspace_bytes(ctx, Q, N) bytes of device scratch, 16-byte aligned, the caller's
+ * (N = 0: what mmsbm_screen_scores needs; a workspace for any N >= 1 serves it too); its size follows
+ * the context's shape, Q and N only.  It holds the score rows of one pass: when Q rows of P16
+ * doubles exceed 256 MiB the call runs passes over blocks of queries.  The environment variable
+ * MMSBM_SCREEN_CHUNK=<queries per pass> lowers the block size (measurement and the tests of the pass
+ * boundary; the results do not depend on it).  theta and pr are only read; all launches go to
+ * `stream` and nothing synchronises.  The caller guarantees that order is a permutation of [0, P).
+ * Replaces nothing in the reference. */
+int mmsbm_screen_max_n(void);
+int mmsbm_screen_workspace_bytes(const mmsbm_ctx *ctx, int64_t Q, int32_t N, int64_t *bytes);
+int mmsbm_screen_topn(mmsbm_ctx *ctx, const int32_t *order, const int32_t *pairs_host, int64_t Q,
+                      const int64_t *known_off, const int32_t *known_thirds, const uint32_t *mask,
+                      const double *theta, const double *pr, int32_t sample, int32_t N, void *ws,
+                      int64_t ws_bytes, double *out_scores, int32_t *out_ids, int64_t *out_count,
+                      void *stream);
+int mmsbm_screen_scores(mmsbm_ctx *ctx, const int32_t *order, const int32_t *pairs_host, int64_t Q,
+                        const int64_t *known_off, const int32_t *known_thirds, const uint32_t *mask,
+                        const double *theta, const double *pr, int32_t sample, void *ws,
+                        int64_t ws_bytes, double *out, void *stream);
+
 /* Link-sharded iteration (single sample over N ranks): each rank's context
  * holds 1/N of the train links (mmsbm_set_links) and the GLOBAL degree (mmsbm_set_degree).
  * Step 1, the accumulation half of make_iteration (:986-1012) over this rank's links:

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .scan import (LimitError, bracket_threshold, census_chunks, check_known_keys, check_pair_mask,
-                   check_partner_known, pair_eligible, rank_of, rank_order)
+                   check_partner_known, check_screen_known, pair_eligible, rank_of, rank_order, screen_pairs)
 
 _CURRENT_STREAM = contextlib.nullcontext()     # a scan call without a stream: nothing to make current
 
@@ -225,7 +225,7 @@ class EMEngine:
 
     def scan_workspace(self, family: str, *size_args) -> torch.Tensor:
         """The scratch of one family ("scan", "partners", "census", "pair_census", "scan_above",
-        "scan_votes", "scan_quorum"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device."""
+        "scan_votes", "scan_quorum", "screen"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device."""
         nbytes = ctypes.c_int64()
         _lib.check(getattr(self.lib, "mmsbm_%s_workspace_bytes" % family)(self.ctx, *size_args,
                                                                           ctypes.byref(nbytes)))
@@ -335,6 +335,72 @@ class EMEngine:
             stream.synchronize()
         counts, scores, ids = counts.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
         return [(scores[i, :int(m)].copy(), ids[i, :int(m)].copy()) for i, m in enumerate(counts)]
+
+    # ----------------------------------------------------------- screen scan
+    @contextlib.contextmanager
+    def _screen_call(self, pairs, known, sample, stream, mask, n):
+        """One call of the screen scan inside a _scan_call: checks the pairs and `known`, uploads the
+        slices and sizes the scratch; -> (Q, the C calls' arguments up to the sample, the scratch's
+        (pointer, bytes), the stream)."""
+        pairs = screen_pairs(pairs, self.P)
+        Q = int(pairs.shape[0])
+        off, thirds = (None, None) if known is None else check_screen_known(known, Q)
+        with self._scan_call(None, sample, stream, mask) as ((ctx, order, _, _, *rest), s):   # no key table
+            mask_p, params = (rest[0], rest[1:]) if mask is not None else (None, rest)
+            ws = self.scan_workspace("screen", Q, int(n))
+            off_d = thirds_d = None
+            if off is not None:
+                off_d = torch.from_numpy(off).to(self.device)
+                thirds_d = torch.from_numpy(thirds if thirds.size else np.zeros(1, np.int32)).to(self.device)
+            yield Q, (ctx, order, _host_ptr(pairs), Q, _ptr(off_d) if off_d is not None else None,
+                      _ptr(thirds_d) if thirds_d is not None else None, mask_p, *params), (_ptr(ws), ws.numel()), s
+
+    def screen_top_async(self, pairs, n: int, known=None, sample: int = None, stream=None, mask=None):
+        """screen_top without the host copy: -> device tensors (scores f64[Q][n], ids int32[Q][n][3],
+        counts int64[Q]); row i answers pairs[i], its rows from counts[i] on are NaN / -1.  Nothing
+        synchronises."""
+        n = int(n)
+        with self._screen_call(pairs, known, sample, stream, mask, n) as (Q, head, ws, s):
+            scores = torch.empty((Q, n), dtype=torch.float64, device=self.device)
+            ids = torch.empty((Q, n, 3), dtype=torch.int32, device=self.device)
+            counts = torch.empty(Q, dtype=torch.int64, device=self.device)
+            _lib.check(self.lib.mmsbm_screen_topn(*head, n, *ws, _ptr(scores), _ptr(ids), _ptr(counts),
+                                                  s.cuda_stream))
+        return scores, ids, counts
+
+    def screen_top(self, pairs, n: int, known=None, sample: int = None, stream=None, mask=None):
+        """For each query pair of gene ids, its n most probable third genes (include/mmsbm.h
+        mmsbm_screen_topn): -> one (scores f64[n'], ids int32[n'][3]) pair per query on the host,
+        best first, n' <= n; an id row is the whole triple in key order, the pair included.
+        known: (known_off, known_thirds) of scan.screen_known for these pairs; sample: a slot of the
+        active prefix, or None for the mean over it; mask: a pair mask (scan.pair_mask): a third gene
+        that forms a blocked pair with either gene of the query is not eligible, and a query whose own
+        pair is blocked has no candidate."""
+        scores, ids, counts = self.screen_top_async(pairs, n, known, sample, stream, mask)
+        if stream is not None:
+            stream.synchronize()
+        counts, scores, ids = counts.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
+        return [(scores[i, :int(m)].copy(), ids[i, :int(m)].copy()) for i, m in enumerate(counts)]
+
+    def screen_scores_async(self, pairs, known=None, sample: int = None, stream=None, mask=None):
+        """screen_scores without the host copy: -> a device tensor f64[Q][P] indexed by the third
+        gene's id.  Nothing synchronises."""
+        with self._screen_call(pairs, known, sample, stream, mask, 0) as (Q, head, ws, s):
+            out = torch.empty((Q, self.P), dtype=torch.float64, device=self.device)
+            _lib.check(self.lib.mmsbm_screen_scores(*head, *ws, _ptr(out), s.cuda_stream))
+            rank = torch.from_numpy(rank_of(rank_order(self.P))).to(self.device)
+            return out[:, rank].contiguous()    # [q][g] = the kernel's [q][rank[g]]
+
+    def screen_scores(self, pairs, known=None, sample: int = None, stream=None, mask=None):
+        """Every query pair's whole score row (include/mmsbm.h mmsbm_screen_scores): -> f64[Q][P] on
+        the host, [i][g] = the score of the triple of pairs[i] and the gene with id g: the pair's
+        predicted interaction profile across the array.  NaN where g is not eligible (the pair's own
+        genes, the thirds of `known`, what `mask` blocks); elsewhere exactly the bits screen_top
+        ranks.  known, sample, mask: as for screen_top."""
+        out = self.screen_scores_async(pairs, known, sample, stream, mask)
+        if stream is not None:
+            stream.synchronize()
+        return out.cpu().numpy()
 
     def census_async(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None, mask=None):
         """census without the host copy: -> device tensors (counts int64[len(thresholds)] in the

@@ -514,6 +514,30 @@ class Model:
         top = np.lexsort((pack_keys(ids, rank, self.P), -scores))[:int(n)]
         return self._rows(scores[top], ids[top])
 
+    def _pair_args(self, pairs):
+        return np.array([[self._gene_arg(g) for g in pair] for pair in pairs], dtype=np.int64).reshape(-1, 2)
+
+    def predict_screen(self, pairs, n, exclude=("train", "test"), mask=None):
+        """For each query pair of genes (ids or names), its n most probable third genes outside the
+        `exclude`d link tables, best first: one list per pair of rows [probability, "i_j_k",
+        [name1, name2, name3]] as predict_partners gives them.  Every pair of the call goes through
+        one screen scan on the GPU (engine.screen_top).  mask: a pair mask (Model.pair_mask): a third
+        gene that forms a blocked pair with either gene of the query is left out.  ValueError on a
+        pair of one gene."""
+        from .scan import screen_known
+        pairs = self._pair_args(pairs)
+        lists = self._push().screen_top(pairs, int(n), screen_known(self, pairs, exclude), sample=0, mask=mask)
+        return [self._rows(scores, ids) for scores, ids in lists]
+
+    def predict_profiles(self, pairs, exclude=("train", "test"), mask=None):
+        """-> ndarray f64 [Q][P]: row i = the probability of the triple of pairs[i] (ids or names)
+        with every gene id, the pair's predicted interaction profile across the array; NaN at the
+        pair's own genes, at the third genes the `exclude`d tables hold for it and at what `mask`
+        blocks (engine.screen_scores)."""
+        from .scan import screen_known
+        pairs = self._pair_args(pairs)
+        return self._push().screen_scores(pairs, screen_known(self, pairs, exclude), sample=0, mask=mask)
+
     # ---------------------------------------------------------- score census
     # Exactness: the counts are exact for the scan's score bits; a listed triple's probability comes
     # from the predict kernel, which sums in another order, so a triple within rounding distance

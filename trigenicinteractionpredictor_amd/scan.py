@@ -92,9 +92,19 @@ blocked pair is not eligible.
     --block-pairs FILE     two gene names or ids per line, tab or space separated: these pairs are
                            blocked, such as the pairs known to interact digenically.
 They apply to the main table (which then goes through `EMEngine.scan_top_any`: masked censuses find
-the cut, the masked threshold scan lists above it), --census and --network, and combine by OR.  With
+the cut, the masked threshold scan lists above it), --census, --network and --screen, and combine by OR.  With
 --gene / --all-genes, --pairs, --gene-census, --consensus and --quorum, whose kernels take no mask,
 they are refused.  --heldout-ranks is not restricted by them.
+
+One more comes from the screen scan (`EMEngine.screen_top`, mmsbm_screen_topn): what crossing a
+double-mutant query against the array is predicted to find.
+    --screen FILE          per query pair of genes, its --screen-top N (default 20, in [1, 1024]) most
+                           probable third genes among the eligible triples (under --exclude, scored by
+                           --best or the ensemble mean): query, rank, probability, ids, names rows, in
+                           query order and then by rank; query = the pair's two names.  The pairs come
+                           from exactly one of --query-pairs FILE (the format of --block-pairs) and
+                           --screen-best Q (the Q pairs --pairs ranks first at --pair-threshold, under
+                           the same exclude and mask).  --allow-genes / --block-pairs apply to it.
 
 Exactness: the counts are exact for the scan's score bits.  A listed triple's probability comes from
 the predict kernel, which sums in another order, so a triple within rounding distance (about 1e-12
@@ -119,6 +129,9 @@ DEFAULT_NETWORK_THRESHOLD = 0.5    # --network without --network-threshold
 DEFAULT_NETWORK_LIMIT = 10000000   # --network without --network-limit: the most rows it writes
 DEFAULT_CONSENSUS_THRESHOLD = 0.5    # --consensus without --consensus-threshold
 DEFAULT_CONSENSUS_LIMIT = 10000000   # --consensus without --consensus-limit: the most rows it writes
+MAX_SCREEN_TOP = 1024    # mmsbm_screen_max_n(): the largest N per query pair
+DEFAULT_SCREEN_TOP = 20  # --screen without --screen-top: the rows per query pair
+MAX_SCREEN_QUERIES = 65535   # the most query pairs one mmsbm_screen_topn call takes
 MAX_QUORUM_DEPTH = 4     # mmsbm_scan_quorum_max_depth(): the deepest sorted list of the quorum scan
 DEFAULT_THRESHOLDS = (0.99, 0.95, 0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3, 0.2, 0.1, 0.05, 0.02, 0.01, 0.005,
                       0.002, 0.001)   # --census without --thresholds
@@ -234,6 +247,84 @@ def check_partner_known(known, Q: int):
         raise ValueError("each query's known pair keys must be sorted and unique "
                          "(scan.partner_known)")
     return off, pairs
+
+
+# -------------------------------------------------------------------------------- screen scan
+def screen_pairs(pairs, P: int) -> np.ndarray:
+    """Query pairs as mmsbm_screen_topn takes them -> contiguous int32[Q][2] gene ids; IndexError on
+    an id outside [0, P), ValueError on a pair of one gene or rows that are not pairs."""
+    pairs = np.asarray(pairs)
+    if pairs.size and not np.issubdtype(pairs.dtype, np.integer):
+        raise ValueError("query pairs must be integer gene ids")
+    if pairs.size % 2 or (pairs.ndim > 1 and pairs.shape[-1] != 2):
+        raise ValueError("query pairs must be rows of two gene ids")
+    pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= int(P)):
+        raise IndexError("query gene id outside [0, %d)" % int(P))
+    if (pairs[:, 0] == pairs[:, 1]).any():
+        raise ValueError("a query pair needs two different genes")
+    return pairs.astype(np.int32)
+
+
+def screen_known(source, pairs, exclude=SETS):
+    """The measured third genes of each query pair, as mmsbm_screen_topn takes them:
+    -> (known_off int64[Q + 1], known_thirds int32[known_off[Q]]), query i's slice holding the
+    sorted, unique rank positions of the third genes of the measured triples of distinct genes that
+    contain both genes of pairs[i].  `source` is a Model or (P, train_ids, test_ids); `pairs` are
+    gene ids in [0, P), two different ones per row (IndexError, ValueError otherwise)."""
+    exclude = parse_exclude(exclude)
+    P, tables = _id_tables(source, exclude)
+    pairs = screen_pairs(pairs, P).astype(np.int64)
+    Q = pairs.shape[0]
+    off = np.zeros(Q + 1, dtype=np.int64)
+    if not tables or not Q:
+        return off, np.zeros(0, dtype=np.int32)
+    ids = np.concatenate(tables, axis=0)
+    distinct = (ids[:, 0] != ids[:, 1]) & (ids[:, 1] != ids[:, 2]) & (ids[:, 0] != ids[:, 2])
+    rank = rank_of(rank_order(P))
+    pos = np.sort(rank[ids[distinct]], axis=1)
+    a, b, c = pos[:, 0], pos[:, 1], pos[:, 2]
+    # one (pair key, third) entry per pair of every triple, sorted by pair then third
+    both = np.unique(np.concatenate([a * P + b, a * P + c, b * P + c]) * P + np.concatenate([c, b, a]))
+    who, third = both // P, both % P
+    qpos = np.sort(rank[pairs], axis=1)
+    qkey = qpos[:, 0] * P + qpos[:, 1]
+    lo, hi = np.searchsorted(who, qkey, side="left"), np.searchsorted(who, qkey, side="right")
+    off[1:] = np.cumsum(hi - lo)
+    thirds = np.concatenate([third[l:h] for l, h in zip(lo, hi)])
+    return off, thirds.astype(np.int32)
+
+
+def check_screen_known(known, Q: int):
+    """The screen scan's (known_off, known_thirds) for Q queries -> contiguous (int64, int32);
+    ValueError unless the offsets are Q + 1 non-decreasing indices into the thirds and every query's
+    slice is sorted and unique (a position may fall from one slice to the next), as screen_known
+    gives them."""
+    off = np.ascontiguousarray(known[0], dtype=np.int64).reshape(-1)
+    thirds = np.ascontiguousarray(known[1], dtype=np.int32).reshape(-1)
+    if off.size != Q + 1 or off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > thirds.size:
+        raise ValueError("known offsets must be %d non-decreasing indices into the third genes "
+                         "(scan.screen_known)" % (Q + 1))
+    rising = thirds[1:] > thirds[:-1]
+    starts = off[1:-1]
+    rising[starts[(starts > 0) & (starts < thirds.size)] - 1] = True   # a new query's slice
+    if not rising[int(off[0]):max(int(off[-1]) - 1, int(off[0]))].all():
+        raise ValueError("each query's known third genes must be sorted and unique "
+                         "(scan.screen_known)")
+    return off, thirds
+
+
+def screen_rows(id_gene, pairs, lists):
+    """screen_top's lists for the query `pairs` (gene ids) -> the driver's rows [query, rank,
+    probability, "i_j_k", names], in query order and then by rank; query = the pair's two names in
+    the order of its key."""
+    rows = []
+    for (g1, g2), (scores, ids) in zip(pairs, lists):
+        a, b = sorted((int(g1), int(g2)), key=str)
+        query = "%s_%s" % (id_gene[a], id_gene[b])
+        rows += [[query, i + 1, float(p), "_".join(str(int(x)) for x in row), sorted(id_gene[int(x)] for x in row)]
+                 for i, (p, row) in enumerate(zip(scores, ids))]
+    return rows
 
 
 # ---------------------------------------------------------------------------------- pair mask
@@ -566,6 +657,10 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [--quorum-votes=] <M, an integer in [1, restarts]; default: all restarts (the minimum over them)>
     [--allow-genes=] <file, one gene name or id per line: only triples of these genes>
     [--block-pairs=] <file, two gene names or ids per line: no triple that contains such a pair>
+    [--screen=] <TSV file: per query pair of genes, its most probable third genes>
+    [--screen-top=] <rows per query pair, in [1, 1024]; default 20>
+    [--query-pairs=] <file, two gene names or ids per line: the query pairs of --screen>
+    [--screen-best=] <Q: the query pairs of --screen are the Q best of --pairs at --pair-threshold>
 """
 
 
@@ -580,7 +675,8 @@ def parse(argv):
     # their defaults) only when one of its options is given: without them cfg is what it always was;
     # --consensus does the same with its four (consensus, consensus_threshold, min_votes,
     # consensus_limit) and --quorum with its two (quorum, quorum_votes); --allow-genes and
-    # --block-pairs add their two (allow_genes, block_pairs) when one of them is given
+    # --block-pairs add their two (allow_genes, block_pairs) when one of them is given; --screen adds
+    # its four (screen, screen_top, query_pairs, screen_best) in the same way
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
@@ -590,7 +686,8 @@ def parse(argv):
                                                         "network-threshold=", "network-limit=", "consensus=",
                                                         "consensus-threshold=", "min-votes=",
                                                         "consensus-limit=", "quorum=", "quorum-votes=",
-                                                        "allow-genes=", "block-pairs="])
+                                                        "allow-genes=", "block-pairs=", "screen=",
+                                                        "screen-top=", "query-pairs=", "screen-best="])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -677,6 +774,21 @@ def parse(argv):
                 cfg["allow_genes"] = arg
             elif opt == "--block-pairs":
                 cfg["block_pairs"] = arg
+            elif opt == "--screen":
+                cfg["screen"] = arg
+            elif opt == "--screen-top":
+                if not 1 <= int(arg) <= MAX_SCREEN_TOP:
+                    print("\n\nERROR: --screen-top should be an integer number in [1, %d]" % MAX_SCREEN_TOP)
+                    raise cli.ArgError()
+                cfg["screen_top"] = int(arg)
+            elif opt == "--query-pairs":
+                cfg["query_pairs"] = arg
+            elif opt == "--screen-best":
+                if not 1 <= int(arg) <= MAX_SCREEN_QUERIES:
+                    print("\n\nERROR: --screen-best should be an integer number of pairs in [1, %d]"
+                          % MAX_SCREEN_QUERIES)
+                    raise cli.ArgError()
+                cfg["screen_best"] = int(arg)
             elif opt == "--thresholds":
                 try:
                     cfg["thresholds"] = parse_thresholds(arg)
@@ -729,6 +841,17 @@ def parse(argv):
                 print("\n\nERROR: --allow-genes / --block-pairs restrict the main table, --census and --network: "
                       "they do not go with %s, whose kernel takes no pair mask" % name)
                 raise cli.ArgError()
+    if any(key in cfg for key in ("screen", "screen_top", "query_pairs", "screen_best")):
+        cfg.setdefault("screen", None)
+        cfg.setdefault("screen_top", DEFAULT_SCREEN_TOP)
+        cfg.setdefault("query_pairs", None)
+        cfg.setdefault("screen_best", None)
+        if cfg["screen"] and cfg["query_pairs"] is None and cfg["screen_best"] is None:
+            print("\n\nERROR: --screen needs its query pairs: --query-pairs FILE or --screen-best Q")
+            raise cli.ArgError()
+        if cfg["query_pairs"] is not None and cfg["screen_best"] is not None:
+            print("\n\nERROR: --query-pairs and --screen-best exclude each other")
+            raise cli.ArgError()
     if cfg["genes"] and cfg["all_genes"]:
         print("\n\nERROR: --gene and --all-genes exclude each other")
         raise cli.ArgError()
@@ -775,6 +898,40 @@ def driver_mask(model, cfg):
     except (OSError, ValueError) as e:
         print("\n\nERROR: --allow-genes / --block-pairs: %s" % (e,))
     raise cli.ArgError()
+
+
+def screen_queries(model, cfg):
+    """The driver's query pairs from --query-pairs, as int32[Q][2] gene ids (None: no --screen, or
+    --screen-best, whose pairs come from the fit); cli.ArgError on a file that does not read, a line
+    without two genes, a gene the fold does not hold, a pair of one gene or too many pairs."""
+    from . import cli
+    if not cfg.get("screen") or cfg.get("query_pairs") is None:
+        return None
+    try:
+        tokens = read_block_pairs(cfg["query_pairs"])
+        flat = resolve_genes(model, [t for pair in tokens for t in pair])
+        pairs = screen_pairs(np.asarray(flat, dtype=np.int64).reshape(-1, 2), model.P)
+        if pairs.shape[0] > MAX_SCREEN_QUERIES:
+            raise ValueError("%d query pairs, more than %d" % (pairs.shape[0], MAX_SCREEN_QUERIES))
+        return pairs
+    except (KeyError, IndexError) as e:
+        print("\n\nERROR: --query-pairs: unknown gene %s" % (e,))
+    except (OSError, ValueError) as e:
+        print("\n\nERROR: --query-pairs: %s" % (e,))
+    raise cli.ArgError()
+
+
+def screen_table(eng, model, cfg, known, sample, extras, queries, mask=None):
+    """The driver's --screen table into `extras` (see run); queries: screen_queries' pairs, or None
+    for --screen-best: the pairs pairs_top ranks first at --pair-threshold under the same exclude
+    and mask."""
+    if not cfg.get("screen"):
+        return
+    if queries is None:
+        queries = eng.pairs_top(cfg["screen_best"], cfg["pair_threshold"], known, sample, **_masked(mask))[2]
+    lists = eng.screen_top(queries, cfg["screen_top"], screen_known(model, queries, cfg["exclude"]), sample,
+                           mask=mask)
+    extras["screen"] = screen_rows(model.id_gene, queries, lists)
 
 
 def _masked(mask):
@@ -887,12 +1044,14 @@ def run(cfg, out=print, extras=None):
     names] and "gene_census" = (thresholds, names, counts int64[P][M]) for --pairs, --gene-census, and
     "network" = rows [rank, probability, ids, names] for --network, and "consensus" = (restarts,
     threshold, hist, rows [rank, votes, probability, ids, names]) for --consensus, and "quorum" =
-    (restarts, votes, rows [rank, quorum score, mean, min, max, ids, names]) for --quorum."""
+    (restarts, votes, rows [rank, quorum score, mean, min, max, ids, names]) for --quorum, and
+    "screen" = rows [query, rank, probability, ids, names] for --screen."""
     from .model import Model
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
     queries = partner_queries(model, cfg)     # before anything touches a GPU
     mask = driver_mask(model, cfg)
+    pair_queries = screen_queries(model, cfg)
     from . import _lib
     from .engine import EMEngine
     from .restarts import stream_states
@@ -912,6 +1071,7 @@ def run(cfg, out=print, extras=None):
         network_table(eng, model, cfg, known, sample, extras, mask)
         consensus_table(eng, model, cfg, known, extras)
         quorum_table(eng, model, cfg, known, extras)
+        screen_table(eng, model, cfg, known, sample, extras, pair_queries, mask)
     if queries is not None:
         out("partner pairs of %d genes: %s" % (len(queries), "sample %d" % sample if sample is not None
                                                else "mean of %d samples" % B))
@@ -1020,6 +1180,9 @@ def main(argv=None, out=print):
     if "quorum" in extras:
         with open(cfg["quorum"], "w", encoding="utf-8") as f:
             write_quorum_tsv(*extras["quorum"], f)
+    if "screen" in extras:
+        with open(cfg["screen"], "w", encoding="utf-8") as f:
+            write_tsv(extras["screen"], f, partners=True)
     partners = bool(cfg["genes"] or cfg["all_genes"])
     if cfg["out"]:
         with open(cfg["out"], "w", encoding="utf-8") as f:
