@@ -244,13 +244,20 @@ def pick_cuts(desc):
 
 
 @functools.lru_cache(maxsize=None)
-def random_pair_mask(P):
-    """10 % of the gene pairs, blocked through scan.pair_mask -> (mask, the key table it stands for)."""
+def random_pair_mask_words(P):
+    """10 % of the gene pairs, blocked through scan.pair_mask -> the mask alone (no key table: that
+    one goes through all P^3 triples, too many at the screen scan's wide rows)."""
     from trigenicinteractionpredictor_amd.scan import pair_mask
     rng = np.random.default_rng(P)
     i, j = np.triu_indices(P, k=1)
     pick = rng.random(i.size) < 0.1
-    mask = pair_mask(P, pairs=np.stack([i[pick], j[pick]], axis=1))
+    return pair_mask(P, pairs=np.stack([i[pick], j[pick]], axis=1))
+
+
+@functools.lru_cache(maxsize=None)
+def random_pair_mask(P):
+    """random_pair_mask_words(P) -> (mask, the key table it stands for)."""
+    mask = random_pair_mask_words(P)
     import masked_ref
     keys = masked_ref.expand(mask, P)
     assert 0 < keys.size < P * (P - 1) * (P - 2) // 6

@@ -2,15 +2,22 @@
 partners_ref.py and the GPU tests): the all-triples float64 scorer, the scan's total order, the
 precondition on adjacent gaps and a few helpers.  numpy only: no GPU, no product code beyond the
 rank order."""
+import functools
+
 import numpy as np
 
 RTOL = 1e-9
 
 
+@functools.lru_cache(maxsize=None)
 def rank_tables(P):
+    """(order, rank) of P genes, read-only; computed once per P (the sort of 262k ids takes a second)."""
     from trigenicinteractionpredictor_amd.scan import rank_of, rank_order
     order = rank_order(P)
-    return order, rank_of(order)
+    rank = rank_of(order)
+    order.setflags(write=False)
+    rank.setflags(write=False)
+    return order, rank
 
 
 def keys_to_ids(keys, P):

@@ -439,6 +439,93 @@ def test_scan_partners_and_census_read_the_rating_1_slice(R, K, B):
     eng.close()
 
 
+# ------------------------------------------------------------------ (f2) the later scan families
+@pytest.mark.parametrize("R,K,B", SCAN_PARAMS, ids=["R%d-K%d-B%d" % c for c in SCAN_PARAMS])
+def test_the_later_scan_families_read_the_rating_1_slice(R, K, B):
+    """The screen scan, the pair census, the threshold scan, the vote scan and the quorum scan at
+    R = 3 and 8: each family's host entry hands its own prep launch the rating count, and the
+    rating-1 slice of slot s lies at (s R + 1) K^3.  With B = 2 both slot 1 and the ensemble run:
+    slot 0's offset is K^3 whatever R is.  Before each comparison, on the reference alone: ratings 0
+    and 2 in rating 1's place give another answer."""
+    import census_ref
+    import pair_census_ref
+    import quorum_ref
+    import scan_ref
+    import screen_ref
+    import votes_ref
+    from test_gpu_scan_above import assert_list_properties
+    from test_gpu_screen import rank_rows, to_ids
+    from trigenicinteractionpredictor_amd import EMEngine
+    P, th, pr, mean, keys, wrong_mean = scan_case(R, K, B)
+    rolled = [np.roll(pr, shift, axis=-1) for shift in (1, -1)]        # ratings 0 and 2 in rating 1's place
+    per = np.stack([scan_ref.ref_scores(th[b], pr[b])[0] for b in range(B)])
+    wrong_per = [np.stack([scan_ref.ref_scores(th[b], w[b])[0] for b in range(B)]) for w in rolled]
+    eng = EMEngine(K, P, B=B, R=R)
+    eng.upload(th, pr)
+    pos = [(0, P - 1), (0, 1), (P - 2, P - 1), (15, 16), (3, 32), (14, 17), (7, 25), (20, 21)]
+    pairs = to_ids(P, pos)
+    N = 16
+    for sample in (None, 1) if B == 2 else (None,):
+        scored = slice(0, B) if sample is None else slice(sample, sample + 1)
+        ns = scored.stop - scored.start
+        scores = mean if sample is None else per[sample]
+        wrong = wrong_mean if sample is None else [w[sample] for w in wrong_per]
+        # the screen scan: rows and the top 16 of eight pairs
+        rows = rank_rows(P, eng.screen_scores(pairs, sample=sample))
+        lists = eng.screen_top(pairs, N, sample=sample)
+        for i, (x, y) in enumerate(pos):
+            want = screen_ref.ref_rows(th, pr, x, y, sample)
+            for w in rolled:
+                other = screen_ref.ref_rows(th, w, x, y, sample)
+                assert not np.array_equal(screen_ref.want_list(other, P, x, y, N)[1], screen_ref.want_list(want, P, x, y, N)[1])
+            screen_ref.check_row(rows[i], want, screen_ref.eligible(P, x, y))
+            screen_ref.check_list(lists[i], want, P, x, y, N)
+        # the pair census
+        thresholds = census_ref.gap_thresholds(scores, 40)[:8]
+        census_ref.assert_clear(scores, thresholds)
+        want = pair_census_ref.ref_pairs(scores, keys, P, thresholds)[1]
+        for other in wrong:
+            assert not np.array_equal(pair_census_ref.ref_pairs(other, keys, P, thresholds)[1], want)
+        np.testing.assert_array_equal(eng.pair_census(thresholds, sample=sample), want)
+        # the threshold scan at a clear threshold near the 95 % quantile
+        clear = np.sort(census_ref.gap_thresholds(scores, 40))[1:-1]
+        t = float(clear[np.argmin(np.abs(clear - np.quantile(scores, 0.95)))])
+        census_ref.assert_clear(scores, [t])
+        hit = scores >= t
+        assert 0 < hit.sum() < scores.size
+        for other in wrong:
+            assert not np.array_equal(other >= t, hit)
+        s, ids = eng.scan_above(t, sample=sample)
+        got = assert_list_properties(s, ids, P)
+        np.testing.assert_array_equal(np.sort(got), keys[hit])
+        np.testing.assert_allclose(s, scores[np.searchsorted(keys, got)], rtol=scan_ref.RTOL, atol=0)
+        # the vote scan: a threshold clear of every scored slot's scores
+        tv = votes_ref.at_quantile(per[scored], votes_ref.clear_thresholds(per[scored], 41), 0.8)
+        census_ref.assert_clear(per[scored].reshape(-1), [tv])
+        votes_r, keys_r, mean_r, hist_r = votes_ref.ref_votes(per[scored], keys, tv)
+        for w in wrong_per:
+            assert not np.array_equal(votes_ref.ref_votes(w[scored], keys, tv)[3], hist_r)
+        np.testing.assert_array_equal(eng.vote_census(tv, sample=sample), hist_r)
+        for m in sorted({1, ns}):
+            v, s, ids = eng.consensus(tv, m, sample=sample)
+            got = scan_ref.packed(ids, P)
+            want_hits = votes_ref.ref_hits(votes_r, keys_r, mean_r, m)
+            np.testing.assert_array_equal(np.sort(got), np.array(sorted(want_hits), dtype=np.int64))
+            at = np.searchsorted(keys_r, got)
+            np.testing.assert_array_equal(v, votes_r[at])
+            np.testing.assert_allclose(s, mean_r[at], rtol=scan_ref.RTOL, atol=0)
+        # the quorum scan at one supported m: the minimum over the scored slots
+        m = ns
+        assert m in quorum_ref.supported(ns, eng.quorum_max_depth)
+        want_s, want_k = quorum_ref.ref_top(per[scored], keys, m, N)        # asserts the gaps
+        for w in wrong_per:
+            assert not np.array_equal(scan_ref.top(quorum_ref.quorum(w[scored], m), keys, N)[1][:N], want_k[:N])
+        s, ids = eng.quorum_top(N, m, sample=sample)
+        np.testing.assert_array_equal(ids, scan_ref.keys_to_ids(want_k[:N], P))
+        np.testing.assert_allclose(s, want_s[:N], rtol=scan_ref.RTOL, atol=0)
+    eng.close()
+
+
 # ------------------------------------------------------------------ (g) eps
 EPS = [1e-3, 1e-30]
 

@@ -43,6 +43,101 @@ def test_reference_eligibility_with_a_mask():
     assert sorted(np.flatnonzero(~ok).tolist()) == [3, 7, 9, 20]       # x, a known third, (3, 9) and (9, 20), y
 
 
+# ------------------------------------------------------------------ the designed rows of the wide tests
+def test_designed_places_are_permutations_in_the_intended_order():
+    for P in (600, ref.WIDE_P, ref.OVERFLOW_P):
+        for order in ref.ORDERS:
+            place = ref.designed_places(P, order)
+            np.testing.assert_array_equal(np.sort(place), np.arange(P))
+        assert (np.diff(ref.designed_places(P, "ascending")) == 1).all()
+        assert (np.diff(ref.designed_places(P, "descending")) == -1).all()
+        saw = ref.designed_places(P, "sawtooth")
+        for r in range(0, P, ref.ROUND):                # every round rises from the bottom of the grid to its top
+            part = saw[r:r + ref.ROUND]
+            rounds = (P + ref.ROUND - 1) // ref.ROUND
+            assert (np.diff(part) > 0).all() and part[0] < rounds
+            assert part.size < ref.ROUND or part[-1] >= P - 2 * rounds
+        assert not np.array_equal(ref.designed_places(P, "shuffled"), ref.designed_places(P, "shuffled", 1))
+
+
+@pytest.mark.parametrize("P,order,B", sorted({(P, order, B) for P, _, order, B in ref.DESIGNED}))
+def test_designed_rows_have_the_intended_order_and_clear_gaps(P, order, B):
+    """Per region the reference row is in the order of the places, and inside the top N + 1 of every
+    N the GPU tests ask, every adjacent relative gap exceeds 1e-9 (check_list's own assertion): for
+    the slots and for the ensemble."""
+    th, pr, place = ref.designed_params(P, order, B)
+    assert th.shape == (B, P, 2) and np.allclose(th.sum(axis=2), 1) and (pr > 0).all() and np.allclose(pr.sum(axis=4), 1)
+    Ns = [N for p, N, o, b in ref.DESIGNED if (p, o, b) == (P, order, B)]
+    for sample in list(range(B)) + ([None] if B > 1 else []):
+        for x, y in ref.three_queries(P):
+            row = ref.ref_rows(th, pr, x, y, sample)
+            ref.check_designed(row, place, P, x, y)
+            for N in Ns:
+                s, ids, gap = ref.want_list(row, P, x, y, N)
+                assert s.size == min(N, P - 2) and gap > 1e-9, (sample, (x, y), N, gap)
+    x, y = ref.three_queries(P)[2]                      # the regions differ: one vector for all three fails
+    row = ref.ref_row(th[0], pr[0], x, y)
+    t = th[0][scan_ref.rank_tables(P)[0], 0]
+    fit = [np.polyfit(t[c], row[c], 1) for c in ref.regions(P, x, y)]
+    assert all(abs(a[0] - b[0]) > 0.03 for a, b in zip(fit, fit[1:]))
+    assert all(f[0] > 0.05 for f in fit)
+
+
+@pytest.mark.parametrize("P,N", ref.LATE)
+def test_a_late_row_holds_its_nth_best_last(P, N):
+    """The order "late:N": for the query (0, 1) the last position is the N-th best of the row, every
+    other eligible position descends, and it is read in a round past the buffer's first overflow."""
+    th, pr, place = ref.designed_params(P, "late:%d" % N)
+    np.testing.assert_array_equal(np.sort(place), np.arange(P))
+    row = ref.ref_row(th[0], pr[0], 0, 1)
+    assert (np.diff(row[2:P - 1]) < 0).all()
+    assert int((row[2:] > row[P - 1]).sum()) == N - 1
+    assert (P - 1) // ref.ROUND > ref.cap_of(N) // ref.ROUND
+
+
+def test_the_stride_row_is_designed_too():
+    P = ref.STRIDE_P
+    th, pr, place = ref.designed_params(P, "shuffled")
+    for x, y in [(0, 1), (262150, 262170)]:
+        row = ref.ref_row(th[0], pr[0], x, y)
+        ref.check_designed(row, place, P, x, y)
+        assert ref.want_list(row, P, x, y, 8)[2] > 1e-9
+
+
+def test_the_cap_rule_matches_the_documented_cap_of_n():
+    """cap = 512, doubled until it holds 2 N; N is capped at mmsbm_screen_max_n() = 1024, so the
+    buffer is at most 2048 entries and the shapes above overflow it or not as they say."""
+    from trigenicinteractionpredictor_amd import _lib
+    assert _lib.load().mmsbm_screen_max_n() == 1024 == max(ref.WIDE_NS)
+    assert [ref.cap_of(n) for n in (1, 8, 100, 255, 256, 257, 512, 513, 1024)] == \
+        [512, 512, 512, 512, 512, 1024, 1024, 2048, 2048]
+    # the arrival-order rows overflow every buffer but the largest, which the rows of OVERFLOW_P overflow
+    assert ref.cap_of(512) == 1024 < ref.WIDE_P - 2 < ref.cap_of(513) == ref.cap_of(1024) < ref.OVERFLOW_P - 2
+    assert ref.STRIDE_P > 4096 * 4 * 16
+
+
+def test_check_list_rejects_a_swap_and_a_replaced_entry():
+    P, N = ref.WIDE_P, 256
+    th, pr, _ = ref.designed_params(P, "shuffled")
+    x, y = ref.three_queries(P)[2]
+    row = ref.ref_row(th[0], pr[0], x, y)
+    full_s, full_ids, _ = ref.want_list(row, P, x, y, N + 1)
+    s, ids = full_s[:N].copy(), full_ids[:N].copy()
+    ref.check_list((s, ids), row, P, x, y, N)
+    for at in (0, 100, N - 2):                          # two adjacent entries swapped
+        s2, ids2 = s.copy(), ids.copy()
+        s2[[at, at + 1]], ids2[[at, at + 1]] = s[[at + 1, at]], ids[[at + 1, at]]
+        with pytest.raises(AssertionError):
+            ref.check_list((s2, ids2), row, P, x, y, N)
+    for at in (0, 100, N - 1):                          # an entry replaced by the (N + 1)-th
+        s2, ids2 = s.copy(), ids.copy()
+        s2[at], ids2[at] = full_s[N], full_ids[N]
+        with pytest.raises(AssertionError):
+            ref.check_list((s2, ids2), row, P, x, y, N)
+    with pytest.raises(AssertionError):                 # the N-th dropped: a list one short
+        ref.check_list((s[:-1], ids[:-1]), row, P, x, y, N)
+
+
 # ------------------------------------------------------------------ screen_known
 def brute_known(m, pairs, exclude):
     _, rank = scan_ref.rank_tables(m.P)
