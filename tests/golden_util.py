@@ -92,3 +92,67 @@ def joint_load(case, name):
         meta = json.load(f)
     vec = np.load(os.path.join(d, name + ".npz"), allow_pickle=False)
     return meta, vec, os.path.join(d, "train.dat"), os.path.join(d, "test.dat")
+
+
+# ---- reference fixtures above K = 10 (tests/golden/make_largek_golden.py) ----
+# tests/golden/largek/<fold>/K<k>_s<seed>.{npz,json} for the folds "tiny" and "multi" (inputs:
+# tests/golden/<fold>/{train,test}.dat) and tests/golden/largek/joint/tiny/ for the joint model
+# (inputs: tests/golden/joint/tiny/).  The link tables are in the input folds' own metadata.
+LARGEK = os.path.join(GOLDEN, "largek")
+LARGEK_JOINT = os.path.join(LARGEK, "joint")
+PR_WALK_CELLS = 100     # cells of the strided walk of pr_index
+PR_FULL_MAX_K = 17      # the files hold the whole p of the last snapshot up to this K
+
+
+def pr_digest(pr):
+    """SHA-256 (uint8[32]) of p as C-contiguous little-endian float64 in the nesting [K][K][K][R]."""
+    import hashlib
+    raw = np.ascontiguousarray(pr, dtype=np.float64).astype("<f8", copy=False).tobytes()
+    return np.frombuffer(hashlib.sha256(raw).digest(), dtype=np.uint8).copy()
+
+
+def pr_index(K, R=2):
+    """The flat indices into p [K][K][K][R] that the files keep at every snapshot, a rule of K
+    alone: the cells n = 0, s, 2s, ... of an evenly strided walk over the K^3 cells (s odd, about
+    K^3 / PR_WALK_CELLS), the eight corner cells (a, b, c in {0, K - 1}) and the diagonal
+    (i, i, i); for each cell every rating.  Sorted, at most 512 entries up to K = 32."""
+    cells = K ** 3
+    stride = -(-cells // PR_WALK_CELLS) | 1
+    pick = set(range(0, cells, stride))
+    ends = (0, K - 1)
+    pick.update((a * K + b) * K + c for a in ends for b in ends for c in ends)
+    pick.update((i * K + i) * K + i for i in range(K))
+    return np.array([n * R + r for n in sorted(pick) for r in range(R)], dtype=np.int64)
+
+
+def _largek_names(root):
+    out = []
+    for meta_path in glob.glob(os.path.join(root, "*", "K*_s*.json")):
+        name = os.path.basename(meta_path)[:-5]
+        k, seed = name[1:].split("_s")
+        out.append((os.path.basename(os.path.dirname(meta_path)), int(k), int(seed), name))
+    return [(fold, name) for fold, _, _, name in sorted(out)]
+
+
+def _largek_load(root, inputs, fold, name):
+    with open(os.path.join(root, fold, name + ".json"), encoding="utf-8") as f:
+        meta = json.load(f)
+    vec = np.load(os.path.join(root, fold, name + ".npz"), allow_pickle=False)
+    return meta, vec, os.path.join(inputs, fold, "train.dat"), os.path.join(inputs, fold, "test.dat")
+
+
+def largek_cases():
+    """(fold, name) of the triplet-model files, by fold, K and seed."""
+    return _largek_names(LARGEK)
+
+
+def largek_load(fold, name):
+    return _largek_load(LARGEK, GOLDEN, fold, name)
+
+
+def largek_joint_cases():
+    return _largek_names(LARGEK_JOINT)
+
+
+def largek_joint_load(fold, name):
+    return _largek_load(LARGEK_JOINT, JOINT, fold, name)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from golden_util import GOLDEN, cases, load
+from parity_util import gm_valid_cs as _gm_valid_cs
 
 pytestmark = pytest.mark.gpu
 
@@ -668,16 +669,6 @@ def test_kernel_family_matches_oracle(tmp_path, monkeypatch, K, env):
     np.testing.assert_allclose(np.array(m.pr), pr_o, rtol=RTOL, atol=ATOL)
     np.testing.assert_allclose(m.compute_likelihood("train"), L_o, rtol=RTOL)
     np.testing.assert_allclose(m.compute_likelihood("test"), LT_o, rtol=RTOL)
-
-
-def _gm_valid_cs(K):
-    """GM<K>::cs_ok: workgroups per S part that divide the NQ fixed X groups of QC chunks (up to
-    four above K = 16 -- at K >= 25 on plans with fewer parts than CUs, like these -- two at
-    K <= 16) and keep one workgroup's S accumulators within 8 chunks (csrc/mmsbm.hip GM)."""
-    nch = (K * K + 63) // 64
-    qc = (nch + 1) // 2 if K <= 16 else (nch + 3) // 4  # (K >= 25: these small plans take GM::Q4)
-    nq = (nch + qc - 1) // qc
-    return [cs for cs in range(1, nq + 1) if nq % cs == 0 and (cs > 1 or nch <= 8) and (nq // cs) * qc <= 8]
 
 
 @pytest.mark.parametrize("K", [13, 16, 20, 22, 25, 30])

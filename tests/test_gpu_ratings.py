@@ -156,7 +156,7 @@ def test_forced_unit_split_matches_oracle(monkeypatch, K):
 
 
 def test_gm_workgroups_per_part_keep_bits_at_three_ratings(monkeypatch):
-    from test_gpu_parity import _gm_valid_cs
+    from parity_util import gm_valid_cs as _gm_valid_cs
     K, R = 20, 3
     valid = _gm_valid_cs(K)
     assert len(valid) >= 2, valid
