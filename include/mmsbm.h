@@ -473,6 +473,53 @@ int mmsbm_scan_quorum_topn_masked(mmsbm_ctx *ctx, const int32_t *order, const in
                                   void *ws, int64_t ws_bytes, double *out_scores, int32_t *out_ids,
                                   int64_t *out_count, void *stream);
 
+/* Dispute scan: the exact top N of the scan's eligible triples ranked by the spread of their restart
+ * scores: on which novel triples do the restarts disagree most.  order, known, n_known, theta, pr, N,
+ * ws, stream, eligibility, the packed key and the total order (score descending; equal scores:
+ * smaller packed key first) are mmsbm_scan_quorum_topn's, and so is the contract, word for word, with
+ * the spread d_t in out_scores.
+ * The scored slots are the ns = active-prefix slots; sample must be -1.  A slot's own score is the
+ * vote scan's and the quorum scan's: the bits a single-sample call on that slot forms.  For a trim
+ * t >= 0 with ns - 2 t >= 2 the spread of a triple is d_t = q_{1+t} - q_{ns-t}, q_m the quorum scan's
+ * m-th largest slot score: t = 0 is the range max - min, t = 1 drops the single highest and the
+ * single lowest restart, t = (ns - 2) / 2 on an even ns is the gap between the two middle scores.
+ * d_t is one IEEE subtraction of two slot scores; nothing else is combined across slots; d_t >= +0.
+ * Result (device), as for mmsbm_scan_quorum_topn: the first *out_count rows of out_scores f64[N] and
+ * out_ids int32[N][3] hold the best triples under the total order; *out_count < N when fewer are
+ * eligible (P < 3: 0); the tail is NaN / -1.  The list is unique: it does not depend on the grid, the
+ * arrival order or the batch the slots sit in.
+ * The kernel keeps, per tile element, two sorted lists of depth t + 1 in registers (the largest and
+ * the smallest scores); t <= mmsbm_scan_spread_max_trim() (3: every legal trim for ns <= 9); a legal
+ * trim above it is MMSBM_ERR_UNSUPPORTED.  Every slot of every tile is formed: a spread only grows as
+ * slots arrive, so there is no early exit.  The environment variable
+ * MMSBM_SCAN_SPREAD_GRID=<workgroups> lowers the grid (measurement; the result does not depend on it).
+ * Checked before any device call: a NULL ctx, order, theta, pr, out_scores, out_ids or out_count,
+ * N < 1, sample >= 0 or fewer than two active slots (one restart has no spread), trim < 0 or
+ * ns - 2 trim < 2, a bad known-key table or a missing, misaligned or small workspace:
+ * MMSBM_ERR_INVALID; K outside [1, MMSBM_MAX_K], N above mmsbm_scan_max_n(), P above 2 000 000, a legal
+ * trim above the cap or an ensemble whose W tile exceeds 64 KiB of LDS (the scan's rule):
+ * MMSBM_ERR_UNSUPPORTED.  Outputs and context are intact after a refusal.
+ * ws: mmsbm_scan_spread_workspace_bytes(ctx, N) bytes of device scratch, 16-byte aligned, the
+ * caller's; its size follows the context's shape and N only.  theta and pr are only read; all
+ * launches go to `stream` and nothing synchronises.  Needs R >= 2.
+ * mmsbm_scan_spread_topn_masked takes the pair mask of mmsbm_scan_census_masked behind n_known, under
+ * mmsbm_scan_quorum_topn_masked's contract: the same workspace, P <= 16384 (MMSBM_ERR_UNSUPPORTED
+ * above), a NULL mask MMSBM_ERR_INVALID; an all-zero mask returns the unmasked list, and a mask
+ * returns the unmasked call's list with the keys of every triple that contains a blocked pair added
+ * to `known`, bit for bit; the pruning bounds, the seeding pass's included, are formed from
+ * masked-eligible candidates only.  Replaces nothing in the reference. */
+int mmsbm_scan_spread_max_trim(void);
+int mmsbm_scan_spread_workspace_bytes(const mmsbm_ctx *ctx, int32_t N, int64_t *bytes);
+int mmsbm_scan_spread_topn(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known, int64_t n_known,
+                           const double *theta, const double *pr, int32_t sample, int32_t trim,
+                           int32_t N, void *ws, int64_t ws_bytes, double *out_scores,
+                           int32_t *out_ids, int64_t *out_count, void *stream);
+int mmsbm_scan_spread_topn_masked(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known,
+                                  int64_t n_known, const uint32_t *mask, const double *theta,
+                                  const double *pr, int32_t sample, int32_t trim, int32_t N,
+                                  void *ws, int64_t ws_bytes, double *out_scores, int32_t *out_ids,
+                                  int64_t *out_count, void *stream);
+
 /* Screen scan: for each query PAIR of genes, the score of Model.do_prediction (:530-547, no eps) of
  * every third gene, and the exact top N of them: what crossing the double-mutant query against the
  * array is predicted to find.  Notation as for mmsbm_partners_topn: order[P] (device) = the gene ids

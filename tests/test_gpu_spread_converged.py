@@ -1,0 +1,138 @@
+"""The dispute scan on converged fits: the ensembles of converged_ref.SCAN_SETS (three seeds each;
+the single-sample set has no spread), tests/golden/converged/.
+
+On a converged fit the restarts sit in different optima and hundreds of triples have a spread of
+1 - O(eps): the top of the list crowds, adjacent gaps of the reference's top 4096 lie below the 4e-9
+two spreads can move against each other, and the ORDER of a top-N list is not determined by the
+reference.  Its SET is, wherever the reference's absolute gap between the N-th and the (N + 1)-th
+spread exceeds census_ref.GAP (1e-7, 25 times that): the lists are compared there, as
+converged_ref.check_set_cut compares, with the spread's absolute tolerance RTOL (hi + lo)
+(tests/spread_ref.py).  Then exactly, without a tolerance, against the slots' own threshold scans.
+"""
+from math import comb
+
+import numpy as np
+import pytest
+
+import census_ref
+import converged_ref as cr
+import scan_ref
+import spread_ref
+from scan_gpu import engine
+from scan_ref import bits, packed
+
+pytestmark = pytest.mark.gpu
+
+GRID = "MMSBM_SCAN_SPREAD_GRID"
+SETS = [label for label, names in cr.SCAN_SETS.items() if len(names) >= 2]
+PARAMS = [(label, known) for label in SETS for known in cr.KNOWN]
+cases = pytest.mark.parametrize("label,known", PARAMS, ids=["%s-%s" % c for c in PARAMS])
+
+
+@pytest.fixture(autouse=True)
+def no_grid_override(monkeypatch):
+    monkeypatch.delenv(GRID, raising=False)
+
+
+def same(x, y):
+    assert len(x) == len(y)
+    for u, v in zip(x, y):
+        assert u.dtype == v.dtype and u.shape == v.shape and bits(u) == bits(v)
+
+
+def clear_cuts(desc, lo, hi):
+    """The cut positions n in [lo, hi] of a DESCENDING spread list at which a top-n set is
+    determined: the ABSOLUTE gap between the n-th and the (n + 1)-th spread exceeds census_ref.GAP."""
+    s = np.asarray(desc, dtype=np.float64)
+    assert (s[:-1] >= s[1:]).all()
+    n = np.arange(max(int(lo), 1), min(int(hi), s.size - 1) + 1)
+    return n[(s[n - 1] - s[n]) > census_ref.GAP]
+
+
+def pick_cuts(desc):
+    """The two N: the largest clear cut <= 4096 and the middle one of [64, 512]."""
+    big, small = clear_cuts(desc, 513, 4096), clear_cuts(desc, 64, 512)
+    assert big.size and small.size
+    return int(big[-1]), int(small[small.size // 2])
+
+
+def check_set_cut(got_scores, got_ids, d, tol, ref_keys, n, known, P):
+    """converged_ref.check_set_cut for spreads: on the reference alone, n is a clear cut; then the
+    returned key set is the reference's top-n set, every spread is within its own key's absolute
+    tolerance of the reference, and the list is sorted by its own bits under the scan's order."""
+    want_s, want_k = scan_ref.top(d, ref_keys, n, known)
+    assert want_s.size == n + 1 and clear_cuts(want_s, n, n).size == 1, ("not a clear cut", n)
+    assert got_ids.dtype == np.int32 and got_scores.dtype == np.float64
+    assert got_ids.shape == (n, 3) and got_scores.shape == (n,)
+    assert np.isfinite(got_scores).all() and (got_scores >= 0).all()
+    got_k = packed(got_ids, P)
+    np.testing.assert_array_equal(got_ids, scan_ref.keys_to_ids(got_k, P))
+    assert np.unique(got_k).size == n, "repeated keys"
+    missing, extra = np.setdiff1d(want_k[:n], got_k), np.setdiff1d(got_k, want_k[:n])
+    assert not missing.size and not extra.size, ("missing", missing[:5], "extra", extra[:5])
+    at = np.searchsorted(ref_keys, got_k)
+    np.testing.assert_array_equal(ref_keys[at], got_k)
+    assert (np.abs(got_scores - d[at]) <= tol[at]).all(), float(np.max(np.abs(got_scores - d[at]) - tol[at]))
+    down = got_scores[:-1] > got_scores[1:]
+    tie = (got_scores[:-1] == got_scores[1:]) & (got_k[:-1] < got_k[1:])
+    bad = np.flatnonzero(~(down | tie))
+    assert not bad.size, ("not in the scan's order at", bad[:5], got_scores[bad[:5]], got_k[bad[:5]])
+    if known is not None and len(known):
+        assert not np.isin(got_k, known).any()
+
+
+@cases
+def test_spread_top_at_clear_cuts(monkeypatch, label, known):
+    s = cr.scan_set(label)
+    kn = s.known[known]
+    eng = engine(s.theta, s.pr)
+    trims = eng.spread_trims()
+    assert trims == spread_ref.legal(s.per.shape[0])
+    for t in trims:
+        d, tol = spread_ref.spread(s.per, t), spread_ref.atol(s.per, t)
+        desc = cr.eligible_desc(d, s.keys, kn)
+        # the order inside is not determined: the reason for comparing sets
+        assert int(np.count_nonzero(desc[:4095] - desc[1:4096] <= 4 * spread_ref.RTOL)) > 0
+        for n in pick_cuts(desc):
+            got = eng.spread_top(n, t, kn)
+            check_set_cut(got[0], got[1], d, tol, s.keys, n, kn, s.P)
+            monkeypatch.setenv(GRID, "7")
+            same(eng.spread_top(n, t, kn), got)
+            monkeypatch.delenv(GRID)
+    eng.close()
+
+
+@pytest.mark.parametrize("label", SETS)
+def test_exact_against_the_slots_threshold_scans(label):
+    """No tolerance, crowded or not: sorted[B - 1 - t] - sorted[t] per key of the slots' own
+    scan_above lists under the total order is spread_top's list in bits and ids, with and without a
+    pair mask."""
+    s = cr.scan_set(label)
+    B, P = s.per.shape[0], s.P
+    eng = engine(s.theta, s.pr)
+    keys, per = None, []
+    for slot in range(B):
+        sc, ids = eng.scan_above(0.0, sample=slot)                  # every triple, whatever its score
+        assert sc.size == comb(P, 3)
+        k = packed(ids, P)
+        at = np.argsort(k)
+        assert keys is None or np.array_equal(keys, k[at])
+        keys = k[at]
+        per.append(sc[at])
+    per = np.sort(np.stack(per), axis=0)
+    mask, blocked = cr.random_pair_mask(P)
+    for name in cr.KNOWN:
+        kn = s.known[name]
+        both = np.union1d(np.zeros(0, np.int64) if kn is None else kn, blocked).astype(np.int64)
+        for t in eng.spread_trims():
+            for known, kw in ((kn, {}), (both, {"mask": mask})):
+                keep = np.ones(keys.size, bool) if known is None else ~np.isin(keys, known)
+                d = (per[B - 1 - t] - per[t])[keep]
+                order = np.lexsort((keys[keep], -d))
+                want_s, want_k = d[order], keys[keep][order]
+                for n in (64, 4096):
+                    got_s, got_ids = eng.spread_top(n, t, kn, **kw)
+                    assert got_s.size == n
+                    assert bits(got_s) == bits(want_s[:n])
+                    np.testing.assert_array_equal(got_ids, scan_ref.keys_to_ids(want_k[:n], P))
+    eng.close()

@@ -50,7 +50,8 @@ def random_known(P, n, seed):
 
 
 ENTRY = {"census": "mmsbm_scan_census", "pair_census": "mmsbm_pair_census", "scan_above": "mmsbm_scan_above",
-         "scan_votes": "mmsbm_scan_votes", "scan": "mmsbm_scan_topn", "scan_quorum": "mmsbm_scan_quorum_topn"}
+         "scan_votes": "mmsbm_scan_votes", "scan": "mmsbm_scan_topn", "scan_quorum": "mmsbm_scan_quorum_topn",
+         "scan_spread": "mmsbm_scan_spread_topn"}
 
 
 def resident(eng, known, sample):

@@ -89,6 +89,12 @@ SIGNATURES = {
                                          _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mmsbm_scan_quorum_topn_masked": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i32, _c_i32, _c_i32, _vp,
                                                _c_i64, _vp, _vp, _vp, _vp]),
+    "mmsbm_scan_spread_max_trim": (_c_int, []),
+    "mmsbm_scan_spread_workspace_bytes": (_c_int, [_vp, _c_i32, ctypes.POINTER(_c_i64)]),
+    "mmsbm_scan_spread_topn": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_i32, _c_i32, _c_i32, _vp, _c_i64, _vp,
+                                        _vp, _vp, _vp]),
+    "mmsbm_scan_spread_topn_masked": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i32, _c_i32, _c_i32, _vp,
+                                               _c_i64, _vp, _vp, _vp, _vp]),
     "mmsbm_screen_max_n": (_c_int, []),
     "mmsbm_screen_workspace_bytes": (_c_int, [_vp, _c_i64, _c_i32, ctypes.POINTER(_c_i64)]),
     "mmsbm_screen_topn": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i32, _c_i32, _vp, _c_i64,

@@ -208,6 +208,48 @@ struct Score {
     q = L[D - 1];
     return true;
   }
+
+  // The dispute scan (scan_spread.hip): the spread d_t = q_{1+t} - q_{ns-t} of the slots' own scores,
+  // per element, for the trim t = D - 1.  The same operands in the same order as tile_mean, each
+  // slot's accumulator formed from zero (that slot's single-sample score, bit for bit) and inserted
+  // into two per-element sorted lists of depth D, as tile_quorum inserts it into one: `top` keeps the
+  // D largest, descending, and `bot` the D smallest, ascending.  The result is one IEEE subtraction,
+  // top[D - 1] - bot[D - 1]: the (1 + t)-th largest minus the (1 + t)-th smallest.  The caller
+  // guarantees ns >= 2 D, so both entries are slot scores (no start value is left) and the result is
+  // >= +0.  Every slot is formed: a spread only grows as slots arrive, so none can be skipped.
+  template <int D>
+  static __device__ __forceinline__ d4v tile_spread(const double* W, const double* __restrict__ thT, int ns,
+                                                    int RB, int P16, int wb, int c0, int m, int kk) {
+    const double inf = __builtin_huge_val();
+    d4v top[D], bot[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      top[j] = d4v{-inf, -inf, -inf, -inf};
+      bot[j] = d4v{inf, inf, inf, inf};
+    }
+    for (int s = 0; s < ns; ++s) {
+      const double* __restrict__ tc = thT + ((size_t)s * KP + kk) * P16 + c0 + m;
+      const double* wr = W + ((size_t)s * RB + wb * 16 + m) * WS + kk;
+      d4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[4 * ks], tc[(size_t)(4 * ks) * P16], acc, 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        double x = acc[i], y = acc[i];
+#pragma unroll
+        for (int j = 0; j < D; ++j) {  // each list keeps the better of the two, x / y carry the other on
+          const double hi = fmax(top[j][i], x), lo = fmin(top[j][i], x);
+          top[j][i] = hi;
+          x = lo;
+          const double lo2 = fmin(bot[j][i], y), hi2 = fmax(bot[j][i], y);
+          bot[j][i] = lo2;
+          y = hi2;
+        }
+      }
+    }
+    return top[D - 1] - bot[D - 1];
+  }
 };
 
 }  // namespace scan_score

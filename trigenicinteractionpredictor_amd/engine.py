@@ -225,7 +225,7 @@ class EMEngine:
 
     def scan_workspace(self, family: str, *size_args) -> torch.Tensor:
         """The scratch of one family ("scan", "partners", "census", "pair_census", "scan_above",
-        "scan_votes", "scan_quorum", "screen"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device."""
+        "scan_votes", "scan_quorum", "scan_spread", "screen"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device."""
         nbytes = ctypes.c_int64()
         _lib.check(getattr(self.lib, "mmsbm_%s_workspace_bytes" % family)(self.ctx, *size_args,
                                                                           ctypes.byref(nbytes)))
@@ -669,6 +669,59 @@ class EMEngine:
         MMSBMError (MMSBM_ERR_UNSUPPORTED).  known, sample: as for scan_top.  mask: as for census
         (mmsbm_scan_quorum_topn_masked): the exact top n over the triples without a blocked pair."""
         scores, ids, count = self.quorum_top_async(n, min_votes, known, sample, stream, mask)
+        if stream is not None:
+            stream.synchronize()
+        m = int(count.cpu()[0])
+        return scores[:m].cpu().numpy(), ids[:m].cpu().numpy()
+
+    # ---------------------------------------------------------- dispute scan
+    @property
+    def spread_max_trim(self) -> int:
+        """mmsbm_scan_spread_max_trim(): the largest trim the kernel holds sorted lists for."""
+        return int(self.lib.mmsbm_scan_spread_max_trim())
+
+    def spread_trims(self) -> list:
+        """The trims spread_top takes for the current active prefix: t >= 0 with active - 2 t >= 2,
+        up to spread_max_trim.  Empty with fewer than two active slots."""
+        return [t for t in range(self.spread_max_trim + 1) if self.active - 2 * t >= 2]
+
+    def _spread_trim(self, trim) -> int:
+        """-> trim as an int; ValueError for fewer than two active slots and for an illegal trim."""
+        ns, trim = self.active, int(trim)
+        if ns < 2:
+            raise ValueError("%d active slot: one restart has no spread" % ns)
+        if trim < 0 or ns - 2 * trim < 2:
+            raise ValueError("trim %d outside [0, %d]: %d active slots must keep two scores"
+                             % (trim, (ns - 2) // 2, ns))
+        return trim
+
+    def spread_top_async(self, n: int, trim: int = 0, known: np.ndarray = None, stream=None, mask=None):
+        """spread_top without the host copy: -> device tensors (scores f64[n], ids int32[n][3],
+        count int64[1]); rows from `count` on are NaN / -1.  Nothing synchronises."""
+        n = int(n)
+        trim = self._spread_trim(trim)      # ValueError before anything is uploaded
+        entry = self.lib.mmsbm_scan_spread_topn if mask is None else self.lib.mmsbm_scan_spread_topn_masked
+        with self._scan_call(known, None, stream, mask) as (head, s):
+            ws = self.scan_workspace("scan_spread", n)
+            scores = torch.empty(n, dtype=torch.float64, device=self.device)
+            ids = torch.empty((n, 3), dtype=torch.int32, device=self.device)
+            count = torch.empty(1, dtype=torch.int64, device=self.device)
+            _lib.check(entry(*head, trim, n, _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids), _ptr(count),
+                             s.cuda_stream))
+        return scores, ids, count
+
+    def spread_top(self, n: int, trim: int = 0, known: np.ndarray = None, stream=None, mask=None):
+        """The n eligible triples on which the active slots disagree most (include/mmsbm.h
+        mmsbm_scan_spread_topn): ranked by d_t = q_{1+t} - q_{ns-t}, t = trim, q_m quorum_top's m-th
+        largest of the ns = active slots' own scores.  trim = 0: the range max - min; 1: without the
+        single highest and the single lowest restart; (ns - 2) // 2 on an even ns: the gap between
+        the two middle scores.  -> (scores f64[n'], ids int32[n'][3] in key order) on the host, best
+        first under scan_top's total order, n' <= n.  Fewer than two active slots and a trim outside
+        spread_trims' rule (t >= 0, ns - 2 t >= 2) raise ValueError; a legal trim above
+        spread_max_trim raises MMSBMError (MMSBM_ERR_UNSUPPORTED).  known: as for scan_top.  mask: as
+        for census (mmsbm_scan_spread_topn_masked): the exact top n over the triples without a
+        blocked pair."""
+        scores, ids, count = self.spread_top_async(n, trim, known, stream, mask)
         if stream is not None:
             stream.synchronize()
         m = int(count.cpu()[0])

@@ -84,6 +84,22 @@ without a threshold chosen in advance.
                            every M up to -n 8, the four lowest and the four highest M beyond.  Not
                            with --best: one restart has no quorum.
 
+One more comes from the dispute scan (`EMEngine.spread_top`, mmsbm_scan_spread_topn): the opposite
+question.  Every table above asks what the restarts agree on; this one asks where they disagree most,
+which are the triples whose measurement would constrain the model most and the predictions to trust
+least.
+    --disputed FILE        the --top eligible triples (under --exclude) ranked by the spread of the -n
+                           restarts' own P(r = 1): the (1 + T)-th largest minus the (1 + T)-th
+                           smallest, --disputed-trim T (default 0: the range max - min; 1: without the
+                           single highest and the single lowest restart, so that one stray restart
+                           makes no dispute; T >= 0 must leave two scores, -n - 2 T >= 2, and is at
+                           most MAX_SPREAD_TRIM = 3: every legal T up to -n 9).  The header comments
+                           give `# samples` and `# disputed trim`; then rank, spread, mean, min, max,
+                           ids, names rows, best first, equal spreads by key.  mean, min and max are
+                           the listed triple's ensemble mean and its lowest and highest restart
+                           score, from the predict kernel.  Not with --best and not with -n 1: one
+                           restart has no spread.
+
 Two options restrict every table they apply to by PAIRS of genes (scan.pair_mask, the masked census
 and threshold scan, mmsbm_scan_census_masked / mmsbm_scan_above_masked): a triple that contains a
 blocked pair is not eligible.
@@ -92,7 +108,8 @@ blocked pair is not eligible.
     --block-pairs FILE     two gene names or ids per line, tab or space separated: these pairs are
                            blocked, such as the pairs known to interact digenically.
 They apply to the main table (which then goes through `EMEngine.scan_top_any`: masked censuses find
-the cut, the masked threshold scan lists above it), --census, --network and --screen, and combine by OR.  With
+the cut, the masked threshold scan lists above it), --census, --network, --screen and --disputed (whose
+kernel takes the mask), and combine by OR.  With
 --gene / --all-genes, --pairs, --gene-census, --consensus and --quorum, whose kernels take no mask,
 they are refused.  --heldout-ranks is not restricted by them.
 
@@ -133,6 +150,7 @@ MAX_SCREEN_TOP = 1024    # mmsbm_screen_max_n(): the largest N per query pair
 DEFAULT_SCREEN_TOP = 20  # --screen without --screen-top: the rows per query pair
 MAX_SCREEN_QUERIES = 65535   # the most query pairs one mmsbm_screen_topn call takes
 MAX_QUORUM_DEPTH = 4     # mmsbm_scan_quorum_max_depth(): the deepest sorted list of the quorum scan
+MAX_SPREAD_TRIM = 3      # mmsbm_scan_spread_max_trim(): the largest trim of the dispute scan
 DEFAULT_THRESHOLDS = (0.99, 0.95, 0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3, 0.2, 0.1, 0.05, 0.02, 0.01, 0.005,
                       0.002, 0.001)   # --census without --thresholds
 
@@ -655,6 +673,8 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [--consensus-limit=] <the most rows --consensus may write; default 10000000>
     [--quorum=] <TSV file: the --top eligible triples by their M-th best restart score>
     [--quorum-votes=] <M, an integer in [1, restarts]; default: all restarts (the minimum over them)>
+    [--disputed=] <TSV file: the --top eligible triples by the spread of the restarts' scores>
+    [--disputed-trim=] <T, an integer >= 0 with restarts - 2 T >= 2, at most 3; default 0 (max - min)>
     [--allow-genes=] <file, one gene name or id per line: only triples of these genes>
     [--block-pairs=] <file, two gene names or ids per line: no triple that contains such a pair>
     [--screen=] <TSV file: per query pair of genes, its most probable third genes>
@@ -676,7 +696,8 @@ def parse(argv):
     # --consensus does the same with its four (consensus, consensus_threshold, min_votes,
     # consensus_limit) and --quorum with its two (quorum, quorum_votes); --allow-genes and
     # --block-pairs add their two (allow_genes, block_pairs) when one of them is given; --screen adds
-    # its four (screen, screen_top, query_pairs, screen_best) in the same way
+    # its four (screen, screen_top, query_pairs, screen_best) in the same way, and --disputed its two
+    # (disputed, disputed_trim)
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
@@ -687,7 +708,8 @@ def parse(argv):
                                                         "consensus-threshold=", "min-votes=",
                                                         "consensus-limit=", "quorum=", "quorum-votes=",
                                                         "allow-genes=", "block-pairs=", "screen=",
-                                                        "screen-top=", "query-pairs=", "screen-best="])
+                                                        "screen-top=", "query-pairs=", "screen-best=",
+                                                        "disputed=", "disputed-trim="])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -770,6 +792,13 @@ def parse(argv):
                     print("\n\nERROR: --quorum-votes should be an integer number in [1, restarts (-n)]")
                     raise cli.ArgError()
                 cfg["quorum_votes"] = int(arg)
+            elif opt == "--disputed":
+                cfg["disputed"] = arg
+            elif opt == "--disputed-trim":
+                if not int(arg) >= 0:
+                    print("\n\nERROR: --disputed-trim should be an integer number >= 0")
+                    raise cli.ArgError()
+                cfg["disputed_trim"] = int(arg)
             elif opt == "--allow-genes":
                 cfg["allow_genes"] = arg
             elif opt == "--block-pairs":
@@ -830,6 +859,23 @@ def parse(argv):
             raise cli.ArgError()
         if cfg["quorum"] and cfg["best"]:
             print("\n\nERROR: --quorum ranks by a score across the restarts: it does not go with --best")
+            raise cli.ArgError()
+    if any(key in cfg for key in ("disputed", "disputed_trim")):
+        cfg.setdefault("disputed", None)
+        cfg.setdefault("disputed_trim", 0)      # the range, max - min
+        if cfg["samples"] < 2:                  # -n may come after --disputed-trim
+            print("\n\nERROR: --disputed ranks by the spread across the restarts: it needs -n 2 or more")
+            raise cli.ArgError()
+        if cfg["disputed_trim"] not in spread_trims(cfg["samples"], None):
+            print("\n\nERROR: --disputed-trim %d of %d restarts: the trim must leave two scores "
+                  "(restarts - 2 T >= 2)" % (cfg["disputed_trim"], cfg["samples"]))
+            raise cli.ArgError()
+        if cfg["disputed_trim"] > MAX_SPREAD_TRIM:
+            print("\n\nERROR: --disputed-trim %d: only trims up to %d are supported"
+                  % (cfg["disputed_trim"], MAX_SPREAD_TRIM))
+            raise cli.ArgError()
+        if cfg["disputed"] and cfg["best"]:
+            print("\n\nERROR: --disputed ranks by the spread across the restarts: it does not go with --best")
             raise cli.ArgError()
     if any(key in cfg for key in ("allow_genes", "block_pairs")):
         cfg.setdefault("allow_genes", None)
@@ -1036,6 +1082,28 @@ def quorum_table(eng, model, cfg, known, extras):
     extras["quorum"] = (eng.active, cfg["quorum_votes"], quorum_rows(model.id_gene, scores, ids, probs))
 
 
+def spread_trims(samples: int, cap=MAX_SPREAD_TRIM) -> list:
+    """The trims the dispute scan takes for `samples` restarts (EMEngine.spread_trims): t >= 0 with
+    samples - 2 t >= 2, up to `cap` (None: every legal one)."""
+    legal = range(max(0, (int(samples) - 2) // 2 + 1)) if int(samples) >= 2 else range(0)
+    return [t for t in legal if cap is None or t <= cap]
+
+
+def spread_rows(id_gene, scores, ids, probs):
+    """spread_top's arrays and predict's probs f64[samples][n] on those ids -> rows [rank, spread,
+    mean, min, max, "i_j_k", names], formed as quorum_rows forms its rows."""
+    return quorum_rows(id_gene, scores, ids, probs)
+
+
+def spread_table(eng, model, cfg, known, extras, mask=None):
+    """The driver's --disputed table into `extras` (see run)."""
+    if not cfg.get("disputed"):
+        return
+    scores, ids = eng.spread_top(cfg["top"], cfg["disputed_trim"], known, **_masked(mask))
+    probs = eng.predict(ids)[:eng.active] if len(scores) else np.zeros((eng.active, 0))
+    extras["disputed"] = (eng.active, cfg["disputed_trim"], spread_rows(model.id_gene, scores, ids, probs))
+
+
 def run(cfg, out=print, extras=None):
     """Fit the restarts as one batch, scan once, return the rows [rank, probability, ids, names]
     (with --gene / --all-genes: [query, rank, probability, ids, names], by query then rank).
@@ -1045,7 +1113,8 @@ def run(cfg, out=print, extras=None):
     "network" = rows [rank, probability, ids, names] for --network, and "consensus" = (restarts,
     threshold, hist, rows [rank, votes, probability, ids, names]) for --consensus, and "quorum" =
     (restarts, votes, rows [rank, quorum score, mean, min, max, ids, names]) for --quorum, and
-    "screen" = rows [query, rank, probability, ids, names] for --screen."""
+    "screen" = rows [query, rank, probability, ids, names] for --screen, and "disputed" = (restarts,
+    trim, rows [rank, spread, mean, min, max, ids, names]) for --disputed."""
     from .model import Model
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
@@ -1072,6 +1141,7 @@ def run(cfg, out=print, extras=None):
         consensus_table(eng, model, cfg, known, extras)
         quorum_table(eng, model, cfg, known, extras)
         screen_table(eng, model, cfg, known, sample, extras, pair_queries, mask)
+        spread_table(eng, model, cfg, known, extras, mask)
     if queries is not None:
         out("partner pairs of %d genes: %s" % (len(queries), "sample %d" % sample if sample is not None
                                                else "mean of %d samples" % B))
@@ -1126,6 +1196,14 @@ def write_quorum_tsv(samples, votes, rows, stream):
     stream.write("rank\tquorum\tmean\tmin\tmax\tids\tnames\n")
     for rank, q, mean, lo, hi, key, names in rows:
         stream.write("%d\t%r\t%r\t%r\t%r\t%s\t%s\n" % (rank, q, mean, lo, hi, key, "_".join(names)))
+
+
+def write_disputed_tsv(samples, trim, rows, stream):
+    stream.write("# samples\t%d\n" % samples)
+    stream.write("# disputed trim\t%d\n" % trim)
+    stream.write("rank\tspread\tmean\tmin\tmax\tids\tnames\n")
+    for rank, d, mean, lo, hi, key, names in rows:
+        stream.write("%d\t%r\t%r\t%r\t%r\t%s\t%s\n" % (rank, d, mean, lo, hi, key, "_".join(names)))
 
 
 def write_pairs_tsv(rows, stream):
@@ -1183,6 +1261,9 @@ def main(argv=None, out=print):
     if "screen" in extras:
         with open(cfg["screen"], "w", encoding="utf-8") as f:
             write_tsv(extras["screen"], f, partners=True)
+    if "disputed" in extras:
+        with open(cfg["disputed"], "w", encoding="utf-8") as f:
+            write_disputed_tsv(*extras["disputed"], f)
     partners = bool(cfg["genes"] or cfg["all_genes"])
     if cfg["out"]:
         with open(cfg["out"], "w", encoding="utf-8") as f:
