@@ -36,7 +36,8 @@ DEPS = {
           os.path.join(INCLUDE, "mmsbm.h")],
     SRC_PAIRS: [os.path.join(INCLUDE, "mmsbm.h"), os.path.join(INCLUDE, "mmsbm_pairs.h")],
     SRC_SCAN: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
-               os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(INCLUDE, "mmsbm.h")],
+               os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(PKG, "csrc", "scan_topn.h"),
+               os.path.join(INCLUDE, "mmsbm.h")],
     SRC_PARTNERS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_host.h"),
                    os.path.join(INCLUDE, "mmsbm.h")],
     SRC_CENSUS: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
@@ -52,11 +53,13 @@ DEPS = {
                      os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(PKG, "csrc", "scan_sweep.h"),
                      os.path.join(INCLUDE, "mmsbm.h")],
     SRC_SCAN_QUORUM: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
-                      os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(INCLUDE, "mmsbm.h")],
+                      os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(PKG, "csrc", "scan_topn.h"),
+                      os.path.join(INCLUDE, "mmsbm.h")],
     SRC_SCREEN: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_host.h"),
                  os.path.join(INCLUDE, "mmsbm.h")],
     SRC_SCAN_SPREAD: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
-                      os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(INCLUDE, "mmsbm.h")],
+                      os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(PKG, "csrc", "scan_topn.h"),
+                      os.path.join(INCLUDE, "mmsbm.h")],
 }
 
 

@@ -28,14 +28,18 @@
 // pass runs first: the same scan and merge over every 61st item, whose exact N-th score (a subset's
 // N-th best is such a lower bound too) is published before the full pass starts, so the full pass
 // appends about 61 N candidates in all instead of filling every buffer from nothing.  At the end each
-// workgroup writes its sorted best N; scan_merge_kernel (own launches, fan-in 32) merges the lists
-// with the same buffer and order.  The exact top N under a total order is unique: the result does
-// not depend on the grid, the arrival order or the batch.  Scores are never combined by atomics
-// and every sum has a fixed order.  The selection machinery (order, buffer, keep-best-N, merge) is
-// scan_select.h, shared with the partner scan (partners.hip); the score phase (prep, W rows, the
-// MFMA chain of a tile, the ensemble's sum and division) is scan_score.h, shared with the sweep of
-// the score census and the pair census (scan_sweep.h), whose scores therefore carry this kernel's
-// bits; the host prologue (shape, checks, launch, dispatch on K) is scan_host.h, shared by all four.
+// workgroup writes its sorted best N; scan_topn.h's merge kernel (own launches, fan-in 32) merges
+// the lists with the same buffer and order.  The exact top N under a total order is unique: the
+// result does not depend on the grid, the arrival order or the batch.  Scores are never combined by
+// atomics and every sum has a fixed order.  The selection machinery (order, buffer, keep-best-N,
+// merge) is scan_select.h, shared with the partner scan (partners.hip); the score phase (prep, W
+// rows, the MFMA chain of a tile, the ensemble's sum and division) is scan_score.h, shared with the
+// sweep of the score census and the pair census (scan_sweep.h), whose scores therefore carry this
+// kernel's bits; the host prologue (shape, checks, launch, dispatch on K) is scan_host.h, shared by
+// all four.  The plan and its workspace layout, the LDS sizing, the merge kernel and the host loop
+// over the seeding pass, the full pass and the merge levels are scan_topn.h, shared with the quorum
+// scan (scan_quorum.hip) and the dispute scan (scan_spread.hip): this file holds the kernel, the
+// call's own checks and the kernel's launch.
 
 #include <hip/hip_runtime.h>
 
@@ -47,18 +51,15 @@
 #include "scan_host.h"
 #include "scan_score.h"
 #include "scan_select.h"
+#include "scan_topn.h"
 
 namespace {
 
 using namespace scan_host;
 using namespace scan_select;
-using scan_score::scan_prep_kernel;
+using namespace scan_topn;
 using scan_score::Score;
 using scan_score::W_LDS_MAX;
-
-constexpr int SCAN_MAX_N = 4096; // documented cap of N (include/mmsbm.h)
-constexpr int SEED_STRIDE = 61;  // the seeding pass scans every 61st item (prime: spreads over a and b)
-constexpr int SEED_MIN_P = 200;  // below it one pass: the seeding launches would cost more than they save
 
 // ------------------------------------------------------------------------------------------
 // Scan
@@ -200,114 +201,18 @@ __global__ __launch_bounds__(NT) void scan_kernel(ScanArgs A) {
   if (threadIdx.x == 0) A.list_n[blockIdx.x] = cnt;
 }
 
-// ------------------------------------------------------------------------------------------
-// Merge: workgroup w keeps the best N of lists [FAN w, FAN (w + 1)); the last level (one
-// workgroup) writes the result: scores, gene ids in key order, count, NaN / -1 tail.
-// ------------------------------------------------------------------------------------------
-struct MergeArgs {
-  const double* in_s;
-  const long long* in_k;
-  const int* in_n;
-  int n_in;
-  double* out_s;      // next level's lists (null on the last level)
-  long long* out_k;
-  int* out_n;
-  const int* order;   // last level
-  double* scores;
-  int* ids;
-  long long* count;
-  unsigned long long* shared;  // last level of the seeding pass: publish the N-th score, no output
-  int N, cap, P;
-};
-
-__global__ __launch_bounds__(NT) void scan_merge_kernel(MergeArgs A) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  Sel* st = reinterpret_cast<Sel*>(smem);
-  double* cs = reinterpret_cast<double*>(smem + sizeof(Sel));
-  long long* ck = reinterpret_cast<long long*>(cs + A.cap);
-  if (threadIdx.x == 0) sel_init(st);
-  __syncthreads();
-  const int l0 = blockIdx.x * FAN, l1 = min(l0 + FAN, A.n_in);
-  wg_merge_lists(st, cs, ck, A.in_s, A.in_k, A.in_n, l0, l1, A.N, A.cap);
-  wg_keep_best(st, cs, ck, A.N, A.shared);  // seeding pass: publishes the subset's N-th score
-  if (A.shared) return;
-  const int cnt = st->count;
-  if (A.out_s) {
-    for (int i = threadIdx.x; i < cnt; i += NT) {
-      A.out_s[(size_t)blockIdx.x * A.N + i] = cs[i];
-      A.out_k[(size_t)blockIdx.x * A.N + i] = ck[i];
-    }
-    if (threadIdx.x == 0) A.out_n[blockIdx.x] = cnt;
-    return;
-  }
-  const long long PP = A.P;
-  for (int i = threadIdx.x; i < A.N; i += NT) {
-    if (i < cnt) {
-      const long long k = ck[i];
-      A.scores[i] = cs[i];
-      A.ids[3 * i] = A.order[k / (PP * PP)];
-      A.ids[3 * i + 1] = A.order[(k / PP) % PP];
-      A.ids[3 * i + 2] = A.order[k % PP];
-    } else {
-      A.scores[i] = __builtin_nan("");
-      A.ids[3 * i] = A.ids[3 * i + 1] = A.ids[3 * i + 2] = -1;
-    }
-  }
-  if (threadIdx.x == 0) *A.count = cnt;
-}
-
-// ------------------------------------------------------------------------------------------
-// Host side
-// ------------------------------------------------------------------------------------------
-struct ScanPlan {
-  ScanShape sh;
-  int N, cap, G, G2;
-  size_t off_thT, off_T, off_cs, off_ck, off_ls[2], off_lk[2], off_ln[2], total;
-};
-
-// Everything that sizes the workspace follows the context's shape and N only (not the sample
-// argument), so one workspace serves every call of that shape.
-int make_plan(const mmsbm_ctx* c, int N, ScanPlan* p) {
-  ScanShape& sh = p->sh;
-  if (int rc = scan_shape(c, "scan", &sh)) return rc;
-  if (N < 1) return fail(MMSBM_ERR_INVALID, "N=%d < 1", N);
-  if (N > SCAN_MAX_N) return fail(MMSBM_ERR_UNSUPPORTED, "N=%d above the scan's cap of %d", N, SCAN_MAX_N);
-  if (int rc = packed_keys_fit(sh)) return rc;
-  p->N = N;
-  p->cap = 512;
-  while (p->cap < 2 * N) p->cap <<= 1;
-  const long long per_cu = N <= 1024 ? 4 : N <= 2048 ? 2 : 1;
-  const long long items = std::max<long long>(1, (long long)sh.P * (sh.P16 / 16));
-  p->G = (int)std::min<long long>(per_cu * sh.ncu, items);
-  p->G2 = (p->G + FAN - 1) / FAN;
-  const size_t G = p->G, cap = p->cap;
-  size_t off = 256;  // [0, 256): the published threshold
-  score_workspace(sh, off, &p->off_thT, &p->off_T);
-  p->off_cs = off, off = align256(off + sizeof(double) * G * cap);
-  p->off_ck = off, off = align256(off + sizeof(long long) * G * cap);
-  const size_t nl[2] = {G, (size_t)p->G2};
-  for (int i = 0; i < 2; ++i) {
-    p->off_ls[i] = off, off = align256(off + sizeof(double) * nl[i] * N);
-    p->off_lk[i] = off, off = align256(off + sizeof(long long) * nl[i] * N);
-    p->off_ln[i] = off, off = align256(off + sizeof(int) * nl[i]);
-  }
-  p->total = off;
-  return MMSBM_OK;
-}
-
 }  // namespace
+
+// ------------------------------------------------------------------------------------------
+// Host side: the plan, the merge and the pass loop are scan_topn.h
+// ------------------------------------------------------------------------------------------
 
 extern "C" {
 
-int mmsbm_scan_max_n(void) { return SCAN_MAX_N; }
+int mmsbm_scan_max_n(void) { return TOPN_MAX_N; }
 
 int mmsbm_scan_workspace_bytes(const mmsbm_ctx* c, int32_t N, int64_t* bytes) {
-  if (!c || !bytes) return fail(MMSBM_ERR_INVALID, "null argument");
-  ScanPlan p;
-  int rc = make_plan(c, N, &p);
-  if (rc) return rc;
-  *bytes = (int64_t)p.total;
-  return MMSBM_OK;
+  return workspace_bytes(c, "scan", N, bytes);
 }
 
 int mmsbm_scan_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
@@ -315,8 +220,8 @@ int mmsbm_scan_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, in
                     int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count,
                     void* stream) {
   if (!c) return fail(MMSBM_ERR_INVALID, "null context");
-  ScanPlan p;
-  int rc = make_plan(c, N, &p);
+  TopNPlan p;
+  int rc = make_plan(c, "scan", N, &p);
   if (rc) return rc;
   if (!order || !theta || !pr || !out_scores || !out_ids || !out_count)
     return fail(MMSBM_ERR_INVALID, "null pointer");
@@ -327,69 +232,19 @@ int mmsbm_scan_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, in
                        &s0)))
     return rc;
   if ((rc = pick_wb(sh, "scan", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
-  const size_t cand_bytes = (size_t)p.cap * 16;
-  const bool cand_lds = sizeof(Sel) + w_bytes + cand_bytes <= (size_t)LDS_MAX;
-  const int lds = (int)(sizeof(Sel) + w_bytes + (cand_lds ? cand_bytes : 0));
-  const int merge_lds = (int)(sizeof(Sel) + cand_bytes);
+  const TopNLds l = lds_sizes(p, w_bytes, 0);
   const bool select = env_override("MMSBM_SCAN_SELECT", 1) != 0;  // measurement: the bare score phase
-
-  DeviceGuard g(sh.device);
   hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  HIP_TRY(hipMemsetAsync(w, 0, 256, s));
-  int* ln[2] = {(int*)(w + p.off_ln[0]), (int*)(w + p.off_ln[1])};
-  double* ls[2] = {(double*)(w + p.off_ls[0]), (double*)(w + p.off_ls[1])};
-  long long* lk[2] = {(long long*)(w + p.off_lk[0]), (long long*)(w + p.off_lk[1])};
-  if (sh.P >= 3) {
-    scan_prep_kernel<<<dim3(sh.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
-                                                     (double*)(w + p.off_T), sh.K, sh.KP, sh.R, sh.P, sh.P16, s0);
-    HIP_TRY(hipGetLastError());
-  }
-  // Pass 0 (large P only) seeds the bound: the same scan and merge over every SEED_STRIDE-th item,
-  // whose exact N-th score (a subset's N-th best is a lower bound of the whole's) is published
-  // instead of written out.  Pass 1 scans every item and starts from that bound, so it appends
-  // about N SEED_STRIDE candidates in all instead of filling every workgroup's buffer from nothing.
-  // The bound only prunes: the result does not depend on it.
-  for (int pass = (select && sh.P >= SEED_MIN_P) ? 0 : 1; pass < 2; ++pass) {
-    const bool seeding = pass == 0;
-    int n_lists = 0;
-    if (sh.P >= 3) {
-      ScanArgs a{};
-      a.thT = (const double*)(w + p.off_thT);
-      a.T = (const double*)(w + p.off_T);
-      a.known = (const long long*)known;
-      a.n_known = n_known;
-      a.cand_s = cand_lds ? nullptr : (double*)(w + p.off_cs);
-      a.cand_k = cand_lds ? nullptr : (long long*)(w + p.off_ck);
-      a.list_s = ls[0];
-      a.list_k = lk[0];
-      a.list_n = ln[0];
-      a.shared = (unsigned long long*)w;
-      a.K = sh.K, a.P = sh.P, a.P16 = sh.P16, a.ns = ns, a.N = N, a.cap = p.cap, a.WB = WB, a.select = select;
-      a.stride = seeding ? SEED_STRIDE : 1;
-      n_lists = seeding ? std::min(p.G, sh.ncu) : p.G;
-      rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
-        return launch_lds(scan_kernel<decltype(ks)::value>, n_lists, lds, s, a);
-      });
-      if (rc) return rc;
-    }
-    int cur = 0;
-    for (;;) {
-      const bool last = n_lists <= FAN;
-      MergeArgs ma{};
-      ma.in_s = ls[cur], ma.in_k = lk[cur], ma.in_n = ln[cur], ma.n_in = n_lists;
-      if (!last) ma.out_s = ls[cur ^ 1], ma.out_k = lk[cur ^ 1], ma.out_n = ln[cur ^ 1];
-      ma.order = order, ma.scores = out_scores, ma.ids = out_ids, ma.count = (long long*)out_count;
-      ma.shared = (seeding && last) ? (unsigned long long*)w : nullptr;
-      ma.N = N, ma.cap = p.cap, ma.P = std::max(sh.P, 1);
-      const int n_out = last ? 1 : (n_lists + FAN - 1) / FAN;
-      if ((rc = launch_lds(scan_merge_kernel, n_out, merge_lds, s, ma))) return rc;
-      if (last) break;
-      n_lists = n_out;
-      cur ^= 1;
-    }
-  }
-  return MMSBM_OK;
+  // without the selection there is no bound to seed
+  return run_passes(p, l.merge_lds, select, p.G, order, theta, pr, ns, s0, ws, out_scores, out_ids, out_count, s,
+                    [&](int n_lists, int stride) {
+    ScanArgs a{};
+    fill_common(a, p, l, ws, known, n_known, ns, WB, stride);
+    a.select = select;
+    return dispatch_ks(sh.KP / 4, [&](auto ks) {
+      return launch_lds(scan_kernel<decltype(ks)::value>, n_lists, l.lds, s, a);
+    });
+  });
 }
 
 }  // extern "C"

@@ -9,7 +9,8 @@
 // 16 WB rows b) round-robin over the workgroups, the W rows of every slot in LDS, the same candidate
 // buffer (LDS when it fits, else workspace), wave_reserve / wg_keep_best, the published bound, the
 // seeding pass over every 61st item at P >= 200 and the fan-in-32 merge (scan_select.h, used as it
-// is; the merge kernel and the host loop are restated here, so that scan.hip's instantiations stay
+// is; the plan, the merge kernel and the host loop over the passes are scan_topn.h, shared with
+// scan.hip and scan_spread.hip; the kernel is restated here, so that scan.hip's instantiations stay
 // the objects they were).  Only the tile differs (scan_score.h, Score<KS>::tile_quorum<D, SMALL>):
 // each slot's 16 x 16 tile is formed from zero with the single-sample MFMA chain, as tile_mean forms
 // it, and inserted into a per-element sorted list of depth D = min(m, ns - m + 1) in registers.  For
@@ -44,19 +45,17 @@
 #include "scan_host.h"
 #include "scan_score.h"
 #include "scan_select.h"
+#include "scan_topn.h"
 
 namespace {
 
 using namespace scan_host;
 using namespace scan_select;
-using scan_score::scan_prep_kernel;
+using namespace scan_topn;
 using scan_score::Score;
 using scan_score::W_LDS_MAX;
 
-constexpr int QUORUM_MAX_N = 4096;    // mmsbm_scan_max_n(): the scan's cap
 constexpr int QUORUM_MAX_DEPTH = 4;   // the deepest sorted list instantiated
-constexpr int SEED_STRIDE = 61;       // as scan.hip
-constexpr int SEED_MIN_P = 200;
 
 struct QuorumArgs {
   const double* thT;          // [ns][KP][P16]
@@ -380,100 +379,8 @@ __global__ __launch_bounds__(NT) void scan_quorum_masked_kernel(QuorumMaskedArgs
 }
 
 // ------------------------------------------------------------------------------------------
-// Merge, as scan.hip's scan_merge_kernel: workgroup w keeps the best N of lists [FAN w, FAN (w + 1));
-// the last level (one workgroup) writes the result: scores, gene ids in key order, count, NaN / -1
-// tail.
+// Host side: the plan, the merge and the pass loop are scan_topn.h
 // ------------------------------------------------------------------------------------------
-struct MergeArgs {
-  const double* in_s;
-  const long long* in_k;
-  const int* in_n;
-  int n_in;
-  double* out_s;      // next level's lists (null on the last level)
-  long long* out_k;
-  int* out_n;
-  const int* order;   // last level
-  double* scores;
-  int* ids;
-  long long* count;
-  unsigned long long* shared;  // last level of the seeding pass: publish the N-th score, no output
-  int N, cap, P;
-};
-
-__global__ __launch_bounds__(NT) void scan_quorum_merge_kernel(MergeArgs A) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  Sel* st = reinterpret_cast<Sel*>(smem);
-  double* cs = reinterpret_cast<double*>(smem + sizeof(Sel));
-  long long* ck = reinterpret_cast<long long*>(cs + A.cap);
-  if (threadIdx.x == 0) sel_init(st);
-  __syncthreads();
-  const int l0 = blockIdx.x * FAN, l1 = min(l0 + FAN, A.n_in);
-  wg_merge_lists(st, cs, ck, A.in_s, A.in_k, A.in_n, l0, l1, A.N, A.cap);
-  wg_keep_best(st, cs, ck, A.N, A.shared);  // seeding pass: publishes the subset's N-th score
-  if (A.shared) return;
-  const int cnt = st->count;
-  if (A.out_s) {
-    for (int i = threadIdx.x; i < cnt; i += NT) {
-      A.out_s[(size_t)blockIdx.x * A.N + i] = cs[i];
-      A.out_k[(size_t)blockIdx.x * A.N + i] = ck[i];
-    }
-    if (threadIdx.x == 0) A.out_n[blockIdx.x] = cnt;
-    return;
-  }
-  const long long PP = A.P;
-  for (int i = threadIdx.x; i < A.N; i += NT) {
-    if (i < cnt) {
-      const long long k = ck[i];
-      A.scores[i] = cs[i];
-      A.ids[3 * i] = A.order[k / (PP * PP)];
-      A.ids[3 * i + 1] = A.order[(k / PP) % PP];
-      A.ids[3 * i + 2] = A.order[k % PP];
-    } else {
-      A.scores[i] = __builtin_nan("");
-      A.ids[3 * i] = A.ids[3 * i + 1] = A.ids[3 * i + 2] = -1;
-    }
-  }
-  if (threadIdx.x == 0) *A.count = cnt;
-}
-
-// ------------------------------------------------------------------------------------------
-// Host side
-// ------------------------------------------------------------------------------------------
-struct QuorumPlan {
-  ScanShape sh;
-  int N, cap, G, G2;
-  size_t off_thT, off_T, off_cs, off_ck, off_ls[2], off_lk[2], off_ln[2], total;
-};
-
-// As scan.hip's plan: everything that sizes the workspace follows the context's shape and N only.
-int make_plan(const mmsbm_ctx* c, int N, QuorumPlan* p) {
-  ScanShape& sh = p->sh;
-  if (int rc = scan_shape(c, "the quorum scan", &sh)) return rc;
-  if (N < 1) return fail(MMSBM_ERR_INVALID, "N=%d < 1", N);
-  if (N > QUORUM_MAX_N)
-    return fail(MMSBM_ERR_UNSUPPORTED, "N=%d above the scan's cap of %d", N, QUORUM_MAX_N);
-  if (int rc = packed_keys_fit(sh)) return rc;
-  p->N = N;
-  p->cap = 512;
-  while (p->cap < 2 * N) p->cap <<= 1;
-  const long long per_cu = N <= 1024 ? 4 : N <= 2048 ? 2 : 1;
-  const long long items = std::max<long long>(1, (long long)sh.P * (sh.P16 / 16));
-  p->G = (int)std::min<long long>(per_cu * sh.ncu, items);
-  p->G2 = (p->G + FAN - 1) / FAN;
-  const size_t G = p->G, cap = p->cap;
-  size_t off = 256;  // [0, 256): the published threshold
-  score_workspace(sh, off, &p->off_thT, &p->off_T);
-  p->off_cs = off, off = align256(off + sizeof(double) * G * cap);
-  p->off_ck = off, off = align256(off + sizeof(long long) * G * cap);
-  const size_t nl[2] = {G, (size_t)p->G2};
-  for (int i = 0; i < 2; ++i) {
-    p->off_ls[i] = off, off = align256(off + sizeof(double) * nl[i] * N);
-    p->off_lk[i] = off, off = align256(off + sizeof(long long) * nl[i] * N);
-    p->off_ln[i] = off, off = align256(off + sizeof(int) * nl[i]);
-  }
-  p->total = off;
-  return MMSBM_OK;
-}
 
 // f(std::integral_constant<int, D>{}) for D in [0, QUORUM_MAX_DEPTH]
 template <class F>
@@ -493,8 +400,8 @@ int quorum_call(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_
                 void* ws, int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count,
                 void* stream) {
   if (!c) return fail(MMSBM_ERR_INVALID, "null context");
-  QuorumPlan p;
-  int rc = make_plan(c, N, &p);
+  TopNPlan p;
+  int rc = make_plan(c, "the quorum scan", N, &p);
   if (rc) return rc;
   if (!order || !theta || !pr || !out_scores || !out_ids || !out_count)
     return fail(MMSBM_ERR_INVALID, "null pointer");
@@ -517,83 +424,33 @@ int quorum_call(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_
                 "(mmsbm_scan_quorum_max_depth)",
                 min_votes, ns, depth, QUORUM_MAX_DEPTH);
   if ((rc = pick_wb(sh, "the quorum scan", 1, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
-  const size_t cand_bytes = (size_t)p.cap * 16;
-  // the masked kernel's mask row may move the candidate buffer to the workspace, which holds it anyway
-  const size_t mrow_bytes = sizeof(unsigned) * (size_t)((MW + 1) & ~1);
-  const bool cand_lds = sizeof(Sel) + w_bytes + mrow_bytes + cand_bytes <= (size_t)LDS_MAX;
-  const int lds = (int)(sizeof(Sel) + w_bytes + mrow_bytes + (cand_lds ? cand_bytes : 0));
-  const int merge_lds = (int)(sizeof(Sel) + cand_bytes);
+  // the masked kernel's mask row lies in front of the candidate buffer
+  const TopNLds l = lds_sizes(p, w_bytes, sizeof(unsigned) * (size_t)((MW + 1) & ~1));
   const bool early = env_override("MMSBM_SCAN_QUORUM_EARLY", 1) != 0;  // measurement
   // measurement: fewer workgroups than planned (the lists and buffers are sized for p.G)
   const long long g_env = env_override("MMSBM_SCAN_QUORUM_GRID", 0);
   const int G = g_env >= 1 ? (int)std::min<long long>(g_env, p.G) : p.G;
-
-  DeviceGuard g(sh.device);
   hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  HIP_TRY(hipMemsetAsync(w, 0, 256, s));
-  int* ln[2] = {(int*)(w + p.off_ln[0]), (int*)(w + p.off_ln[1])};
-  double* ls[2] = {(double*)(w + p.off_ls[0]), (double*)(w + p.off_ls[1])};
-  long long* lk[2] = {(long long*)(w + p.off_lk[0]), (long long*)(w + p.off_lk[1])};
-  if (sh.P >= 3) {
-    scan_prep_kernel<<<dim3(sh.P16, ns), NT, 0, s>>>(order, theta, pr, (double*)(w + p.off_thT),
-                                                     (double*)(w + p.off_T), sh.K, sh.KP, sh.R, sh.P, sh.P16, s0);
-    HIP_TRY(hipGetLastError());
-  }
-  // Pass 0 (large P only) seeds the bound and pass 1 scans every item, as in mmsbm_scan_topn: the
-  // N-th best q_m of a subset is a lower bound of the whole's.  The bound only prunes.
-  for (int pass = sh.P >= SEED_MIN_P ? 0 : 1; pass < 2; ++pass) {
-    const bool seeding = pass == 0;
-    int n_lists = 0;
-    if (sh.P >= 3) {
-      QuorumArgs a{};
-      a.thT = (const double*)(w + p.off_thT);
-      a.T = (const double*)(w + p.off_T);
-      a.known = (const long long*)known;
-      a.n_known = n_known;
-      a.cand_s = cand_lds ? nullptr : (double*)(w + p.off_cs);
-      a.cand_k = cand_lds ? nullptr : (long long*)(w + p.off_ck);
-      a.list_s = ls[0];
-      a.list_k = lk[0];
-      a.list_n = ln[0];
-      a.shared = (unsigned long long*)w;
-      a.K = sh.K, a.P = sh.P, a.P16 = sh.P16, a.ns = ns, a.N = N, a.cap = p.cap, a.WB = WB;
-      a.first = early ? ns - min_votes : ns;
-      a.stride = seeding ? SEED_STRIDE : 1;
-      n_lists = seeding ? std::min(G, sh.ncu) : G;
-      QuorumMaskedArgs am{};
-      static_cast<QuorumArgs&>(am) = a;
-      am.mask = mask, am.MW = MW;
-      rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
-        return dispatch_depth(ns > 1 ? depth : 0, [&](auto d) {
-          constexpr int KS = decltype(ks)::value, D = decltype(d)::value;
-          if (masked) {
-            if (D > 0 && smallest) return launch_lds(scan_quorum_masked_kernel<KS, D, D != 0>, n_lists, lds, s, am);
-            return launch_lds(scan_quorum_masked_kernel<KS, D, false>, n_lists, lds, s, am);
-          }
-          if (D > 0 && smallest) return launch_lds(scan_quorum_kernel<KS, D, D != 0>, n_lists, lds, s, a);
-          return launch_lds(scan_quorum_kernel<KS, D, false>, n_lists, lds, s, a);
-        });
+  // the N-th best q_m of a subset is a lower bound of the whole's: the seeding pass as in mmsbm_scan_topn
+  return run_passes(p, l.merge_lds, true, G, order, theta, pr, ns, s0, ws, out_scores, out_ids, out_count, s,
+                    [&](int n_lists, int stride) {
+    QuorumMaskedArgs am{};
+    QuorumArgs& a = am;
+    fill_common(a, p, l, ws, known, n_known, ns, WB, stride);
+    a.first = early ? ns - min_votes : ns;
+    am.mask = mask, am.MW = MW;
+    return dispatch_ks(sh.KP / 4, [&](auto ks) {
+      return dispatch_depth(ns > 1 ? depth : 0, [&](auto d) {
+        constexpr int KS = decltype(ks)::value, D = decltype(d)::value;
+        if (masked) {
+          if (D > 0 && smallest) return launch_lds(scan_quorum_masked_kernel<KS, D, D != 0>, n_lists, l.lds, s, am);
+          return launch_lds(scan_quorum_masked_kernel<KS, D, false>, n_lists, l.lds, s, am);
+        }
+        if (D > 0 && smallest) return launch_lds(scan_quorum_kernel<KS, D, D != 0>, n_lists, l.lds, s, a);
+        return launch_lds(scan_quorum_kernel<KS, D, false>, n_lists, l.lds, s, a);
       });
-      if (rc) return rc;
-    }
-    int cur = 0;
-    for (;;) {
-      const bool last = n_lists <= FAN;
-      MergeArgs ma{};
-      ma.in_s = ls[cur], ma.in_k = lk[cur], ma.in_n = ln[cur], ma.n_in = n_lists;
-      if (!last) ma.out_s = ls[cur ^ 1], ma.out_k = lk[cur ^ 1], ma.out_n = ln[cur ^ 1];
-      ma.order = order, ma.scores = out_scores, ma.ids = out_ids, ma.count = (long long*)out_count;
-      ma.shared = (seeding && last) ? (unsigned long long*)w : nullptr;
-      ma.N = N, ma.cap = p.cap, ma.P = std::max(sh.P, 1);
-      const int n_out = last ? 1 : (n_lists + FAN - 1) / FAN;
-      if ((rc = launch_lds(scan_quorum_merge_kernel, n_out, merge_lds, s, ma))) return rc;
-      if (last) break;
-      n_lists = n_out;
-      cur ^= 1;
-    }
-  }
-  return MMSBM_OK;
+    });
+  });
 }
 }  // namespace
 
@@ -602,12 +459,7 @@ extern "C" {
 int mmsbm_scan_quorum_max_depth(void) { return QUORUM_MAX_DEPTH; }
 
 int mmsbm_scan_quorum_workspace_bytes(const mmsbm_ctx* c, int32_t N, int64_t* bytes) {
-  if (!c || !bytes) return fail(MMSBM_ERR_INVALID, "null argument");
-  QuorumPlan p;
-  int rc = make_plan(c, N, &p);
-  if (rc) return rc;
-  *bytes = (int64_t)p.total;
-  return MMSBM_OK;
+  return workspace_bytes(c, "the quorum scan", N, bytes);
 }
 
 int mmsbm_scan_quorum_topn(mmsbm_ctx* c, const int32_t* order, const int64_t* known, int64_t n_known,
