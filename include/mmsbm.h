@@ -159,6 +159,25 @@ int mmsbm_scan_topn(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known, 
                     int64_t ws_bytes, double *out_scores, int32_t *out_ids, int64_t *out_count,
                     void *stream);
 
+/* Pair-masked genome-wide scan: mmsbm_scan_topn with the pair mask of mmsbm_scan_census_masked behind
+ * n_known, under that call's layout and rule: mask (device) = uint32[rows][words_per_row] of
+ * mmsbm_pair_mask_shape in rank positions, bit y of row x set = the pair (x, y) is blocked, only
+ * x < y read.  A triple a < b < c is eligible when it is eligible for the unmasked call and none of
+ * (a, b), (a, c), (b, c) is blocked.  Everything else is the unmasked call's: the arguments, the
+ * result rows, the total order, the cap on N, the measurement variables (MMSBM_SCAN_SELECT=0: the
+ * bare score phase; MMSBM_SCAN_GRID=<workgroups> lowers the grid, on which neither call's list
+ * depends) and the workspace (mmsbm_scan_workspace_bytes, unchanged).  A listed score carries the bits mmsbm_scan_topn gives that
+ * triple, so an all-zero mask returns the unmasked list, and a mask returns the unmasked call's list
+ * with the keys of every triple that contains a blocked pair added to `known`: the exact, unique
+ * top N of the masked-eligible triples (the pruning bounds, the seeding pass's included, are formed
+ * from masked-eligible candidates only), *out_count < N when fewer are eligible.  P <= 16384
+ * (MMSBM_ERR_UNSUPPORTED above); a NULL mask is MMSBM_ERR_INVALID: the unmasked call exists for that.
+ * Every check comes before any device call.  Replaces nothing in the reference. */
+int mmsbm_scan_topn_masked(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known,
+                           int64_t n_known, const uint32_t *mask, const double *theta,
+                           const double *pr, int32_t sample, int32_t N, void *ws, int64_t ws_bytes,
+                           double *out_scores, int32_t *out_ids, int64_t *out_count, void *stream);
+
 /* Partner scan: for each query gene, the exact top N of Model.do_prediction (:530-547, no eps) over
  * the pairs of other genes it forms a triple with.  Notation as for mmsbm_scan_topn: order[P]
  * (device) = the gene ids sorted by str(id), Th' = theta in that order, p_1 the rating-1 lattice, a
@@ -202,6 +221,24 @@ int mmsbm_partners_topn(mmsbm_ctx *ctx, const int32_t *order, const int32_t *que
                         const int64_t *known_off, const int64_t *known_pairs, const double *theta,
                         const double *pr, int32_t sample, int32_t N, void *ws, int64_t ws_bytes,
                         double *out_scores, int32_t *out_ids, int64_t *out_count, void *stream);
+
+/* Pair-masked partner scan: mmsbm_partners_topn with the pair mask of mmsbm_scan_census_masked behind
+ * known_pairs (the same layout; only x < y read).  A candidate pair b < c of the query at rank
+ * position q is eligible when it is eligible for the unmasked call and none of {q, b}, {q, c}, (b, c)
+ * is blocked; the pairs with q are read at (min, max).  Everything else is the unmasked call's: the
+ * arguments, the rows, the total order, the caps, the measurement variable and the workspace
+ * (mmsbm_partners_workspace_bytes, unchanged).  A listed score carries the bits mmsbm_partners_topn
+ * gives that candidate, so an all-zero mask returns the unmasked rows, and a mask returns the
+ * unmasked call's rows with the pair keys b P + c of every blocked candidate added to the query's
+ * slice of known_pairs.  A query whose every candidate is blocked has count 0 and a NaN / -1 row; a
+ * query's row still does not depend on Q, on the other queries, on the grid or on the batch.
+ * P <= 16384 (MMSBM_ERR_UNSUPPORTED above); a NULL mask is MMSBM_ERR_INVALID: the unmasked call
+ * exists for that.  Every check comes before any device call.  Replaces nothing in the reference. */
+int mmsbm_partners_topn_masked(mmsbm_ctx *ctx, const int32_t *order, const int32_t *queries_host,
+                               int64_t Q, const int64_t *known_off, const int64_t *known_pairs,
+                               const uint32_t *mask, const double *theta, const double *pr,
+                               int32_t sample, int32_t N, void *ws, int64_t ws_bytes,
+                               double *out_scores, int32_t *out_ids, int64_t *out_count, void *stream);
 
 /* Score census: for M thresholds, the exact number of the scan's eligible triples whose score is at
  * or above each, and the number of eligible triples.  order, known, n_known, theta, pr, sample

@@ -95,6 +95,10 @@ SIGNATURES = {
                                         _vp, _vp, _vp]),
     "mmsbm_scan_spread_topn_masked": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i32, _c_i32, _c_i32, _vp,
                                                _c_i64, _vp, _vp, _vp, _vp]),
+    "mmsbm_scan_topn_masked": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i32, _c_i32, _vp, _c_i64, _vp,
+                                        _vp, _vp, _vp]),
+    "mmsbm_partners_topn_masked": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i32, _c_i32, _vp,
+                                            _c_i64, _vp, _vp, _vp, _vp]),
     "mmsbm_screen_max_n": (_c_int, []),
     "mmsbm_screen_workspace_bytes": (_c_int, [_vp, _c_i64, _c_i32, ctypes.POINTER(_c_i64)]),
     "mmsbm_screen_topn": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i32, _c_i32, _vp, _c_i64,

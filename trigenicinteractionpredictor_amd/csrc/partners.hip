@@ -27,6 +27,9 @@
 // query's lists (fan-in 32, at most two levels) and writes its row.  The exact top N under a total
 // order is unique, no score is formed by an atomic and every sum has a fixed order: a query's row
 // does not depend on Q, the other queries, the grid or the batch.
+//
+// partners_masked_kernel (mmsbm_partners_topn_masked) is partners_kernel's pair-masked twin: the
+// query's own bit row in LDS, row blocks and tiles dropped by it, the (b, c) bits per element.
 
 #include <hip/hip_runtime.h>
 
@@ -292,6 +295,259 @@ __global__ __launch_bounds__(NT) void partners_kernel(PartArgs A) {
   if (threadIdx.x == 0) A.list_n[blockIdx.x] = cnt;
 }
 
+// The masked partner scan (mmsbm_partners_topn_masked): the pair mask travels in the masked kernel's
+// own argument struct, so PartArgs and partners_kernel are what they were.
+struct PartMaskedArgs : PartArgs {
+  const unsigned* mask;  // [P16][MW] (include/mmsbm.h, mmsbm_pair_mask_shape)
+  int MW;
+};
+
+// partners_kernel's masked twin, restated and not a shared body (scan_quorum.hip says why; DESIGN.md
+// holds the figures that show partners_kernel's instantiations unchanged).
+//
+// A candidate pair b < c of the query at q is eligible only if none of {q, b}, {q, c}, (b, c) is set
+// in the pair mask (read at x < y only).  The query's own bit row: bit x of qrow is set when the pair
+// {q, x} is blocked, i.e. bit x of mask row q for x > q and bit q of mask row x for x < q; bit q
+// itself and the bits from P on are set too (no candidate there), so the skips below need no bounds
+// of their own.  Each workgroup builds it once, 64 positions per wave and ballot, in LDS in front of
+// the candidate buffer (MW words rounded up to 2: at most 2 KiB).  An item is skipped, before its
+// U / L rows are formed, when every row of its block is blocked with q; a tile, before its chains,
+// when halfword ct of qrow is 0xFFFF (its 16 columns are all blocked with q).  Per element the
+// blocked bit is qrow[b] | qrow[c] | mask[b][c], the (b, c) halfwords of the lane's four rows loaded
+// one tile ahead as scan.hip's twin loads them, and it is folded into pass[i]: no blocked candidate
+// enters a buffer, so the workgroup's N-th best and the query's published bound are formed from
+// masked-eligible candidates only and stay lower bounds of the query's masked N-th best.  The score
+// phase is partners_kernel's, so a listed score carries the bits the unmasked call gives it.
+template <int KS>
+__global__ __launch_bounds__(NT) void partners_masked_kernel(PartMaskedArgs A) {
+  constexpr int KP = 4 * KS, WS = KP + 2;  // W row stride: conflict-free A-operand reads
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  Sel* st = reinterpret_cast<Sel*>(smem);
+  double* W = reinterpret_cast<double*>(smem + sizeof(Sel));  // [2][ns][RB][WS]: U, L
+  const int RB = 16 * A.WB;
+  const int P = A.P, P16 = A.P16, K = A.K, ns = A.ns;
+  double* cs = W + (size_t)2 * ns * RB * WS;
+  unsigned* qrow = reinterpret_cast<unsigned*>(cs);  // the query's bit row, before the candidate buffer
+  const int MW2 = (A.MW + 1) & ~1;
+  cs += MW2 >> 1;                                    // the candidate buffer
+  long long* ck = reinterpret_cast<long long*>(cs + A.cap);
+  const int qi = blockIdx.x / A.gpq, j = blockIdx.x % A.gpq;
+  const int q = A.qpos[qi];
+  const bool q_ok = q >= 0 && q < P;
+  unsigned long long* shared = A.shared + qi;
+  if (threadIdx.x == 0) {
+    sel_init(st);
+    if (A.known_off) {
+      st->klo = A.known_off[qi];
+      st->khi = A.known_off[qi + 1];
+    }
+  }
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = lane & 15, kk = lane >> 4;
+  const int wb = wave % A.WB, wc = wave / A.WB, CW = 4 / A.WB;
+  const int nct = P16 / 16;
+  const int nbq = (P + RB - 1) / RB;
+  const int CT = (nct + A.ncc - 1) / A.ncc;  // c-tiles per chunk
+  const long long PP = (long long)P;
+  const double inv_div = (double)ns;
+  const size_t Tq = (size_t)qi * 3 * K * KP, Ts = (size_t)A.Q * 3 * K * KP;
+
+  // the query's bit row: position x of this wave's 64, words x / 32 and x / 32 + 1 from one ballot
+  for (int x = threadIdx.x; x < 32 * MW2; x += NT) {
+    bool on = true;  // q itself, positions from P on, a query without a position
+    if (q_ok && x < P && x != q) {
+      const unsigned w = x > q ? A.mask[(size_t)q * A.MW + (x >> 5)] : A.mask[(size_t)x * A.MW + (q >> 5)];
+      on = (w >> ((x > q ? x : q) & 31)) & 1u;
+    }
+    const unsigned long long bal = __ballot(on);
+    if (lane == 0) {
+      qrow[x >> 5] = (unsigned)bal;
+      qrow[(x >> 5) + 1] = (unsigned)(bal >> 32);
+    }
+  }
+  __syncthreads();
+  const unsigned short* qrow16 = reinterpret_cast<const unsigned short*>(qrow);
+
+  // the query's items round-robin over its workgroups
+  for (int it = q_ok ? j : INT_MAX; it < nbq * A.ncc; it += A.gpq) {
+    const int bq = it / A.ncc, cc = it % A.ncc;
+    const int ct_lo = cc * CT, ct_hi = min(nct, ct_lo + CT);
+    const int r0 = bq * RB;
+    if (ct_lo >= ct_hi || r0 >= P - 1 || ct_hi * 16 - 1 <= r0) continue;  // no b < c here
+    {
+      // the {q, b} bits of the item's rows: RB = 16, 32 or 64 bits of qrow from bit r0 on
+      const int w0 = r0 >> 5;
+      unsigned long long bits = (unsigned long long)qrow[w0] >> (r0 & 31);  // w0 < MW: r0 < P - 1
+      if (RB == 64 && w0 + 1 < MW2) bits |= (unsigned long long)qrow[w0 + 1] << 32;
+      const int hi = min(P, r0 + RB) - r0;  // 0 < hi <= RB
+      const unsigned long long need = hi >= 64 ? ~0ull : (1ull << hi) - 1;
+      if ((bits & need) == need) continue;  // workgroup-uniform: every row of the block is blocked with q
+    }
+    __syncthreads();  // the previous item's W is read
+    if (threadIdx.x == 0) {
+      const unsigned long long g = __hip_atomic_load(shared, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      st->gthr = g ? __longlong_as_double((long long)g) : neg_inf();
+    }
+    // U = W1 of the rows above q and W2 of the rows below it, L = W3 of the rows below it (zero
+    // elsewhere), every sample
+    for (int idx = threadIdx.x; idx < 2 * ns * RB * KP; idx += NT) {
+      const int z = idx % KP, r = (idx / KP) % RB, s = (idx / (KP * RB)) % ns, ul = idx / (KP * RB * ns);
+      const int rowb = r0 + r;
+      const int mm = ul ? 2 : rowb > q ? 0 : 1;
+      double v = 0.0;
+      if (rowb < P && rowb != q && (ul == 0 || rowb < q)) {
+        const double* __restrict__ Tm = A.T + (size_t)s * Ts + Tq + (size_t)mm * K * KP + z;
+        const double* __restrict__ tb = A.thT + (size_t)s * KP * P16 + rowb;
+        for (int i = 0; i < K; ++i) v = fma(tb[(size_t)i * P16], Tm[i * KP], v);
+      }
+      W[((size_t)(ul * ns + s) * RB + r) * WS + z] = v;
+    }
+    __syncthreads();
+
+    const int btile = bq * A.WB + wb, b0 = btile * 16;
+    const bool wave_on = b0 < P - 1;
+    const bool rows_hi = b0 + 15 > q, rows_lo = b0 < q;  // the tile has rows above / below q
+    int ct = ct_lo + wc;
+    if (ct < btile) ct += (btile - ct + CW - 1) / CW * CW;  // every c of those tiles is below every b
+    const long long klo = st->klo, khi = st->khi;
+    double areg[2][KS];  // single sample: the A operands live in registers for the whole item
+    unsigned qbm = 0;                // bit i: the pair {q, b0 + kk + 4 i} is blocked
+    unsigned bcn[4] = {0, 0, 0, 0};  // the next tile's (b, c) halfwords, in flight
+    // halfword ct of mask rows b0 + kk + 4 i: inside the mask for a wave that is on (rows <= b0 + 15 <
+    // P16, halfwords ct < P16 / 16 <= 2 MW)
+    const unsigned bc_off = (unsigned)(b0 + kk) * (unsigned)A.MW * 4u;
+    auto load_bc = [&](unsigned (&h)[4], int ct) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        h[i] = *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(A.mask) +
+                                                        (size_t)(16 * i) * A.MW + (bc_off + 2u * (unsigned)ct));
+    };
+    if (wave_on) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + kk + 4 * i;
+        qbm |= ((qrow[b >> 5] >> (b & 31)) & 1u) << i;
+      }
+      if (ns == 1) {
+#pragma unroll
+        for (int ul = 0; ul < 2; ++ul)
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) areg[ul][ks] = W[((size_t)ul * RB + wb * 16 + m) * WS + 4 * ks + kk];
+      }
+    }
+    for (;;) {
+      // the thresholds change only when the workgroup sorts its buffer (behind a barrier)
+      const double thr_s = st->thr_s, gthr = st->gthr;
+      const long long thr_k = st->thr_k;
+      const double cut = fmax(thr_s, gthr);
+      if (wave_on) {
+        double bnext[KS];  // single sample: the next tile's Th' operand is in flight
+        if (ns == 1 && ct < ct_hi) {
+          const double* __restrict__ tc = A.thT + (size_t)kk * P16 + ct * 16 + m;
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) bnext[ks] = tc[(size_t)(4 * ks) * P16];
+        }
+        if (ct < ct_hi) load_bc(bcn, ct);  // also for a tile that is redone
+        for (; ct < ct_hi; ct += CW) {
+          const int c0 = ct * 16, c = c0 + m;
+          // U: some c > q (rows below q) or rows above q (all their c are); L: rows and c below q
+          const bool need[2] = {rows_hi || c0 + 15 > q, rows_lo && c0 < q};
+          const unsigned qc = qrow16[ct];
+          const bool dead = qc == 0xFFFFu;  // every pair {q, c} of the tile is blocked (wave-uniform)
+          unsigned blk = qbm | (((qc >> m) & 1u) ? 0xFu : 0u);  // bit i: element i of the tile is blocked
+#pragma unroll
+          for (int i = 0; i < 4; ++i) blk |= ((bcn[i] >> m) & 1u) << i;
+          if (ct + CW < ct_hi) load_bc(bcn, ct + CW);
+          double bcur[KS];
+          if (ns == 1) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) bcur[ks] = bnext[ks];
+            if (ct + CW < ct_hi) {
+              const double* __restrict__ tc = A.thT + (size_t)kk * P16 + c + 16 * CW;
+#pragma unroll
+              for (int ks = 0; ks < KS; ++ks) bnext[ks] = tc[(size_t)(4 * ks) * P16];
+            }
+          }
+          if (dead) continue;  // no chain, no selection
+          d4v res = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int ul = 0; ul < 2; ++ul) {
+            if (!need[ul]) continue;  // wave-uniform
+            d4v tot = {0.0, 0.0, 0.0, 0.0};
+            if (ns == 1) {
+#pragma unroll
+              for (int ks = 0; ks < KS; ++ks)
+                tot = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ul][ks], bcur[ks], tot, 0, 0, 0);
+            } else {
+              for (int s = 0; s < ns; ++s) {
+                const double* __restrict__ tc = A.thT + ((size_t)s * KP + kk) * P16 + c;
+                const double* wr = W + ((size_t)(ul * ns + s) * RB + wb * 16 + m) * WS + kk;
+                d4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+                  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[4 * ks], tc[(size_t)(4 * ks) * P16], acc, 0, 0, 0);
+                tot = s == 0 ? acc : tot + acc;  // samples added in slot order
+              }
+              tot = tot / inv_div;
+            }
+            // lane holds S[b0 + kk + 4 i][c0 + m]: keep the chain of its own column
+            if ((c < q) == (ul == 1)) res = tot;
+          }
+          if (!A.select) {
+            asm volatile("" ::"v"(res[0]), "v"(res[1]), "v"(res[2]), "v"(res[3]));  // keep the score phase live
+            continue;
+          }
+          // first the score alone against the larger of the two bounds (equal scores stay in: the
+          // key decides below); nearly every tile ends here once the buffer holds N
+          if (!__ballot(res[0] >= cut || res[1] >= cut || res[2] >= cut || res[3] >= cut)) continue;
+          bool pass[4];
+          long long key[4];
+          unsigned long long mk[4];
+          int n = 0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int b = b0 + kk + 4 * i;
+            // the triple's packed key, q in its sorted place
+            key[i] = b > q ? ((long long)q * PP + b) * PP + c
+                   : c > q ? ((long long)b * PP + q) * PP + c
+                           : ((long long)b * PP + c) * PP + q;
+            pass[i] = b < c && c < P && b != q && c != q && !(res[i] < gthr) &&
+                      before(res[i], key[i], thr_s, thr_k);
+            pass[i] = pass[i] && !((blk >> i) & 1u);
+            if (pass[i] && khi > klo) pass[i] = !is_known(A.known, klo, khi, (long long)b * PP + c);
+            mk[i] = __ballot(pass[i]);
+            n += __popcll(mk[i]);
+          }
+          if (!n) continue;
+          int pos = wave_reserve(st, n, A.cap);
+          if (pos < 0) break;  // the tile is redone after the workgroup made room
+          const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (pass[i]) {
+              const int at = pos + __popcll(mk[i] & below);
+              cs[at] = res[i];
+              ck[at] = key[i];
+            }
+            pos += __popcll(mk[i]);
+          }
+        }
+      }
+      __syncthreads();
+      if (!st->overflow) break;
+      wg_keep_best(st, cs, ck, A.N, shared);
+    }
+  }
+  wg_keep_best(st, cs, ck, A.N, shared);
+  const int cnt = st->count;
+  for (int i = threadIdx.x; i < cnt; i += NT) {
+    A.list_s[(size_t)blockIdx.x * A.N + i] = cs[i];
+    A.list_k[(size_t)blockIdx.x * A.N + i] = ck[i];
+  }
+  if (threadIdx.x == 0) A.list_n[blockIdx.x] = cnt;
+}
+
 // ------------------------------------------------------------------------------------------
 // Merge, grid (lists out per query, Q): workgroup (w, i) keeps the best N of query i's lists
 // [FAN w, FAN (w + 1)); the last level (one workgroup per query) writes the query's row: scores,
@@ -398,31 +654,19 @@ int make_plan(const mmsbm_ctx* c, long long Q, int N, PartPlan* p) {
   return MMSBM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mmsbm_partners_max_n(void) { return PARTNERS_MAX_N; }
-
-int mmsbm_partners_workspace_bytes(const mmsbm_ctx* c, int64_t Q, int32_t N, int64_t* bytes) {
-  if (!c || !bytes) return fail(MMSBM_ERR_INVALID, "null argument");
-  PartPlan p;
-  int rc = make_plan(c, Q, N, &p);
-  if (rc) return rc;
-  *bytes = (int64_t)p.total;
-  return MMSBM_OK;
-}
-
-int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_host, int64_t Q,
-                        const int64_t* known_off, const int64_t* known_pairs, const double* theta,
-                        const double* pr, int32_t sample, int32_t N, void* ws, int64_t ws_bytes,
-                        double* out_scores, int32_t* out_ids, int64_t* out_count, void* stream) {
+// Both entry points; `masked`: mmsbm_partners_topn_masked, whose mask must not be null.
+int partners_call(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_host, int64_t Q,
+                  const int64_t* known_off, const int64_t* known_pairs, const uint32_t* mask, bool masked,
+                  const double* theta, const double* pr, int32_t sample, int32_t N, void* ws, int64_t ws_bytes,
+                  double* out_scores, int32_t* out_ids, int64_t* out_count, void* stream) {
   if (!c) return fail(MMSBM_ERR_INVALID, "null context");
   PartPlan p;
   int rc = make_plan(c, Q, N, &p);
   if (rc) return rc;
-  if (Q == 0) return MMSBM_OK;
   const ScanShape& sh = p.sh;
+  int MW = 0;
+  if (masked && (rc = check_pair_mask(sh, "the partner scan", mask, &MW))) return rc;
+  if (Q == 0) return MMSBM_OK;
   if (!order || !queries_host || !theta || !pr || !out_scores || !out_ids || !out_count)
     return fail(MMSBM_ERR_INVALID, "null pointer");
   if (known_off && !known_pairs) return fail(MMSBM_ERR_INVALID, "known_off without known_pairs");
@@ -436,9 +680,12 @@ int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queri
     return rc;
   if ((rc = pick_wb(sh, "the partner scan", 2, ns, W_LDS_MAX, &WB, &w_bytes))) return rc;
   const size_t cand_bytes = (size_t)p.cap * 16;
-  const int lds = (int)(sizeof(Sel) + w_bytes + cand_bytes);
+  // the masked kernel's bit row of the query lies in front of the candidate buffer
+  const size_t qrow_bytes = sizeof(unsigned) * (size_t)((MW + 1) & ~1);
+  const int lds = (int)(sizeof(Sel) + w_bytes + qrow_bytes + cand_bytes);
   const int merge_lds = (int)(sizeof(Sel) + cand_bytes);
-  static_assert(sizeof(Sel) + W_LDS_MAX + 2 * PARTNERS_MAX_N * 16 <= LDS_MAX, "the buffer stays in LDS");
+  static_assert(sizeof(Sel) + W_LDS_MAX + PAIR_MASK_MAX_P / 8 + 2 * PARTNERS_MAX_N * 16 <= LDS_MAX,
+                "the query's bit row and the buffer stay in LDS");
   const bool select = env_override("MMSBM_PARTNERS_SELECT", 1) != 0;  // measurement: the bare score phase
 
   DeviceGuard g(sh.device);
@@ -459,7 +706,9 @@ int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queri
                                                      (double*)(w + p.off_T), (int*)(w + p.off_qpos), sh.K,
                                                      sh.KP, sh.R, sh.P, nq, s0);
     HIP_TRY(hipGetLastError());
-    PartArgs a{};
+    PartMaskedArgs am{};
+    PartArgs& a = am;
+    am.mask = mask, am.MW = MW;
     a.thT = (const double*)(w + p.off_thT);
     a.T = (const double*)(w + p.off_T);
     a.qpos = (const int*)(w + p.off_qpos);
@@ -475,7 +724,9 @@ int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queri
     n_lists = p.gpq;
     const int G = nq * p.gpq;
     rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
-      return launch_lds(partners_kernel<decltype(ks)::value>, G, lds, s, a);
+      constexpr int KS = decltype(ks)::value;
+      if (masked) return launch_lds(partners_masked_kernel<KS>, G, lds, s, am);
+      return launch_lds(partners_kernel<KS>, G, lds, s, a);
     });
     if (rc) return rc;
   }
@@ -494,6 +745,38 @@ int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queri
     cur ^= 1;
   }
   return MMSBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmsbm_partners_max_n(void) { return PARTNERS_MAX_N; }
+
+int mmsbm_partners_workspace_bytes(const mmsbm_ctx* c, int64_t Q, int32_t N, int64_t* bytes) {
+  if (!c || !bytes) return fail(MMSBM_ERR_INVALID, "null argument");
+  PartPlan p;
+  int rc = make_plan(c, Q, N, &p);
+  if (rc) return rc;
+  *bytes = (int64_t)p.total;
+  return MMSBM_OK;
+}
+
+int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_host, int64_t Q,
+                        const int64_t* known_off, const int64_t* known_pairs, const double* theta,
+                        const double* pr, int32_t sample, int32_t N, void* ws, int64_t ws_bytes,
+                        double* out_scores, int32_t* out_ids, int64_t* out_count, void* stream) {
+  return partners_call(c, order, queries_host, Q, known_off, known_pairs, nullptr, false, theta, pr, sample, N, ws,
+                       ws_bytes, out_scores, out_ids, out_count, stream);
+}
+
+int mmsbm_partners_topn_masked(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_host, int64_t Q,
+                               const int64_t* known_off, const int64_t* known_pairs, const uint32_t* mask,
+                               const double* theta, const double* pr, int32_t sample, int32_t N, void* ws,
+                               int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count,
+                               void* stream) {
+  return partners_call(c, order, queries_host, Q, known_off, known_pairs, mask, true, theta, pr, sample, N, ws,
+                       ws_bytes, out_scores, out_ids, out_count, stream);
 }
 
 }  // extern "C"

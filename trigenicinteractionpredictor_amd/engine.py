@@ -277,31 +277,32 @@ class EMEngine:
         perm_d = torch.from_numpy(perm).to(self.device)
         return torch.empty_like(joined).index_copy_(axis, perm_d, joined), outs[-1]
 
-    def scan_top_async(self, n: int, known: np.ndarray = None, sample: int = None, stream=None):
+    def scan_top_async(self, n: int, known: np.ndarray = None, sample: int = None, stream=None, mask=None):
         """scan_top without the host copy: -> device tensors (scores f64[n], ids int32[n][3],
         count int64[1]); rows from `count` on are NaN / -1.  Nothing synchronises."""
         n = int(n)
-        with self._scan_call(known, sample, stream) as (head, s):
+        entry = self.lib.mmsbm_scan_topn if mask is None else self.lib.mmsbm_scan_topn_masked
+        with self._scan_call(known, sample, stream, mask) as (head, s):
             ws = self.scan_workspace("scan", n)
             scores = torch.empty(n, dtype=torch.float64, device=self.device)
             ids = torch.empty((n, 3), dtype=torch.int32, device=self.device)
             count = torch.empty(1, dtype=torch.int64, device=self.device)
-            _lib.check(self.lib.mmsbm_scan_topn(*head, n, _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids),
-                                                _ptr(count), s.cuda_stream))
+            _lib.check(entry(*head, n, _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids), _ptr(count), s.cuda_stream))
         return scores, ids, count
 
-    def scan_top(self, n: int, known: np.ndarray = None, sample: int = None, stream=None):
+    def scan_top(self, n: int, known: np.ndarray = None, sample: int = None, stream=None, mask=None):
         """The n most probable triples of distinct genes (include/mmsbm.h mmsbm_scan_topn):
         -> (scores f64[n'], ids int32[n'][3] in key order) on the host, best first, n' <= n.
         known: sorted int64 packed keys to skip (scan.known_keys); sample: a slot of the active
-        prefix, or None for the mean over it."""
-        scores, ids, count = self.scan_top_async(n, known, sample, stream)
+        prefix, or None for the mean over it.  mask: as for census (mmsbm_scan_topn_masked): the
+        exact top n over the triples without a blocked pair; None: the unmasked call."""
+        scores, ids, count = self.scan_top_async(n, known, sample, stream, mask)
         if stream is not None:
             stream.synchronize()
         m = int(count.cpu()[0])
         return scores[:m].cpu().numpy(), ids[:m].cpu().numpy()
 
-    def partners_top_async(self, queries, n: int, known=None, sample: int = None, stream=None):
+    def partners_top_async(self, queries, n: int, known=None, sample: int = None, stream=None, mask=None):
         """partners_top without the host copy: -> device tensors (scores f64[Q][n],
         ids int32[Q][n][3], counts int64[Q]); row i answers queries[i], its rows from counts[i] on
         are NaN / -1.  Nothing synchronises."""
@@ -309,8 +310,9 @@ class EMEngine:
         queries = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
         Q = int(queries.size)
         off, pairs = (None, None) if known is None else check_partner_known(known, Q)
-        with self._scan_call(None, sample, stream) as ((ctx, order, _, _, *params), s):   # no key table
-            ws = self.scan_workspace("partners", Q, n)
+        entry = self.lib.mmsbm_partners_topn if mask is None else self.lib.mmsbm_partners_topn_masked
+        with self._scan_call(None, sample, stream, mask) as ((ctx, order, _, _, *params), s):   # no key table
+            ws = self.scan_workspace("partners", Q, n)   # params: the mask (if any), theta, pr, the sample
             off_d = pairs_d = None
             if off is not None:
                 off_d = torch.from_numpy(off).to(self.device)
@@ -318,19 +320,21 @@ class EMEngine:
             scores = torch.empty((Q, n), dtype=torch.float64, device=self.device)
             ids = torch.empty((Q, n, 3), dtype=torch.int32, device=self.device)
             counts = torch.empty(Q, dtype=torch.int64, device=self.device)
-            _lib.check(self.lib.mmsbm_partners_topn(
+            _lib.check(entry(
                 ctx, order, _host_ptr(queries), Q, _ptr(off_d) if off_d is not None else None,
                 _ptr(pairs_d) if pairs_d is not None else None, *params, n, _ptr(ws), ws.numel(),
                 _ptr(scores), _ptr(ids), _ptr(counts), s.cuda_stream))
         return scores, ids, counts
 
-    def partners_top(self, queries, n: int, known=None, sample: int = None, stream=None):
+    def partners_top(self, queries, n: int, known=None, sample: int = None, stream=None, mask=None):
         """For each query gene id, its n most probable partner pairs (include/mmsbm.h
         mmsbm_partners_topn): -> one (scores f64[n'], ids int32[n'][3]) pair per query on the host,
         best first, n' <= n; an id row is the whole triple in key order, the query included.
         known: (known_off, known_pairs) of scan.partner_known for these queries; sample: a slot of
-        the active prefix, or None for the mean over it."""
-        scores, ids, counts = self.partners_top_async(queries, n, known, sample, stream)
+        the active prefix, or None for the mean over it.  mask: a pair mask (scan.pair_mask;
+        mmsbm_partners_topn_masked): a pair that is blocked, or holds a gene that forms a blocked pair
+        with the query, is no candidate; a query with none left gets an empty list."""
+        scores, ids, counts = self.partners_top_async(queries, n, known, sample, stream, mask)
         if stream is not None:
             stream.synchronize()
         counts, scores, ids = counts.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
@@ -503,24 +507,19 @@ class EMEngine:
         scan_above fetches what lies at or above it and the list is cut to n.  Exact: the three
         kernels see the same score bits under the same total order.  `limit`: as for scan_above
         (reached only when more than that many triples tie around rank n).
-        mask: a pair mask (scan.pair_mask).  The top-N kernel takes none, so with a mask scan_top is
-        never called: masked censuses bracket the threshold between 0 and 1 (scores are
-        probabilities), the masked scan_above fetches the rows and the list is cut to n."""
+        mask: a pair mask (scan.pair_mask), handed to each of the three calls: the same route over
+        the masked-eligible triples."""
         n = int(n)
         if n < 1:
             raise ValueError("scan_top_any needs n >= 1")
-        if mask is not None:
-            lo = bracket_threshold(n, 1.0, lambda t: self.census(t, known, sample, mask=mask)[0])
-            scores, ids = self.scan_above(lo, known, sample, limit=limit, mask=mask)
-            return scores[:n], ids[:n]
         max_n = int(self.lib.mmsbm_scan_max_n())
         if n <= max_n:
-            return self.scan_top(n, known, sample)
-        scores, ids = self.scan_top(max_n, known, sample)
+            return self.scan_top(n, known, sample, mask=mask)
+        scores, ids = self.scan_top(max_n, known, sample, mask=mask)
         if scores.size < max_n:         # fewer eligible triples than that: this is all of them
             return scores, ids
-        lo = bracket_threshold(n, float(scores[-1]), lambda t: self.census(t, known, sample)[0])
-        scores, ids = self.scan_above(lo, known, sample, limit=limit)
+        lo = bracket_threshold(n, float(scores[-1]), lambda t: self.census(t, known, sample, mask=mask)[0])
+        scores, ids = self.scan_above(lo, known, sample, limit=limit, mask=mask)
         return scores[:n], ids[:n]
 
     # ------------------------------------------------------------- vote scan

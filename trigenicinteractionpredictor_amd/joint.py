@@ -622,13 +622,17 @@ class Model:
                 blocked = np.concatenate([blocked, np.asarray(seen, dtype=np.int32)], axis=0)
         return pair_mask(P, pairs=blocked)
 
-    def _trigenic_known(self, exclude):
-        """The measured triples of the `exclude`d tables as sorted packed keys (scan.known_keys);
-        `test_links` holds the test pairs too (:511-533), which are no triples."""
-        from .scan import known_keys
+    def _trigenic_tables(self):
+        """(P, train ids, test ids) of the measured triples, as scan.known_keys and scan.partner_known
+        take them; `test_links` holds the test pairs too (:511-533), which are no triples."""
         tables = [np.array([[int(g) for g in key.split("_")] for key in table if key.count("_") == 2],
                            dtype=np.int64).reshape(-1, 3) for table in (self.links, self.test_links)]
-        return known_keys((self.P, *tables), exclude)
+        return (self.P, *tables)
+
+    def _trigenic_known(self, exclude):
+        """The measured triples of the `exclude`d tables as sorted packed keys (scan.known_keys)."""
+        from .scan import known_keys
+        return known_keys(self._trigenic_tables(), exclude)
 
     def predict_novel_trigenic(self, n, threshold=0.5, exclude=("train", "test")):
         """The n most probable triples of distinct genes outside the `exclude`d triplet tables none
@@ -638,6 +642,26 @@ class Model:
         scores, ids = self._push().tri.scan_top_any(int(n), self._trigenic_known(exclude), sample=0,
                                                     mask=self.digenic_mask(threshold))
         return [[float(p), "_".join(str(int(g)) for g in row), sorted(self.id_gene[int(g)] for g in row)]
+                for p, row in zip(scores, ids)]
+
+    def predict_trigenic_partners(self, gene, n, threshold=0.5, exclude=("train", "test")):
+        """The n most probable triples predict_novel_trigenic ranks that contain `gene` (an id or a
+        name), best first, rows as there: the partner scan of the gene on the triplet engine under
+        digenic_mask(threshold) (EMEngine.partners_top with the mask).  No listed triple holds a pair
+        the digenic side blocks, the pairs with `gene` included.  It stands to predict_novel_trigenic
+        as Model.predict_partners stands to predict_novel."""
+        from .scan import partner_known
+        try:
+            g = int(gene)
+        except ValueError:
+            g = self.gene_id[gene]
+        if not -self.P <= g < self.P:
+            raise IndexError("list index out of range")
+        g %= self.P
+        known = partner_known(self._trigenic_tables(), [g], exclude)
+        (scores, ids), = self._push().tri.partners_top([g], int(n), known, sample=0,
+                                                       mask=self.digenic_mask(threshold))
+        return [[float(p), "_".join(str(int(x)) for x in row), sorted(self.id_gene[int(x)] for x in row)]
                 for p, row in zip(scores, ids)]
 
     def novel_trigenic_census(self, thresholds, threshold=0.5, exclude=("train", "test")):

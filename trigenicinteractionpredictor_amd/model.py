@@ -421,22 +421,23 @@ class Model:
         eng = self._push()
         return float(eng.predict(np.array([ids], dtype=np.int32))[0, 0])
 
-    def predict_novel(self, n, exclude=("train", "test")):
+    def predict_novel(self, n, exclude=("train", "test"), mask=None):
         """The n most probable triples of distinct genes outside the `exclude`d link tables, best
         first: [probability, "i_j_k", [name1, name2, name3]] with the key as `links` spells it
         (:349-358), the probability of do_prediction (:530-547) and the names sorted as the
-        `nlinks` keys are.  One scan of all C(P, 3) triples on the GPU (engine.scan_top)."""
+        `nlinks` keys are.  One scan of all C(P, 3) triples on the GPU (engine.scan_top).  mask: a
+        pair mask (Model.pair_mask): no triple that contains a blocked pair of genes is listed."""
         from .scan import known_keys
         eng = self._push()
-        scores, ids = eng.scan_top(int(n), known_keys(self, exclude), sample=0)
+        scores, ids = eng.scan_top(int(n), known_keys(self, exclude), sample=0, **_masked(mask))
         return self._rows(scores, ids)
 
     def predict_novel_any(self, n, exclude=("train", "test"), mask=None):
         """predict_novel for any n >= 1: above the scan's cap of 4096 rows, censuses bracket the
         score of rank n and one threshold scan fetches what lies at or above it
         (engine.scan_top_any).  Up to the cap it is predict_novel.  mask: a pair mask
-        (Model.pair_mask): no triple that contains a blocked pair of genes is listed; every n then
-        goes through the masked censuses and the masked threshold scan."""
+        (Model.pair_mask): no triple that contains a blocked pair of genes is listed; the route is
+        the same, through the masked calls."""
         from .scan import known_keys
         scores, ids = self._push().scan_top_any(int(n), known_keys(self, exclude), sample=0, **_masked(mask))
         return self._rows(scores, ids)
@@ -479,22 +480,26 @@ class Model:
         return [[float(p), "_".join(str(int(g)) for g in row), sorted(self.id_gene[int(g)] for g in row)]
                 for p, row in zip(scores, ids)]
 
-    def predict_partners(self, gene, n, exclude=("train", "test")):
+    def predict_partners(self, gene, n, exclude=("train", "test"), mask=None):
         """The n most probable triples that contain `gene` (an id or a name) and two other, distinct
         genes, outside the `exclude`d link tables, best first; rows shaped like predict_novel's:
         [probability, "i_j_k", [name1, name2, name3]], the gene included in the key.  One partner
-        scan of its (P - 1)(P - 2) / 2 pairs on the GPU (engine.partners_top)."""
+        scan of its (P - 1)(P - 2) / 2 pairs on the GPU (engine.partners_top).  mask: a pair mask
+        (Model.pair_mask): no triple that contains a blocked pair of genes is listed, the pairs with
+        `gene` included."""
         from .scan import partner_known
         g = self._gene_arg(gene)
         eng = self._push()
-        (scores, ids), = eng.partners_top([g], int(n), partner_known(self, [g], exclude), sample=0)
+        (scores, ids), = eng.partners_top([g], int(n), partner_known(self, [g], exclude), sample=0, **_masked(mask))
         return self._rows(scores, ids)
 
-    def predict_third(self, gene1, gene2, n, exclude=("train", "test")):
+    def predict_third(self, gene1, gene2, n, exclude=("train", "test"), mask=None):
         """The n most probable third genes of the pair (gene1, gene2), best first, rows as
         predict_partners gives them.  The P - 2 listed triples go through the predict kernel and a
-        host sort under the scan's order (probability descending, equal ones by packed key)."""
-        from .scan import pack_keys, parse_exclude, rank_of, rank_order
+        host sort under the scan's order (probability descending, equal ones by packed key).  mask:
+        a pair mask (Model.pair_mask), applied on the host: a triple that contains a blocked pair is
+        left out, so a blocked query pair gives []."""
+        from .scan import check_pair_mask, pack_keys, parse_exclude, rank_of, rank_order
         g1, g2 = self._gene_arg(gene1), self._gene_arg(gene2)
         if g1 == g2:
             raise ValueError("predict_third needs two different genes")
@@ -507,6 +512,11 @@ class Model:
         tables = [self.links if name == "train" else self.test_links for name in parse_exclude(exclude)]
         keep = np.array([not any("_".join(str(int(g)) for g in row) in t for t in tables) for row in ids],
                         dtype=bool)
+        if mask is not None:
+            mask = check_pair_mask(mask, self.P)
+            a, b, c = pos[:, 0], pos[:, 1], pos[:, 2]      # sorted positions: the mask is read at x < y
+            bit = lambda x, y: ((mask[x, y >> 5] >> (y & 31).astype(np.uint32)) & np.uint32(1)).astype(bool)  # noqa: E731
+            keep &= ~(bit(a, b) | bit(a, c) | bit(b, c))
         ids = ids[keep]
         if not ids.shape[0]:
             return []

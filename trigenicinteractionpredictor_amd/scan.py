@@ -100,18 +100,17 @@ least.
                            score, from the predict kernel.  Not with --best and not with -n 1: one
                            restart has no spread.
 
-Two options restrict every table they apply to by PAIRS of genes (scan.pair_mask, the masked census
-and threshold scan, mmsbm_scan_census_masked / mmsbm_scan_above_masked): a triple that contains a
-blocked pair is not eligible.
+Two options restrict every table they apply to by PAIRS of genes (scan.pair_mask and the masked
+kernels, mmsbm_scan_topn_masked, mmsbm_scan_census_masked, mmsbm_scan_above_masked, ...): a triple
+that contains a blocked pair is not eligible.
     --allow-genes FILE     one gene name or id per line: the gene universe, such as the strains of an
                            array.  Every pair that touches another gene is blocked.
     --block-pairs FILE     two gene names or ids per line, tab or space separated: these pairs are
                            blocked, such as the pairs known to interact digenically.
-They apply to the main table (which then goes through `EMEngine.scan_top_any`: masked censuses find
-the cut, the masked threshold scan lists above it), --census, --network, --screen and --disputed (whose
-kernel takes the mask), and combine by OR.  With
---gene / --all-genes, --pairs, --gene-census, --consensus and --quorum, whose kernels take no mask,
-they are refused.  --heldout-ranks is not restricted by them.
+They apply to the main table (which then goes through `EMEngine.scan_top_any`: one masked top-N scan
+up to 4096 rows), --census, --network, --screen and --disputed, and combine by OR.  With
+--gene / --all-genes, --pairs, --gene-census, --consensus and --quorum, which the driver does not
+restrict yet, they are refused.  --heldout-ranks is not restricted by them.
 
 One more comes from the screen scan (`EMEngine.screen_top`, mmsbm_screen_topn): what crossing a
 double-mutant query against the array is predicted to find.
@@ -884,8 +883,8 @@ def parse(argv):
                          (cfg["gene_census"], "--gene-census"), (cfg.get("consensus"), "--consensus"),
                          (cfg.get("quorum"), "--quorum")):
             if on:
-                print("\n\nERROR: --allow-genes / --block-pairs restrict the main table, --census and --network: "
-                      "they do not go with %s, whose kernel takes no pair mask" % name)
+                print("\n\nERROR: --allow-genes / --block-pairs restrict the main table, --census, --network, "
+                      "--screen and --disputed: the driver does not apply them to %s" % name)
                 raise cli.ArgError()
     if any(key in cfg for key in ("screen", "screen_top", "query_pairs", "screen_best")):
         cfg.setdefault("screen", None)
@@ -1152,7 +1151,7 @@ def run(cfg, out=print, extras=None):
                 for g, (scores, ids) in zip(queries, lists) for i, (p, row) in enumerate(zip(scores, ids))]
     out("scanning %d genes: %s" % (model.P, "sample %d" % sample if sample is not None
                                    else "mean of %d samples" % B))
-    if mask is not None:    # the top-N kernel takes no mask: masked censuses and the masked threshold scan
+    if mask is not None:    # the masked top-N scan; above its cap masked censuses and the masked threshold scan
         scores, ids = eng.scan_top_any(cfg["top"], known, sample, mask=mask)
     else:
         scores, ids = eng.scan_top(cfg["top"], known, sample)
