@@ -625,6 +625,58 @@ int mmsbm_screen_scores(mmsbm_ctx *ctx, const int32_t *order, const int32_t *pai
                         const double *theta, const double *pr, int32_t sample, void *ws,
                         int64_t ws_bytes, double *out, void *stream);
 
+/* Screen statistics: a query pair's row, and the exact top N of it, by an order statistic of the
+ * restarts' own scores instead of one slot or the mean: what mmsbm_scan_quorum_topn and
+ * mmsbm_scan_spread_topn are genome-wide, per query pair.  Everything not said here (the queries, x < y,
+ * the candidates c, the packed key, pairs_host, known_off / known_thirds, mask, Q, N, P, the outputs,
+ * the workspace, MMSBM_SCREEN_CHUNK, the stream) is mmsbm_screen_topn's and mmsbm_screen_scores's.
+ * Slots: the ns = n_active slots of the active prefix; there is no sample argument.  For a query
+ * (x, y) and a position c, slot s's OWN SCORE is the word mmsbm_screen_scores(sample = s) writes at
+ * [query][c], bit for bit: the same v vectors (screen_prep_kernel), the same MFMA chain from zero
+ * over ascending k, each element keeping the chain of its own region.
+ *   stat = MMSBM_SCREEN_STAT_QUORUM, arg = m in [1, ns]: the value is q_m, the m-th largest of the
+ *     slots' own scores (m = 1: the maximum, m = ns: the minimum).  No floating-point value is combined
+ *     across slots: the value is one slot's word, and with ns = 1, m = 1 the row is slot 0's row bit
+ *     for bit.  At least m slots score c at or above T exactly when q_m >= T.
+ *   stat = MMSBM_SCREEN_STAT_SPREAD, arg = the trim t >= 0 with ns - 2 t >= 2: the value is
+ *     d_t = q_{1+t} - q_{ns-t}, ONE IEEE subtraction of two slot scores, so d_t >= +0 (t = 0: the
+ *     range max - min).  Slots that agree bit for bit give +0 with the sign bit clear.
+ * The kernel keeps, per element, the D largest and the D smallest scores in sorted lists held in
+ * registers, D = min(m, ns - m + 1) for the quorum (the m-th largest is the (ns - m + 1)-th smallest:
+ * the shorter list is read) and D = t + 1 for the spread; D <= mmsbm_screen_stat_max_depth() = 4, the
+ * caps of mmsbm_scan_quorum_max_depth and mmsbm_scan_spread_max_trim.  Every slot of a row is formed
+ * before anything is selected: there is no early exit.
+ * Eligibility is exactly the screen scan's (c not in {x, y}; the query's known slice; the mask bits of
+ * (x, y), (x, c), (y, c)); an ineligible place of a row is NaN and is no candidate of a list.
+ * mmsbm_screen_stat_scores, result (device): out f64[Q][P] by RANK POSITION, as mmsbm_screen_scores.
+ * mmsbm_screen_stat_topn, result (device): out_scores f64[Q][N], out_ids int32[Q][N][3], out_count
+ * int64[Q] as mmsbm_screen_topn: the query's best N values under the screen scan's total order (value
+ * descending; equal values by the smaller packed key of the sorted triple, i.e. smaller c first), the
+ * tail NaN / -1; the scores are the words of the row.  Q = 0 returns MMSBM_OK and writes nothing;
+ * P < 3: counts 0 and rows of NaN.
+ * A row or a list depends on (x, y), the active slots and the eligibility only: not on Q, on the other
+ * queries, on the order in which the pair's two ids were given, on the pass size or on the grid (every
+ * chain has a fixed order, max and min are exact, no score is formed by an atomic).
+ * Refusals, all before any device call and with the outputs untouched: those of mmsbm_screen_topn /
+ * mmsbm_screen_scores (without the sample's), and MMSBM_ERR_INVALID: an unknown stat; m outside
+ * [1, ns]; t < 0 or ns - 2 t < 2; the spread with ns < 2.  MMSBM_ERR_UNSUPPORTED: a legal argument
+ * whose depth D exceeds mmsbm_screen_stat_max_depth().
+ * ws: mmsbm_screen_workspace_bytes(ctx, Q, N) bytes, N = 0 for mmsbm_screen_stat_scores: the screen
+ * scan's workspace, no larger.  Replaces nothing in the reference. */
+#define MMSBM_SCREEN_STAT_QUORUM 0
+#define MMSBM_SCREEN_STAT_SPREAD 1
+int mmsbm_screen_stat_max_depth(void);
+int mmsbm_screen_stat_topn(mmsbm_ctx *ctx, const int32_t *order, const int32_t *pairs_host, int64_t Q,
+                           const int64_t *known_off, const int32_t *known_thirds,
+                           const uint32_t *mask, const double *theta, const double *pr, int32_t stat,
+                           int32_t arg, int32_t N, void *ws, int64_t ws_bytes, double *out_scores,
+                           int32_t *out_ids, int64_t *out_count, void *stream);
+int mmsbm_screen_stat_scores(mmsbm_ctx *ctx, const int32_t *order, const int32_t *pairs_host, int64_t Q,
+                             const int64_t *known_off, const int32_t *known_thirds,
+                             const uint32_t *mask, const double *theta, const double *pr,
+                             int32_t stat, int32_t arg, void *ws, int64_t ws_bytes, double *out,
+                             void *stream);
+
 /* Link-sharded iteration (single sample over N ranks): each rank's context
  * holds 1/N of the train links (mmsbm_set_links) and the GLOBAL degree (mmsbm_set_degree).
  * Step 1, the accumulation half of make_iteration (:986-1012) over this rank's links:

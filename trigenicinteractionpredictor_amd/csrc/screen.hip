@@ -25,6 +25,9 @@
 // its candidate buffer (wave_reserve, wg_keep_best) and writes the best N: it sees the whole row, so
 // there is no merge and no published bound.  Every sum has a fixed order and no score is formed by
 // an atomic: a query's row depends on (x, y), the sample and the eligibility only.
+// screen_stat_kernel (mmsbm_screen_stat_*): the same tile with an order statistic of the slots' own
+// scores in the mean's place, the quorum score q_m or the spread q_{1+t} - q_{ns-t}, from
+// per-element sorted lists in registers; the rest of a stat call is the screen scan's host side.
 
 #include <hip/hip_runtime.h>
 
@@ -253,6 +256,119 @@ __global__ __launch_bounds__(NT) void screen_score_kernel(ScreenArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Stat score: the row of a statistic of the slots' own scores (mmsbm_screen_stat_*).  The tiling, the
+// grid, the wave-to-c-tile rule, the region ballots, the eligibility and the store tail are
+// screen_score_kernel's.  Each slot's `res` is formed as that kernel's ensemble path forms it (A from
+// V[s][q][reg][KP], B from thT, every needed region's chain from zero), so it is the word
+// mmsbm_screen_scores(sample = s) writes; instead of being added to a total it is inserted into two
+// per-element sorted lists of depth D held in registers, `top` (the D largest, descending) and `bot`
+// (the D smallest, ascending), by the max / min chain of scan_score.h's tile_spread with
+// compile-time indices.  The wave-uniform `mode` picks the value once the row's slots are all in
+// (nothing is selected before the row is complete, so no slot is skipped): the D-th largest, the
+// D-th smallest or their difference, one IEEE subtraction.  The host guarantees D <= ns (quorum) or
+// 2 D <= ns (spread), so no start value reaches the output.  No floating-point value is combined
+// across slots except in that subtraction.
+// ------------------------------------------------------------------------------------------
+enum : int { STAT_TOP = 0, STAT_BOT = 1, STAT_SPREAD = 2 };
+
+template <int KS, int D>
+__global__ __launch_bounds__(NT) void screen_stat_kernel(ScreenArgs A, int mode) {
+  constexpr int KP = 4 * KS;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = lane & 15, kk = lane >> 4;
+  const int P = A.P, P16 = A.P16, ns = A.ns, nq = A.nq;
+  const int q0 = blockIdx.y * 16;
+  const int arow = min(q0 + m, nq - 1);  // rows past the pass repeat its last query; they are not written
+  // the lane's four output rows q0 + kk + 4 i: positions, known slice, the query's own pair
+  int xs[4], ys[4];
+  long long klo[4], khi[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = q0 + kk + 4 * i;
+    xs[i] = ys[i] = -1;
+    klo[i] = khi[i] = 0;
+    if (r < nq) {
+      const int gq = A.q_base + r;
+      xs[i] = A.xy[2 * gq];
+      ys[i] = A.xy[2 * gq + 1];
+      if (A.known_off) {
+        klo[i] = A.known_off[gq];
+        khi[i] = A.known_off[gq + 1];
+      }
+      if (xs[i] >= 0 && A.mask && blocked(A.mask, A.MW, xs[i], ys[i])) xs[i] = ys[i] = -1;  // no candidate
+    }
+  }
+  const int nct = P16 / 16;
+  const double inf = __builtin_huge_val();
+  for (int ct = blockIdx.x * 4 + wave; ct < nct; ct += gridDim.x * 4) {
+    const int c = ct * 16 + m;  // < P16
+    int region[4];
+    bool mine[3] = {false, false, false};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      region[i] = c < xs[i] ? 0 : c < ys[i] ? 1 : 2;
+      if (xs[i] >= 0 && c < P) {
+        mine[0] |= region[i] == 0;
+        mine[1] |= region[i] == 1;
+        mine[2] |= region[i] == 2;
+      }
+    }
+    const bool need[3] = {__ballot(mine[0]) != 0, __ballot(mine[1]) != 0, __ballot(mine[2]) != 0};  // wave-uniform
+    d4v top[D], bot[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      top[j] = d4v{-inf, -inf, -inf, -inf};
+      bot[j] = d4v{inf, inf, inf, inf};
+    }
+    for (int s = 0; s < ns; ++s) {
+      const double* __restrict__ tc = A.thT + ((size_t)s * KP + kk) * P16 + c;
+      double b[KS];
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) b[ks] = tc[(size_t)(4 * ks) * P16];
+      d4v res = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int reg = 0; reg < 3; ++reg) {
+        if (!need[reg]) continue;
+        d4v acc = {0.0, 0.0, 0.0, 0.0};
+        const double* __restrict__ vr = A.V + (((size_t)s * nq + arow) * 3 + reg) * KP + kk;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(vr[4 * ks], b[ks], acc, 0, 0, 0);
+        // lane holds S[q0 + kk + 4 i][c]: every element keeps the chain of its own region
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (region[i] == reg) res[i] = acc[i];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        double x = res[i], y = res[i];
+#pragma unroll
+        for (int j = 0; j < D; ++j) {  // each list keeps the better of the two, x / y carry the other on
+          const double hi = fmax(top[j][i], x), lo = fmin(top[j][i], x);
+          top[j][i] = hi;
+          x = lo;
+          const double lo2 = fmin(bot[j][i], y), hi2 = fmax(bot[j][i], y);
+          bot[j][i] = lo2;
+          y = hi2;
+        }
+      }
+    }
+    const d4v tot = mode == STAT_TOP ? top[D - 1] : mode == STAT_BOT ? bot[D - 1] : top[D - 1] - bot[D - 1];
+    if (c >= P) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = q0 + kk + 4 * i;
+      if (r >= nq) continue;
+      const int x = xs[i], y = ys[i];
+      bool ok = x >= 0 && c != x && c != y;
+      if (ok && khi[i] > klo[i]) ok = !third_known(A.known, klo[i], khi[i], c);
+      if (ok && A.mask) ok = !blocked(A.mask, A.MW, min(x, c), max(x, c)) && !blocked(A.mask, A.MW, min(y, c), max(y, c));
+      A.out[(size_t)r * A.ld + c] = ok ? tot[i] : __builtin_nan("");
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // Select, grid nq: workgroup r keeps the best N of row r (NaN: not eligible) under the scan's total
 // order and writes the query's list: scores, gene ids in key order, count, NaN / -1 tail.
 // ------------------------------------------------------------------------------------------
@@ -378,17 +494,68 @@ int make_plan(const mmsbm_ctx* c, long long Q, int N, bool masked, ScreenPlan* p
   return MMSBM_OK;
 }
 
-// One call of either entry: N = 0 writes the rows to out_rows [Q][P], N >= 1 the lists.
+constexpr int STAT_MAX_DEPTH = 4;  // the deepest sorted lists screen_stat_kernel is built for
+
+// f(std::integral_constant<int, D>{}) for D in [1, STAT_MAX_DEPTH]
+template <class F>
+int dispatch_depth(int d, F&& f) {
+  switch (d) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
+
+// The (stat, arg) of a stat entry over ns scored slots -> the kernel's list depth and mode, after the
+// checks of include/mmsbm.h.
+int stat_plan(int stat, int arg, int ns, int* depth, int* mode) {
+  if (stat == MMSBM_SCREEN_STAT_QUORUM) {
+    if (arg < 1 || arg > ns)
+      return fail(MMSBM_ERR_INVALID, "the screen scan: votes m=%d outside [1, %d], the scored slots", arg, ns);
+    const int from_top = arg, from_bot = ns - arg + 1;  // the m-th largest is the (ns - m + 1)-th smallest
+    *depth = std::min(from_top, from_bot);
+    *mode = from_top <= from_bot ? STAT_TOP : STAT_BOT;
+    if (*depth > STAT_MAX_DEPTH)
+      return fail(MMSBM_ERR_UNSUPPORTED,
+                  "the screen scan: m=%d of %d slots needs a sorted list of depth %d, above the cap of %d "
+                  "(mmsbm_screen_stat_max_depth)",
+                  arg, ns, *depth, STAT_MAX_DEPTH);
+    return MMSBM_OK;
+  }
+  if (stat == MMSBM_SCREEN_STAT_SPREAD) {
+    if (ns < 2)
+      return fail(MMSBM_ERR_INVALID, "the screen scan: %d active slot: one restart has no spread", ns);
+    if (arg < 0 || ns - 2 * (long long)arg < 2)
+      return fail(MMSBM_ERR_INVALID, "the screen scan: trim=%d outside [0, %d]: %d scored slots must keep two scores",
+                  arg, (ns - 2) / 2, ns);
+    *depth = arg + 1;
+    *mode = STAT_SPREAD;
+    if (*depth > STAT_MAX_DEPTH)
+      return fail(MMSBM_ERR_UNSUPPORTED,
+                  "the screen scan: trim=%d of %d slots needs two sorted lists of depth %d, above the cap of %d "
+                  "(mmsbm_screen_stat_max_depth)",
+                  arg, ns, *depth, STAT_MAX_DEPTH);
+    return MMSBM_OK;
+  }
+  return fail(MMSBM_ERR_INVALID, "the screen scan: unknown statistic %d", stat);
+}
+
+// One call of any entry: N = 0 writes the rows to out_rows [Q][P], N >= 1 the lists.  stat = null:
+// the row of `sample` (screen_score_kernel); otherwise the row of the statistic (stat[0], stat[1]) =
+// (stat, arg) over the active slots (screen_stat_kernel), with sample = -1.
 int screen_run(mmsbm_ctx* c, const int32_t* order, const int32_t* pairs_host, int64_t Q, const int64_t* known_off,
                const int32_t* known_thirds, const uint32_t* mask, const double* theta, const double* pr,
-               int32_t sample, int32_t N, void* ws, int64_t ws_bytes, double* out_rows, double* out_scores,
-               int32_t* out_ids, int64_t* out_count, void* stream) {
+               int32_t sample, const int32_t* stat, int32_t N, void* ws, int64_t ws_bytes, double* out_rows,
+               double* out_scores, int32_t* out_ids, int64_t* out_count, void* stream) {
   if (!c) return fail(MMSBM_ERR_INVALID, "null context");
   ScreenPlan p;
   int rc = make_plan(c, Q, N, mask != nullptr, &p);
   if (rc) return rc;
-  if (Q == 0) return MMSBM_OK;
   const ScanShape& sh = p.sh;
+  int depth = 0, mode = 0;
+  if (stat && (rc = stat_plan(stat[0], stat[1], sh.nact, &depth, &mode))) return rc;
+  if (Q == 0) return MMSBM_OK;
   const bool lists = N > 0;
   const char* remedy = "mmsbm_screen_workspace_bytes";
   if (!order || !theta || !pr || !pairs_host ||
@@ -442,9 +609,16 @@ int screen_run(mmsbm_ctx* c, const int32_t* order, const int32_t* pairs_host, in
     a.K = sh.K, a.P = sh.P, a.P16 = sh.P16, a.ns = ns, a.nq = nq, a.q_base = q_base;
     const dim3 grid(std::min((nct + 3) / 4, SCORE_GRID_X), (nq + 15) / 16);
     rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
-      screen_score_kernel<decltype(ks)::value><<<grid, NT, 0, s>>>(a);
-      HIP_TRY(hipGetLastError());
-      return (int)MMSBM_OK;
+      if (!stat) {
+        screen_score_kernel<decltype(ks)::value><<<grid, NT, 0, s>>>(a);
+        HIP_TRY(hipGetLastError());
+        return (int)MMSBM_OK;
+      }
+      return dispatch_depth(depth, [&](auto d) {
+        screen_stat_kernel<decltype(ks)::value, decltype(d)::value><<<grid, NT, 0, s>>>(a, mode);
+        HIP_TRY(hipGetLastError());
+        return (int)MMSBM_OK;
+      });
     });
     if (rc) return rc;
     if (!lists) continue;
@@ -478,16 +652,39 @@ int mmsbm_screen_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* pairs_h
                       double* out_scores, int32_t* out_ids, int64_t* out_count, void* stream) {
   if (!c) return fail(MMSBM_ERR_INVALID, "null context");
   if (N == 0) return fail(MMSBM_ERR_UNSUPPORTED, "N=0 outside the screen scan's [1, %d]", SCREEN_MAX_N);
-  return screen_run(c, order, pairs_host, Q, known_off, known_thirds, mask, theta, pr, sample, N, ws, ws_bytes,
-                    nullptr, out_scores, out_ids, out_count, stream);
+  return screen_run(c, order, pairs_host, Q, known_off, known_thirds, mask, theta, pr, sample, nullptr, N, ws,
+                    ws_bytes, nullptr, out_scores, out_ids, out_count, stream);
 }
 
 int mmsbm_screen_scores(mmsbm_ctx* c, const int32_t* order, const int32_t* pairs_host, int64_t Q,
                         const int64_t* known_off, const int32_t* known_thirds, const uint32_t* mask,
                         const double* theta, const double* pr, int32_t sample, void* ws, int64_t ws_bytes,
                         double* out, void* stream) {
-  return screen_run(c, order, pairs_host, Q, known_off, known_thirds, mask, theta, pr, sample, 0, ws, ws_bytes, out,
-                    nullptr, nullptr, nullptr, stream);
+  return screen_run(c, order, pairs_host, Q, known_off, known_thirds, mask, theta, pr, sample, nullptr, 0, ws,
+                    ws_bytes, out, nullptr, nullptr, nullptr, stream);
+}
+
+int mmsbm_screen_stat_max_depth(void) { return STAT_MAX_DEPTH; }
+
+int mmsbm_screen_stat_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* pairs_host, int64_t Q,
+                           const int64_t* known_off, const int32_t* known_thirds, const uint32_t* mask,
+                           const double* theta, const double* pr, int32_t stat, int32_t arg, int32_t N, void* ws,
+                           int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count,
+                           void* stream) {
+  if (!c) return fail(MMSBM_ERR_INVALID, "null context");
+  if (N == 0) return fail(MMSBM_ERR_UNSUPPORTED, "N=0 outside the screen scan's [1, %d]", SCREEN_MAX_N);
+  const int32_t stat_arg[2] = {stat, arg};
+  return screen_run(c, order, pairs_host, Q, known_off, known_thirds, mask, theta, pr, -1, stat_arg, N, ws, ws_bytes,
+                    nullptr, out_scores, out_ids, out_count, stream);
+}
+
+int mmsbm_screen_stat_scores(mmsbm_ctx* c, const int32_t* order, const int32_t* pairs_host, int64_t Q,
+                             const int64_t* known_off, const int32_t* known_thirds, const uint32_t* mask,
+                             const double* theta, const double* pr, int32_t stat, int32_t arg, void* ws,
+                             int64_t ws_bytes, double* out, void* stream) {
+  const int32_t stat_arg[2] = {stat, arg};
+  return screen_run(c, order, pairs_host, Q, known_off, known_thirds, mask, theta, pr, -1, stat_arg, 0, ws, ws_bytes,
+                    out, nullptr, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

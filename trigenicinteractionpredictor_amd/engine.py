@@ -225,7 +225,8 @@ class EMEngine:
 
     def scan_workspace(self, family: str, *size_args) -> torch.Tensor:
         """The scratch of one family ("scan", "partners", "census", "pair_census", "scan_above",
-        "scan_votes", "scan_quorum", "scan_spread", "screen"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device."""
+        "scan_votes", "scan_quorum", "scan_spread", "screen"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device.
+        The screen scan's statistics (screen_quorum_*, screen_spread_*) run in the "screen" scratch."""
         nbytes = ctypes.c_int64()
         _lib.check(getattr(self.lib, "mmsbm_%s_workspace_bytes" % family)(self.ctx, *size_args,
                                                                           ctypes.byref(nbytes)))
@@ -402,6 +403,113 @@ class EMEngine:
         genes, the thirds of `known`, what `mask` blocks); elsewhere exactly the bits screen_top
         ranks.  known, sample, mask: as for screen_top."""
         out = self.screen_scores_async(pairs, known, sample, stream, mask)
+        if stream is not None:
+            stream.synchronize()
+        return out.cpu().numpy()
+
+    # ------------------------------------------------------ screen statistics
+    @property
+    def screen_stat_max_depth(self) -> int:
+        """mmsbm_screen_stat_max_depth(): the deepest per-element sorted lists the screen scan's
+        statistics kernel holds (quorum_max_depth, and spread_max_trim + 1)."""
+        return int(self.lib.mmsbm_screen_stat_max_depth())
+
+    def _screen_votes(self, min_votes) -> int:
+        """-> min_votes as an int (None: every active slot, as quorum_top defaults); ValueError
+        outside [1, active]."""
+        ns = self.active
+        m = ns if min_votes is None else int(min_votes)
+        if not 1 <= m <= ns:
+            raise ValueError("min_votes %d outside [1, %d], the scored slots" % (m, ns))
+        return m
+
+    def _screen_stat_top_async(self, pairs, n, stat, arg, known, stream, mask):
+        """mmsbm_screen_stat_topn -> device tensors as screen_top_async returns them."""
+        n = int(n)
+        with self._screen_call(pairs, known, None, stream, mask, n) as (Q, head, ws, s):
+            scores = torch.empty((Q, n), dtype=torch.float64, device=self.device)
+            ids = torch.empty((Q, n, 3), dtype=torch.int32, device=self.device)
+            counts = torch.empty(Q, dtype=torch.int64, device=self.device)
+            # head ends with the sample, which the stat entries do not take
+            _lib.check(self.lib.mmsbm_screen_stat_topn(*head[:-1], stat, arg, n, *ws, _ptr(scores), _ptr(ids),
+                                                       _ptr(counts), s.cuda_stream))
+        return scores, ids, counts
+
+    def _screen_stat_scores_async(self, pairs, stat, arg, known, stream, mask):
+        """mmsbm_screen_stat_scores -> a device tensor as screen_scores_async returns it."""
+        with self._screen_call(pairs, known, None, stream, mask, 0) as (Q, head, ws, s):
+            out = torch.empty((Q, self.P), dtype=torch.float64, device=self.device)
+            _lib.check(self.lib.mmsbm_screen_stat_scores(*head[:-1], stat, arg, *ws, _ptr(out), s.cuda_stream))
+            rank = torch.from_numpy(rank_of(rank_order(self.P))).to(self.device)
+            return out[:, rank].contiguous()    # [q][g] = the kernel's [q][rank[g]]
+
+    def _screen_lists(self, tensors, stream):
+        """screen_top's host lists from the device tensors of a *_top_async."""
+        scores, ids, counts = tensors
+        if stream is not None:
+            stream.synchronize()
+        counts, scores, ids = counts.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
+        return [(scores[i, :int(m)].copy(), ids[i, :int(m)].copy()) for i, m in enumerate(counts)]
+
+    def screen_quorum_top_async(self, pairs, n: int, min_votes: int = None, known=None, stream=None, mask=None):
+        """screen_quorum_top without the host copy: -> device tensors as screen_top_async returns
+        them.  Nothing synchronises."""
+        m = self._screen_votes(min_votes)       # ValueError before anything is uploaded
+        return self._screen_stat_top_async(pairs, n, _lib.MMSBM_SCREEN_STAT_QUORUM, m, known, stream, mask)
+
+    def screen_quorum_top(self, pairs, n: int, min_votes: int = None, known=None, stream=None, mask=None):
+        """For each query pair of gene ids, its n third genes with the highest quorum score
+        (include/mmsbm.h mmsbm_screen_stat_topn, MMSBM_SCREEN_STAT_QUORUM): q_m = the m-th largest of
+        the active slots' own screen_scores(sample=s) words, m = min_votes (None: every active slot,
+        the minimum over them; 1: the maximum).  At least m restarts score a third gene at or above T
+        exactly when its q_m >= T.  -> lists as screen_top returns them, best first under its total
+        order.  min_votes outside [1, active] raises ValueError; a depth min(m, active - m + 1) above
+        screen_stat_max_depth raises MMSBMError (MMSBM_ERR_UNSUPPORTED).  known, mask: as for
+        screen_top."""
+        return self._screen_lists(self.screen_quorum_top_async(pairs, n, min_votes, known, stream, mask), stream)
+
+    def screen_quorum_scores_async(self, pairs, min_votes: int = None, known=None, stream=None, mask=None):
+        """screen_quorum_scores without the host copy: -> a device tensor f64[Q][P] indexed by the
+        third gene's id.  Nothing synchronises."""
+        m = self._screen_votes(min_votes)
+        return self._screen_stat_scores_async(pairs, _lib.MMSBM_SCREEN_STAT_QUORUM, m, known, stream, mask)
+
+    def screen_quorum_scores(self, pairs, min_votes: int = None, known=None, stream=None, mask=None):
+        """Every query pair's whole row of quorum scores (mmsbm_screen_stat_scores): -> f64[Q][P] on
+        the host indexed by gene id as screen_scores returns it, NaN where the gene is not eligible;
+        elsewhere exactly the bits screen_quorum_top ranks, each one the word of one slot's
+        screen_scores row.  min_votes, known, mask: as for screen_quorum_top."""
+        out = self.screen_quorum_scores_async(pairs, min_votes, known, stream, mask)
+        if stream is not None:
+            stream.synchronize()
+        return out.cpu().numpy()
+
+    def screen_spread_top_async(self, pairs, n: int, trim: int = 0, known=None, stream=None, mask=None):
+        """screen_spread_top without the host copy: -> device tensors as screen_top_async returns
+        them.  Nothing synchronises."""
+        trim = self._spread_trim(trim)          # ValueError before anything is uploaded
+        return self._screen_stat_top_async(pairs, n, _lib.MMSBM_SCREEN_STAT_SPREAD, trim, known, stream, mask)
+
+    def screen_spread_top(self, pairs, n: int, trim: int = 0, known=None, stream=None, mask=None):
+        """For each query pair of gene ids, the n third genes on which the active slots disagree most
+        (mmsbm_screen_stat_topn, MMSBM_SCREEN_STAT_SPREAD): ranked by d_t = q_{1+t} - q_{ns-t},
+        t = trim, over the ns = active slots' own screen_scores words (trim = 0: max - min).
+        -> lists as screen_top returns them.  Fewer than two active slots and a trim outside
+        spread_trims' rule raise ValueError; a legal trim above screen_stat_max_depth - 1 raises
+        MMSBMError (MMSBM_ERR_UNSUPPORTED).  known, mask: as for screen_top."""
+        return self._screen_lists(self.screen_spread_top_async(pairs, n, trim, known, stream, mask), stream)
+
+    def screen_spread_scores_async(self, pairs, trim: int = 0, known=None, stream=None, mask=None):
+        """screen_spread_scores without the host copy: -> a device tensor f64[Q][P] indexed by the
+        third gene's id.  Nothing synchronises."""
+        trim = self._spread_trim(trim)
+        return self._screen_stat_scores_async(pairs, _lib.MMSBM_SCREEN_STAT_SPREAD, trim, known, stream, mask)
+
+    def screen_spread_scores(self, pairs, trim: int = 0, known=None, stream=None, mask=None):
+        """Every query pair's whole row of spreads (mmsbm_screen_stat_scores): -> f64[Q][P] on the
+        host indexed by gene id, NaN where the gene is not eligible; elsewhere >= +0 and exactly the
+        bits screen_spread_top ranks.  trim, known, mask: as for screen_spread_top."""
+        out = self.screen_spread_scores_async(pairs, trim, known, stream, mask)
         if stream is not None:
             stream.synchronize()
         return out.cpu().numpy()

@@ -108,7 +108,8 @@ that contains a blocked pair is not eligible.
     --block-pairs FILE     two gene names or ids per line, tab or space separated: these pairs are
                            blocked, such as the pairs known to interact digenically.
 They apply to the main table (which then goes through `EMEngine.scan_top_any`: one masked top-N scan
-up to 4096 rows), --census, --network, --screen and --disputed, and combine by OR.  With
+up to 4096 rows), --census, --network, --screen (with --screen-quorum and --screen-disputed) and
+--disputed, and combine by OR.  With
 --gene / --all-genes, --pairs, --gene-census, --consensus and --quorum, which the driver does not
 restrict yet, they are refused.  --heldout-ranks is not restricted by them.
 
@@ -121,6 +122,24 @@ double-mutant query against the array is predicted to find.
                            from exactly one of --query-pairs FILE (the format of --block-pairs) and
                            --screen-best Q (the Q pairs --pairs ranks first at --pair-threshold, under
                            the same exclude and mask).  --allow-genes / --block-pairs apply to it.
+
+Two more come from the screen scan's statistics (`EMEngine.screen_quorum_top`, `screen_spread_top`,
+mmsbm_screen_stat_topn): --quorum and --disputed per query pair, over the query pairs of --query-pairs
+or --screen-best and with the same --screen-top rows per pair.  Either goes with or without --screen.
+    --screen-quorum FILE   per query pair, its --screen-top third genes ranked by their quorum score:
+                           the M-th largest of the -n restarts' own P(r = 1), --screen-votes M (in
+                           [1, -n]; default -n: the minimum over the restarts; the depth rule of
+                           --quorum-votes).  A third gene has at least M votes at a threshold T exactly
+                           when its quorum score is >= T.  The header comments give `# samples` and
+                           `# screen votes`; then query, rank, quorum, mean, min, max, ids, names rows,
+                           in query order and then by rank.
+    --screen-disputed FILE per query pair, its --screen-top third genes ranked by the spread of the
+                           -n restarts' own P(r = 1), --screen-trim T (default 0: max - min; the rule
+                           of --disputed-trim).  The header comments give `# samples` and
+                           `# screen trim`; then query, rank, spread, mean, min, max, ids, names rows.
+mean, min and max are the listed triple's ensemble mean and its lowest and highest restart score, from
+the predict kernel.  --exclude, --allow-genes and --block-pairs apply as they do to --screen.  Not
+with --best (and --screen-disputed not with -n 1): one restart has no quorum and no spread.
 
 Exactness: the counts are exact for the scan's score bits.  A listed triple's probability comes from
 the predict kernel, which sums in another order, so a triple within rounding distance (about 1e-12
@@ -150,6 +169,7 @@ DEFAULT_SCREEN_TOP = 20  # --screen without --screen-top: the rows per query pai
 MAX_SCREEN_QUERIES = 65535   # the most query pairs one mmsbm_screen_topn call takes
 MAX_QUORUM_DEPTH = 4     # mmsbm_scan_quorum_max_depth(): the deepest sorted list of the quorum scan
 MAX_SPREAD_TRIM = 3      # mmsbm_scan_spread_max_trim(): the largest trim of the dispute scan
+MAX_SCREEN_STAT_DEPTH = 4    # mmsbm_screen_stat_max_depth(): the deepest sorted lists of the screen statistics
 DEFAULT_THRESHOLDS = (0.99, 0.95, 0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3, 0.2, 0.1, 0.05, 0.02, 0.01, 0.005,
                       0.002, 0.001)   # --census without --thresholds
 
@@ -680,6 +700,10 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [--screen-top=] <rows per query pair, in [1, 1024]; default 20>
     [--query-pairs=] <file, two gene names or ids per line: the query pairs of --screen>
     [--screen-best=] <Q: the query pairs of --screen are the Q best of --pairs at --pair-threshold>
+    [--screen-quorum=] <TSV file: per query pair, its --screen-top third genes by their M-th best restart score>
+    [--screen-votes=] <M, an integer in [1, restarts]; default: all restarts (the minimum over them)>
+    [--screen-disputed=] <TSV file: per query pair, its --screen-top third genes by the spread of the restarts' scores>
+    [--screen-trim=] <T, an integer >= 0 with restarts - 2 T >= 2, at most 3; default 0 (max - min)>
 """
 
 
@@ -696,7 +720,9 @@ def parse(argv):
     # consensus_limit) and --quorum with its two (quorum, quorum_votes); --allow-genes and
     # --block-pairs add their two (allow_genes, block_pairs) when one of them is given; --screen adds
     # its four (screen, screen_top, query_pairs, screen_best) in the same way, and --disputed its two
-    # (disputed, disputed_trim)
+    # (disputed, disputed_trim); --screen-quorum and --screen-disputed add their two each
+    # (screen_quorum, screen_votes; screen_disputed, screen_trim) and, being tables over --screen's
+    # query pairs, --screen's four
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
@@ -708,7 +734,8 @@ def parse(argv):
                                                         "consensus-limit=", "quorum=", "quorum-votes=",
                                                         "allow-genes=", "block-pairs=", "screen=",
                                                         "screen-top=", "query-pairs=", "screen-best=",
-                                                        "disputed=", "disputed-trim="])
+                                                        "disputed=", "disputed-trim=", "screen-quorum=",
+                                                        "screen-votes=", "screen-disputed=", "screen-trim="])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -798,6 +825,20 @@ def parse(argv):
                     print("\n\nERROR: --disputed-trim should be an integer number >= 0")
                     raise cli.ArgError()
                 cfg["disputed_trim"] = int(arg)
+            elif opt == "--screen-quorum":
+                cfg["screen_quorum"] = arg
+            elif opt == "--screen-votes":
+                if not int(arg) >= 1:
+                    print("\n\nERROR: --screen-votes should be an integer number in [1, restarts (-n)]")
+                    raise cli.ArgError()
+                cfg["screen_votes"] = int(arg)
+            elif opt == "--screen-disputed":
+                cfg["screen_disputed"] = arg
+            elif opt == "--screen-trim":
+                if not int(arg) >= 0:
+                    print("\n\nERROR: --screen-trim should be an integer number >= 0")
+                    raise cli.ArgError()
+                cfg["screen_trim"] = int(arg)
             elif opt == "--allow-genes":
                 cfg["allow_genes"] = arg
             elif opt == "--block-pairs":
@@ -876,6 +917,38 @@ def parse(argv):
         if cfg["disputed"] and cfg["best"]:
             print("\n\nERROR: --disputed ranks by the spread across the restarts: it does not go with --best")
             raise cli.ArgError()
+    if any(key in cfg for key in ("screen_quorum", "screen_votes")):
+        cfg.setdefault("screen_quorum", None)
+        cfg.setdefault("screen_votes", cfg["samples"])      # every restart
+        cfg.setdefault("screen", None)                      # a table of --screen's query pairs: its checks below
+        if cfg["screen_votes"] > cfg["samples"]:            # -n may come after --screen-votes
+            print("\n\nERROR: --screen-votes should be an integer number in [1, restarts (-n)]")
+            raise cli.ArgError()
+        if quorum_depth(cfg["screen_votes"], cfg["samples"]) > MAX_SCREEN_STAT_DEPTH:
+            print("\n\nERROR: --screen-votes %d of %d restarts: only the %d lowest and the %d highest values are "
+                  "supported" % (cfg["screen_votes"], cfg["samples"], MAX_SCREEN_STAT_DEPTH, MAX_SCREEN_STAT_DEPTH))
+            raise cli.ArgError()
+        if cfg["screen_quorum"] and cfg["best"]:
+            print("\n\nERROR: --screen-quorum ranks by a score across the restarts: it does not go with --best")
+            raise cli.ArgError()
+    if any(key in cfg for key in ("screen_disputed", "screen_trim")):
+        cfg.setdefault("screen_disputed", None)
+        cfg.setdefault("screen_trim", 0)        # the range, max - min
+        cfg.setdefault("screen", None)
+        if cfg["samples"] < 2:                  # -n may come after --screen-trim
+            print("\n\nERROR: --screen-disputed ranks by the spread across the restarts: it needs -n 2 or more")
+            raise cli.ArgError()
+        if cfg["screen_trim"] not in spread_trims(cfg["samples"], None):
+            print("\n\nERROR: --screen-trim %d of %d restarts: the trim must leave two scores "
+                  "(restarts - 2 T >= 2)" % (cfg["screen_trim"], cfg["samples"]))
+            raise cli.ArgError()
+        if cfg["screen_trim"] > MAX_SCREEN_STAT_DEPTH - 1:
+            print("\n\nERROR: --screen-trim %d: only trims up to %d are supported"
+                  % (cfg["screen_trim"], MAX_SCREEN_STAT_DEPTH - 1))
+            raise cli.ArgError()
+        if cfg["screen_disputed"] and cfg["best"]:
+            print("\n\nERROR: --screen-disputed ranks by the spread across the restarts: it does not go with --best")
+            raise cli.ArgError()
     if any(key in cfg for key in ("allow_genes", "block_pairs")):
         cfg.setdefault("allow_genes", None)
         cfg.setdefault("block_pairs", None)
@@ -891,7 +964,7 @@ def parse(argv):
         cfg.setdefault("screen_top", DEFAULT_SCREEN_TOP)
         cfg.setdefault("query_pairs", None)
         cfg.setdefault("screen_best", None)
-        if cfg["screen"] and cfg["query_pairs"] is None and cfg["screen_best"] is None:
+        if _screen_tables(cfg) and cfg["query_pairs"] is None and cfg["screen_best"] is None:
             print("\n\nERROR: --screen needs its query pairs: --query-pairs FILE or --screen-best Q")
             raise cli.ArgError()
         if cfg["query_pairs"] is not None and cfg["screen_best"] is not None:
@@ -907,6 +980,11 @@ def parse(argv):
         print("\n\nERROR: --heldout-ranks needs a test file (-e)")
         raise cli.ArgError()
     return cfg
+
+
+def _screen_tables(cfg) -> bool:
+    """Whether cfg asks for a table over query pairs: --screen, --screen-quorum or --screen-disputed."""
+    return bool(cfg.get("screen") or cfg.get("screen_quorum") or cfg.get("screen_disputed"))
 
 
 def partner_queries(model, cfg):
@@ -946,11 +1024,12 @@ def driver_mask(model, cfg):
 
 
 def screen_queries(model, cfg):
-    """The driver's query pairs from --query-pairs, as int32[Q][2] gene ids (None: no --screen, or
-    --screen-best, whose pairs come from the fit); cli.ArgError on a file that does not read, a line
-    without two genes, a gene the fold does not hold, a pair of one gene or too many pairs."""
+    """The driver's query pairs from --query-pairs, as int32[Q][2] gene ids (None: no --screen,
+    --screen-quorum or --screen-disputed, or --screen-best, whose pairs come from the fit);
+    cli.ArgError on a file that does not read, a line without two genes, a gene the fold does not
+    hold, a pair of one gene or too many pairs."""
     from . import cli
-    if not cfg.get("screen") or cfg.get("query_pairs") is None:
+    if not _screen_tables(cfg) or cfg.get("query_pairs") is None:
         return None
     try:
         tokens = read_block_pairs(cfg["query_pairs"])
@@ -969,14 +1048,42 @@ def screen_queries(model, cfg):
 def screen_table(eng, model, cfg, known, sample, extras, queries, mask=None):
     """The driver's --screen table into `extras` (see run); queries: screen_queries' pairs, or None
     for --screen-best: the pairs pairs_top ranks first at --pair-threshold under the same exclude
-    and mask."""
-    if not cfg.get("screen"):
+    and mask.  --screen-quorum and --screen-disputed put their tables over the same pairs."""
+    if not _screen_tables(cfg):
         return
     if queries is None:
         queries = eng.pairs_top(cfg["screen_best"], cfg["pair_threshold"], known, sample, **_masked(mask))[2]
-    lists = eng.screen_top(queries, cfg["screen_top"], screen_known(model, queries, cfg["exclude"]), sample,
-                           mask=mask)
-    extras["screen"] = screen_rows(model.id_gene, queries, lists)
+    thirds = screen_known(model, queries, cfg["exclude"])
+    if cfg.get("screen"):
+        lists = eng.screen_top(queries, cfg["screen_top"], thirds, sample, mask=mask)
+        extras["screen"] = screen_rows(model.id_gene, queries, lists)
+    if cfg.get("screen_quorum"):
+        lists = eng.screen_quorum_top(queries, cfg["screen_top"], cfg["screen_votes"], thirds, mask=mask)
+        rows = screen_stat_rows(eng, model.id_gene, queries, lists)
+        extras["screen_quorum"] = (eng.active, cfg["screen_votes"], rows)
+    if cfg.get("screen_disputed"):
+        lists = eng.screen_spread_top(queries, cfg["screen_top"], cfg["screen_trim"], thirds, mask=mask)
+        rows = screen_stat_rows(eng, model.id_gene, queries, lists)
+        extras["screen_disputed"] = (eng.active, cfg["screen_trim"], rows)
+
+
+def screen_stat_rows(eng, id_gene, pairs, lists):
+    """screen_quorum_top's or screen_spread_top's lists for the query `pairs` -> the driver's rows
+    [query, rank, value, mean, min, max, "i_j_k", names], in query order and then by rank: per query
+    quorum_rows' rows behind screen_rows' query name.  mean, min and max come from one predict call
+    on every listed triple."""
+    sizes = [len(scores) for scores, _ in lists]
+    if not sum(sizes):
+        return []
+    listed = np.concatenate([ids for _, ids in lists if len(ids)])
+    probs = np.asarray(eng.predict(listed)[:eng.active], dtype=np.float64)
+    rows, at = [], 0
+    for (g1, g2), (scores, ids), n in zip(pairs, lists, sizes):
+        a, b = sorted((int(g1), int(g2)), key=str)
+        query = "%s_%s" % (id_gene[a], id_gene[b])
+        rows += [[query] + r for r in quorum_rows(id_gene, scores, ids, probs[:, at:at + n])]
+        at += n
+    return rows
 
 
 def _masked(mask):
@@ -1113,7 +1220,10 @@ def run(cfg, out=print, extras=None):
     threshold, hist, rows [rank, votes, probability, ids, names]) for --consensus, and "quorum" =
     (restarts, votes, rows [rank, quorum score, mean, min, max, ids, names]) for --quorum, and
     "screen" = rows [query, rank, probability, ids, names] for --screen, and "disputed" = (restarts,
-    trim, rows [rank, spread, mean, min, max, ids, names]) for --disputed."""
+    trim, rows [rank, spread, mean, min, max, ids, names]) for --disputed, and "screen_quorum" =
+    (restarts, votes, rows [query, rank, quorum score, mean, min, max, ids, names]) and
+    "screen_disputed" = (restarts, trim, rows of the same form) for --screen-quorum and
+    --screen-disputed."""
     from .model import Model
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
@@ -1205,6 +1315,16 @@ def write_disputed_tsv(samples, trim, rows, stream):
         stream.write("%d\t%r\t%r\t%r\t%r\t%s\t%s\n" % (rank, d, mean, lo, hi, key, "_".join(names)))
 
 
+def write_screen_stat_tsv(samples, arg, rows, stream, what):
+    """The --screen-quorum (what = "quorum", arg = the votes) or --screen-disputed (what = "spread",
+    arg = the trim) table."""
+    stream.write("# samples\t%d\n" % samples)
+    stream.write("# screen %s\t%d\n" % ("votes" if what == "quorum" else "trim", arg))
+    stream.write("query\trank\t%s\tmean\tmin\tmax\tids\tnames\n" % what)
+    for query, rank, v, mean, lo, hi, key, names in rows:
+        stream.write("%s\t%d\t%r\t%r\t%r\t%r\t%s\t%s\n" % (query, rank, v, mean, lo, hi, key, "_".join(names)))
+
+
 def write_pairs_tsv(rows, stream):
     stream.write("rank\tcount\teligible\tids\tnames\n")
     for i, (count, eligible, key, names) in enumerate(rows):
@@ -1263,6 +1383,12 @@ def main(argv=None, out=print):
     if "disputed" in extras:
         with open(cfg["disputed"], "w", encoding="utf-8") as f:
             write_disputed_tsv(*extras["disputed"], f)
+    if "screen_quorum" in extras:
+        with open(cfg["screen_quorum"], "w", encoding="utf-8") as f:
+            write_screen_stat_tsv(*extras["screen_quorum"], f, "quorum")
+    if "screen_disputed" in extras:
+        with open(cfg["screen_disputed"], "w", encoding="utf-8") as f:
+            write_screen_stat_tsv(*extras["screen_disputed"], f, "spread")
     partners = bool(cfg["genes"] or cfg["all_genes"])
     if cfg["out"]:
         with open(cfg["out"], "w", encoding="utf-8") as f:
