@@ -677,6 +677,62 @@ int mmsbm_screen_stat_scores(mmsbm_ctx *ctx, const int32_t *order, const int32_t
                              int32_t stat, int32_t arg, void *ws, int64_t ws_bytes, double *out,
                              void *stream);
 
+/* Partner statistics: the exact top N of a query gene's pairs by an order statistic of the restarts'
+ * own scores instead of one slot or the mean: what mmsbm_scan_quorum_topn and mmsbm_scan_spread_topn
+ * are genome-wide and mmsbm_screen_stat_topn is per query pair, per query gene.  Everything not said
+ * here (queries_host, the candidates b < c of the query at q, the packed key of the sorted triple,
+ * known_off / known_pairs, Q <= 65535, N <= mmsbm_partners_max_n(), the outputs with their NaN / -1
+ * tail and out_count, MMSBM_PARTNERS_SELECT, the stream) is mmsbm_partners_topn's, and with a mask
+ * mmsbm_partners_topn_masked's.  One entry serves both: mask = NULL means no mask, and P <= 16384
+ * holds only when a mask is given.
+ * Slots: the ns = n_active slots of the active prefix; there is no sample argument.  Slot s's OWN
+ * SCORE of a candidate is the word mmsbm_partners_topn(sample = s) lists for it, bit for bit: the
+ * same T tables (partners_prep_kernel), the same U / L rows, the same MFMA chain from zero over
+ * ascending k, each lane keeping the chain of its own column (c < q: L, otherwise U) per slot, before
+ * anything is inserted.
+ *   stat = MMSBM_PARTNERS_STAT_QUORUM, arg = m in [1, ns]: the value is q_m, the m-th largest of the
+ *     slots' own scores (m = 1: the maximum, m = ns: the minimum).  No floating-point value is
+ *     combined across slots: the value is one slot's word, and with ns = 1, m = 1 the list is
+ *     mmsbm_partners_topn(sample = 0)'s bit for bit.  At least m slots score the candidate at or above
+ *     T exactly when q_m >= T.
+ *   stat = MMSBM_PARTNERS_STAT_SPREAD, arg = the trim t >= 0 with ns - 2 t >= 2: the value is
+ *     d_t = q_{1+t} - q_{ns-t}, ONE IEEE subtraction of two slot scores, so d_t >= +0 (t = 0: the
+ *     range max - min).  Slots that agree bit for bit give +0 with the sign bit clear.
+ * The kernel keeps, per element, sorted lists in registers of depth D = min(m, ns - m + 1) for the
+ * quorum (the m-th largest is the (ns - m + 1)-th smallest: the shorter list is kept) and two of
+ * depth D = t + 1 for the spread; D <= mmsbm_partners_stat_max_depth() = 4.
+ * Exactness: no blocked or excluded candidate enters a candidate buffer, and every pruning bound (a
+ * workgroup's N-th best, the query's published word) is formed from eligible candidates' final
+ * statistic only, so it is a lower bound of the query's N-th best value.  A spread only grows as
+ * slots arrive, so the spread forms every slot.  The quorum stops a wave's tile early: once more than
+ * ns - m slots of EVERY element of the tile are strictly below the larger of the two bounds, no
+ * element can reach it and the tile's remaining slots are not formed (wave-uniform; equal scores
+ * stay in).  MMSBM_PARTNERS_STAT_EARLY=0 (read at the call) turns that off; the list depends on
+ * neither setting.
+ * Result (device): out_scores f64[Q][N], out_ids int32[Q][N][3], out_count int64[Q] as
+ * mmsbm_partners_topn: the query's best N values under the scan's total order (value descending;
+ * equal values by the smaller packed key of the sorted triple).  Q = 0 returns MMSBM_OK and writes
+ * nothing; P < 3: counts 0 and rows of NaN.  A query's list and its words depend on the query, the
+ * active slots and the eligibility only: not on Q, on the other queries, on the order of the slots,
+ * on the grid or on the early exit (every chain has a fixed order, max and min are exact, no value
+ * is formed by an atomic).
+ * Refusals, all before any device call and with the outputs and the context untouched: those of
+ * mmsbm_partners_topn (without the sample's), with a mask those of mmsbm_partners_topn_masked's mask
+ * (P above 16384, a misaligned mask), and MMSBM_ERR_INVALID: an unknown stat; m outside [1, ns];
+ * t < 0 or ns - 2 t < 2; the spread with ns < 2.  MMSBM_ERR_UNSUPPORTED: a legal argument whose depth
+ * D exceeds mmsbm_partners_stat_max_depth(); the ensemble rule of the partner scan,
+ * ns (4 ceil(K / 4) + 2) > 384.
+ * ws: mmsbm_partners_workspace_bytes(ctx, Q, N) bytes: the partner scan's workspace, no larger.
+ * Replaces nothing in the reference. */
+#define MMSBM_PARTNERS_STAT_QUORUM 0
+#define MMSBM_PARTNERS_STAT_SPREAD 1
+int mmsbm_partners_stat_max_depth(void);
+int mmsbm_partners_stat_topn(mmsbm_ctx *ctx, const int32_t *order, const int32_t *queries_host,
+                             int64_t Q, const int64_t *known_off, const int64_t *known_pairs,
+                             const uint32_t *mask, const double *theta, const double *pr, int32_t stat,
+                             int32_t arg, int32_t N, void *ws, int64_t ws_bytes, double *out_scores,
+                             int32_t *out_ids, int64_t *out_count, void *stream);
+
 /* Link-sharded iteration (single sample over N ranks): each rank's context
  * holds 1/N of the train links (mmsbm_set_links) and the GLOBAL degree (mmsbm_set_degree).
  * Step 1, the accumulation half of make_iteration (:986-1012) over this rank's links:

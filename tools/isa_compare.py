@@ -1,15 +1,17 @@
 """Compare the gfx950 device code of the three top-N scans between two trees, kernel by kernel.
 
-    python tools/isa_compare.py BEFORE_DIR AFTER_DIR
+    python tools/isa_compare.py BEFORE_DIR AFTER_DIR [NAME ...]
 
-Each directory holds, per source scan / scan_quorum / scan_spread, NAME.s and NAME.rpass: the device
+Each directory holds, per source scan / scan_quorum / scan_spread (or the NAMEs given, e.g.
+partners), NAME.s and NAME.rpass: the device
 assembly and the stderr of the build's own command line with
     --cuda-device-only -S -Rpass-analysis=kernel-resource-usage -o NAME.s csrc/NAME.hip
 A kernel's body runs from its label to its .Lfunc_end; comments and directives are dropped and the
 local labels renumbered in order of appearance before the instruction sequences are compared.  The
 resource row is everything the remark prints for the kernel (registers, spills, scratch, LDS,
 occupancy).  Kernels pair by mangled name; the merge kernels (one per file) pair with each other
-whatever their names.  Prints one line per kernel family and exits 1 on any difference.
+whatever their names.  Prints one line per kernel family and exits 1 on any difference; a kernel
+that only the second tree has is listed and counts as one.
 """
 import collections
 import os
@@ -64,13 +66,13 @@ def resources(path):
 def family(name):
     if "merge_kernel" in name:
         return "merge kernel"
-    m = re.search(r"\d+(scan_[a-z_]*kernel)", name)
+    m = re.search(r"\d+((?:scan|partners|screen)_[a-z_]*kernel)", name)
     return m.group(1) if m else name
 
 
-def main(before, after):
+def main(before, after, sources=SOURCES):
     bad = 0
-    for src in SOURCES:
+    for src in sources:
         kb, ka = (kernels(os.path.join(d, src + ".s")) for d in (before, after))
         rb, ra = (resources(os.path.join(d, src + ".rpass")) for d in (before, after))
         assert set(kb) == set(rb) and set(ka) == set(ra), "assembly and remarks name other kernels"
@@ -98,4 +100,4 @@ def main(before, after):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(sys.argv[1], sys.argv[2], tuple(sys.argv[3:]) or SOURCES))

@@ -22,6 +22,8 @@ MMSBM_ERR_ZERO_DEGREE = -3
 MMSBM_ERR_UNSUPPORTED = -4
 MMSBM_SCREEN_STAT_QUORUM = 0    # the stat argument of mmsbm_screen_stat_topn / mmsbm_screen_stat_scores
 MMSBM_SCREEN_STAT_SPREAD = 1
+MMSBM_PARTNERS_STAT_QUORUM = 0  # the stat argument of mmsbm_partners_stat_topn
+MMSBM_PARTNERS_STAT_SPREAD = 1
 SET_TRAIN = 0
 SET_TEST = 1
 FAMILY_AUTO = 0     # mmsbm_set_family: the small-K kernel family from B
@@ -112,6 +114,9 @@ SIGNATURES = {
                                         _c_i64, _vp, _vp, _vp, _vp]),
     "mmsbm_screen_stat_scores": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i32, _c_i32, _vp,
                                           _c_i64, _vp, _vp]),
+    "mmsbm_partners_stat_max_depth": (_c_int, []),
+    "mmsbm_partners_stat_topn": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i32, _c_i32, _c_i32, _vp,
+                                          _c_i64, _vp, _vp, _vp, _vp]),
     # include/mmsbm_pairs.h — the joint model's pair lattice
     "mmsbm_pairs_create": (_c_int, [_c_int, ctypes.POINTER(_vp)]),
     "mmsbm_pairs_destroy": (_c_int, [_vp]),

@@ -30,6 +30,9 @@
 //
 // partners_masked_kernel (mmsbm_partners_topn_masked) is partners_kernel's pair-masked twin: the
 // query's own bit row in LDS, row blocks and tiles dropped by it, the (b, c) bits per element.
+// partners_stat_kernel (mmsbm_partners_stat_topn): the ensemble path's tile with an order statistic
+// of the slots' own scores in the mean's place, the quorum score q_m or the spread q_{1+t} - q_{ns-t},
+// from per-element sorted lists in registers; the mask is a nullable pointer.
 
 #include <hip/hip_runtime.h>
 
@@ -549,6 +552,296 @@ __global__ __launch_bounds__(NT) void partners_masked_kernel(PartMaskedArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Stat scan (mmsbm_partners_stat_topn): the top N of a query by an order statistic of the slots' own
+// scores.  Restated beside its two siblings and not a shared body, so that their instantiations stay
+// what they were (DESIGN.md holds the figures).  The items, the U / L rows of every slot in LDS, the
+// tile walk, the keys, the eligibility, the buffer and the two bounds are partners_kernel's; the
+// query's bit row, the item and tile skips and the (b, c) halfwords are partners_masked_kernel's,
+// behind a nullable mask pointer (workgroup-uniform).
+// Each slot's tile is formed as the ensemble path forms it (A from the slot's U / L rows, B from the
+// slot's thT, every needed chain from zero over ascending k, the lane keeping the chain of its own
+// column), so it is the word mmsbm_partners_topn(sample = s) lists; instead of joining a sum it is
+// inserted into per-element sorted lists of depth D held in registers, `top` (the D largest,
+// descending) and `bot` (the D smallest, ascending), by the max / min chain of scan_score.h with
+// compile-time indices.  The wave-uniform `mode` says which list is kept and read: STAT_TOP the D-th
+// largest, STAT_BOT the D-th smallest, STAT_SPREAD both and their difference, one IEEE subtraction.
+// The host guarantees D <= ns (quorum) or 2 D <= ns (spread), so no start value reaches a buffer.
+// Early exit (the quorum, tile_quorum's rule): from slot `first` = ns - m on and before the last
+// slot, one ballot asks whether any element of the wave's tile can still reach cut = max(thr_s,
+// gthr); with STAT_BOT the list's last entry, the (ns - m + 1)-th smallest so far, is below cut
+// exactly when it cannot, with STAT_TOP the entries at or above cut plus the slots still to come
+// fall short of m exactly then.  If none can, the tile's remaining slots are not formed.  An element
+// below cut is dropped by the selection anyway, so the list does not change.  first = ns: never (the
+// spread, whose value only grows as slots arrive, and MMSBM_PARTNERS_STAT_EARLY=0).
+// Only the final statistic of an eligible candidate enters the buffer, so the workgroup's N-th best
+// and the query's published word are lower bounds of the query's N-th best value.
+// ------------------------------------------------------------------------------------------
+enum : int { STAT_TOP = 0, STAT_BOT = 1, STAT_SPREAD = 2 };
+
+struct PartStatArgs : PartMaskedArgs {  // mask = null: none (MW = 0)
+  int mode;   // STAT_*
+  int first;  // the first slot after which a tile may end early (ns: never)
+};
+
+template <int KS, int D>
+__global__ __launch_bounds__(NT) void partners_stat_kernel(PartStatArgs A) {
+  constexpr int KP = 4 * KS, WS = KP + 2;  // W row stride: conflict-free A-operand reads
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  Sel* st = reinterpret_cast<Sel*>(smem);
+  double* W = reinterpret_cast<double*>(smem + sizeof(Sel));  // [2][ns][RB][WS]: U, L
+  const int RB = 16 * A.WB;
+  const int P = A.P, P16 = A.P16, K = A.K, ns = A.ns, mode = A.mode, first = A.first;
+  const bool masked = A.mask != nullptr;  // workgroup-uniform
+  double* cs = W + (size_t)2 * ns * RB * WS;
+  unsigned* qrow = reinterpret_cast<unsigned*>(cs);  // the query's bit row, before the candidate buffer
+  const int MW2 = (A.MW + 1) & ~1;                   // 0 without a mask
+  cs += MW2 >> 1;                                    // the candidate buffer
+  long long* ck = reinterpret_cast<long long*>(cs + A.cap);
+  const int qi = blockIdx.x / A.gpq, j = blockIdx.x % A.gpq;
+  const int q = A.qpos[qi];
+  const bool q_ok = q >= 0 && q < P;
+  unsigned long long* shared = A.shared + qi;
+  if (threadIdx.x == 0) {
+    sel_init(st);
+    if (A.known_off) {
+      st->klo = A.known_off[qi];
+      st->khi = A.known_off[qi + 1];
+    }
+  }
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = lane & 15, kk = lane >> 4;
+  const int wb = wave % A.WB, wc = wave / A.WB, CW = 4 / A.WB;
+  const int nct = P16 / 16;
+  const int nbq = (P + RB - 1) / RB;
+  const int CT = (nct + A.ncc - 1) / A.ncc;  // c-tiles per chunk
+  const long long PP = (long long)P;
+  const double inf = __builtin_huge_val();
+  const size_t Tq = (size_t)qi * 3 * K * KP, Ts = (size_t)A.Q * 3 * K * KP;
+
+  // the query's bit row: position x of this wave's 64, words x / 32 and x / 32 + 1 from one ballot
+  for (int x = threadIdx.x; x < 32 * MW2; x += NT) {
+    bool on = true;  // q itself, positions from P on, a query without a position
+    if (q_ok && x < P && x != q) {
+      const unsigned w = x > q ? A.mask[(size_t)q * A.MW + (x >> 5)] : A.mask[(size_t)x * A.MW + (q >> 5)];
+      on = (w >> ((x > q ? x : q) & 31)) & 1u;
+    }
+    const unsigned long long bal = __ballot(on);
+    if (lane == 0) {
+      qrow[x >> 5] = (unsigned)bal;
+      qrow[(x >> 5) + 1] = (unsigned)(bal >> 32);
+    }
+  }
+  __syncthreads();
+  const unsigned short* qrow16 = reinterpret_cast<const unsigned short*>(qrow);
+
+  // the query's items round-robin over its workgroups
+  for (int it = q_ok ? j : INT_MAX; it < nbq * A.ncc; it += A.gpq) {
+    const int bq = it / A.ncc, cc = it % A.ncc;
+    const int ct_lo = cc * CT, ct_hi = min(nct, ct_lo + CT);
+    const int r0 = bq * RB;
+    if (ct_lo >= ct_hi || r0 >= P - 1 || ct_hi * 16 - 1 <= r0) continue;  // no b < c here
+    if (masked) {
+      // the {q, b} bits of the item's rows: RB = 16, 32 or 64 bits of qrow from bit r0 on
+      const int w0 = r0 >> 5;
+      unsigned long long bits = (unsigned long long)qrow[w0] >> (r0 & 31);  // w0 < MW: r0 < P - 1
+      if (RB == 64 && w0 + 1 < MW2) bits |= (unsigned long long)qrow[w0 + 1] << 32;
+      const int hi = min(P, r0 + RB) - r0;  // 0 < hi <= RB
+      const unsigned long long need = hi >= 64 ? ~0ull : (1ull << hi) - 1;
+      if ((bits & need) == need) continue;  // workgroup-uniform: every row of the block is blocked with q
+    }
+    __syncthreads();  // the previous item's W is read
+    if (threadIdx.x == 0) {
+      const unsigned long long g = __hip_atomic_load(shared, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      st->gthr = g ? __longlong_as_double((long long)g) : neg_inf();
+    }
+    // U = W1 of the rows above q and W2 of the rows below it, L = W3 of the rows below it (zero
+    // elsewhere), every slot
+    for (int idx = threadIdx.x; idx < 2 * ns * RB * KP; idx += NT) {
+      const int z = idx % KP, r = (idx / KP) % RB, s = (idx / (KP * RB)) % ns, ul = idx / (KP * RB * ns);
+      const int rowb = r0 + r;
+      const int mm = ul ? 2 : rowb > q ? 0 : 1;
+      double v = 0.0;
+      if (rowb < P && rowb != q && (ul == 0 || rowb < q)) {
+        const double* __restrict__ Tm = A.T + (size_t)s * Ts + Tq + (size_t)mm * K * KP + z;
+        const double* __restrict__ tb = A.thT + (size_t)s * KP * P16 + rowb;
+        for (int i = 0; i < K; ++i) v = fma(tb[(size_t)i * P16], Tm[i * KP], v);
+      }
+      W[((size_t)(ul * ns + s) * RB + r) * WS + z] = v;
+    }
+    __syncthreads();
+
+    const int btile = bq * A.WB + wb, b0 = btile * 16;
+    const bool wave_on = b0 < P - 1;
+    const bool rows_hi = b0 + 15 > q, rows_lo = b0 < q;  // the tile has rows above / below q
+    int ct = ct_lo + wc;
+    if (ct < btile) ct += (btile - ct + CW - 1) / CW * CW;  // every c of those tiles is below every b
+    const long long klo = st->klo, khi = st->khi;
+    unsigned qbm = 0;                // bit i: the pair {q, b0 + kk + 4 i} is blocked
+    unsigned bcn[4] = {0, 0, 0, 0};  // the next tile's (b, c) halfwords, in flight
+    // halfword ct of mask rows b0 + kk + 4 i: inside the mask for a wave that is on (rows <= b0 + 15 <
+    // P16, halfwords ct < P16 / 16 <= 2 MW)
+    const unsigned bc_off = (unsigned)(b0 + kk) * (unsigned)A.MW * 4u;
+    auto load_bc = [&](unsigned (&h)[4], int ct) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        h[i] = *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(A.mask) +
+                                                        (size_t)(16 * i) * A.MW + (bc_off + 2u * (unsigned)ct));
+    };
+    if (wave_on && masked) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + kk + 4 * i;
+        qbm |= ((qrow[b >> 5] >> (b & 31)) & 1u) << i;
+      }
+    }
+    for (;;) {
+      // the thresholds change only when the workgroup sorts its buffer (behind a barrier)
+      const double thr_s = st->thr_s, gthr = st->gthr;
+      const long long thr_k = st->thr_k;
+      const double cut = fmax(thr_s, gthr);
+      if (wave_on) {
+        if (masked && ct < ct_hi) load_bc(bcn, ct);  // also for a tile that is redone
+        for (; ct < ct_hi; ct += CW) {
+          const int c0 = ct * 16, c = c0 + m;
+          // U: some c > q (rows below q) or rows above q (all their c are); L: rows and c below q
+          const bool need[2] = {rows_hi || c0 + 15 > q, rows_lo && c0 < q};
+          unsigned blk = 0;  // bit i: element i of the tile is blocked
+          if (masked) {
+            const unsigned qc = qrow16[ct];
+            blk = qbm | (((qc >> m) & 1u) ? 0xFu : 0u);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) blk |= ((bcn[i] >> m) & 1u) << i;
+            if (ct + CW < ct_hi) load_bc(bcn, ct + CW);
+            if (qc == 0xFFFFu) continue;  // every pair {q, c} of the tile is blocked (wave-uniform)
+          }
+          d4v top[D], bot[D];
+#pragma unroll
+          for (int jj = 0; jj < D; ++jj) {
+            top[jj] = d4v{-inf, -inf, -inf, -inf};
+            bot[jj] = d4v{inf, inf, inf, inf};
+          }
+          bool live = true;
+          for (int s = 0; s < ns; ++s) {
+            const double* __restrict__ tc = A.thT + ((size_t)s * KP + kk) * P16 + c;
+            double bv[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) bv[ks] = tc[(size_t)(4 * ks) * P16];
+            d4v sc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int ul = 0; ul < 2; ++ul) {
+              if (!need[ul]) continue;  // wave-uniform
+              const double* wr = W + ((size_t)(ul * ns + s) * RB + wb * 16 + m) * WS + kk;
+              d4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+              for (int ks = 0; ks < KS; ++ks)
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[4 * ks], bv[ks], acc, 0, 0, 0);
+              // lane holds S[b0 + kk + 4 i][c0 + m]: keep the chain of its own column
+              if ((c < q) == (ul == 1)) sc = acc;
+            }
+            // each list keeps the better of the two, x carries the other on
+            if (mode != STAT_BOT) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                double x = sc[i];
+#pragma unroll
+                for (int jj = 0; jj < D; ++jj) {
+                  const double hi = fmax(top[jj][i], x), lo = fmin(top[jj][i], x);
+                  top[jj][i] = hi;
+                  x = lo;
+                }
+              }
+            }
+            if (mode != STAT_TOP) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                double x = sc[i];
+#pragma unroll
+                for (int jj = 0; jj < D; ++jj) {
+                  const double lo = fmin(bot[jj][i], x), hi = fmax(bot[jj][i], x);
+                  bot[jj][i] = lo;
+                  x = hi;
+                }
+              }
+            }
+            if (s >= first && s + 1 < ns) {  // wave-uniform; the quorum only
+              bool alive = false;
+              if (mode == STAT_BOT) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) alive |= !(bot[D - 1][i] < cut);  // +inf until D slots are in
+              } else {
+                const int short_of = D - (ns - 1 - s);  // >= 1 from slot ns - D on
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                  int n = 0;
+#pragma unroll
+                  for (int jj = 0; jj < D; ++jj) n += top[jj][i] >= cut;
+                  alive |= n >= short_of;
+                }
+              }
+              if (!__ballot(alive)) {
+                live = false;
+                break;
+              }
+            }
+          }
+          if (!live) continue;  // no element of the tile reaches cut
+          const d4v res = mode == STAT_TOP ? top[D - 1] : mode == STAT_BOT ? bot[D - 1] : top[D - 1] - bot[D - 1];
+          if (!A.select) {
+            asm volatile("" ::"v"(res[0]), "v"(res[1]), "v"(res[2]), "v"(res[3]));  // keep the score phase live
+            continue;
+          }
+          // first the value alone against the larger of the two bounds (equal values stay in: the
+          // key decides below); nearly every tile ends here once the buffer holds N
+          if (!__ballot(res[0] >= cut || res[1] >= cut || res[2] >= cut || res[3] >= cut)) continue;
+          bool pass[4];
+          long long key[4];
+          unsigned long long mk[4];
+          int n = 0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int b = b0 + kk + 4 * i;
+            // the triple's packed key, q in its sorted place
+            key[i] = b > q ? ((long long)q * PP + b) * PP + c
+                   : c > q ? ((long long)b * PP + q) * PP + c
+                           : ((long long)b * PP + c) * PP + q;
+            pass[i] = b < c && c < P && b != q && c != q && !(res[i] < gthr) &&
+                      before(res[i], key[i], thr_s, thr_k);
+            pass[i] = pass[i] && !((blk >> i) & 1u);
+            if (pass[i] && khi > klo) pass[i] = !is_known(A.known, klo, khi, (long long)b * PP + c);
+            mk[i] = __ballot(pass[i]);
+            n += __popcll(mk[i]);
+          }
+          if (!n) continue;
+          int pos = wave_reserve(st, n, A.cap);
+          if (pos < 0) break;  // the tile is redone after the workgroup made room
+          const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (pass[i]) {
+              const int at = pos + __popcll(mk[i] & below);
+              cs[at] = res[i];
+              ck[at] = key[i];
+            }
+            pos += __popcll(mk[i]);
+          }
+        }
+      }
+      __syncthreads();
+      if (!st->overflow) break;
+      wg_keep_best(st, cs, ck, A.N, shared);
+    }
+  }
+  wg_keep_best(st, cs, ck, A.N, shared);
+  const int cnt = st->count;
+  for (int i = threadIdx.x; i < cnt; i += NT) {
+    A.list_s[(size_t)blockIdx.x * A.N + i] = cs[i];
+    A.list_k[(size_t)blockIdx.x * A.N + i] = ck[i];
+  }
+  if (threadIdx.x == 0) A.list_n[blockIdx.x] = cnt;
+}
+
+// ------------------------------------------------------------------------------------------
 // Merge, grid (lists out per query, Q): workgroup (w, i) keeps the best N of query i's lists
 // [FAN w, FAN (w + 1)); the last level (one workgroup per query) writes the query's row: scores,
 // gene ids in key order, count, NaN / -1 tail.
@@ -654,11 +947,62 @@ int make_plan(const mmsbm_ctx* c, long long Q, int N, PartPlan* p) {
   return MMSBM_OK;
 }
 
-// Both entry points; `masked`: mmsbm_partners_topn_masked, whose mask must not be null.
+constexpr int STAT_MAX_DEPTH = 4;  // the deepest sorted lists partners_stat_kernel is built for
+
+// f(std::integral_constant<int, D>{}) for D in [1, STAT_MAX_DEPTH]
+template <class F>
+int dispatch_depth(int d, F&& f) {
+  switch (d) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
+
+// The (stat, arg) of the stat entry over ns scored slots -> the kernel's list depth and mode, after
+// the checks of include/mmsbm.h.
+int stat_plan(int stat, int arg, int ns, int* depth, int* mode) {
+  if (stat == MMSBM_PARTNERS_STAT_QUORUM) {
+    if (arg < 1 || arg > ns)
+      return fail(MMSBM_ERR_INVALID, "the partner scan: votes m=%d outside [1, %d], the scored slots", arg, ns);
+    const int from_top = arg, from_bot = ns - arg + 1;  // the m-th largest is the (ns - m + 1)-th smallest
+    *depth = std::min(from_top, from_bot);
+    *mode = from_top <= from_bot ? STAT_TOP : STAT_BOT;
+    if (*depth > STAT_MAX_DEPTH)
+      return fail(MMSBM_ERR_UNSUPPORTED,
+                  "the partner scan: m=%d of %d slots needs a sorted list of depth %d, above the cap of %d "
+                  "(mmsbm_partners_stat_max_depth)",
+                  arg, ns, *depth, STAT_MAX_DEPTH);
+    return MMSBM_OK;
+  }
+  if (stat == MMSBM_PARTNERS_STAT_SPREAD) {
+    if (ns < 2)
+      return fail(MMSBM_ERR_INVALID, "the partner scan: %d active slot: one restart has no spread", ns);
+    if (arg < 0 || ns - 2 * (long long)arg < 2)
+      return fail(MMSBM_ERR_INVALID,
+                  "the partner scan: trim=%d outside [0, %d]: %d scored slots must keep two scores", arg,
+                  (ns - 2) / 2, ns);
+    *depth = arg + 1;
+    *mode = STAT_SPREAD;
+    if (*depth > STAT_MAX_DEPTH)
+      return fail(MMSBM_ERR_UNSUPPORTED,
+                  "the partner scan: trim=%d of %d slots needs two sorted lists of depth %d, above the cap of %d "
+                  "(mmsbm_partners_stat_max_depth)",
+                  arg, ns, *depth, STAT_MAX_DEPTH);
+    return MMSBM_OK;
+  }
+  return fail(MMSBM_ERR_INVALID, "the partner scan: unknown statistic %d", stat);
+}
+
+// Every entry point; `masked`: the call reads a pair mask (mmsbm_partners_topn_masked, whose mask must
+// not be null, or mmsbm_partners_stat_topn with one).  stat = null: the list of `sample`; otherwise the
+// list of the statistic (stat[0], stat[1]) = (stat, arg) over the active slots (partners_stat_kernel),
+// with sample = -1.
 int partners_call(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_host, int64_t Q,
                   const int64_t* known_off, const int64_t* known_pairs, const uint32_t* mask, bool masked,
-                  const double* theta, const double* pr, int32_t sample, int32_t N, void* ws, int64_t ws_bytes,
-                  double* out_scores, int32_t* out_ids, int64_t* out_count, void* stream) {
+                  const double* theta, const double* pr, int32_t sample, const int32_t* stat, int32_t N, void* ws,
+                  int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count, void* stream) {
   if (!c) return fail(MMSBM_ERR_INVALID, "null context");
   PartPlan p;
   int rc = make_plan(c, Q, N, &p);
@@ -666,6 +1010,8 @@ int partners_call(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_hos
   const ScanShape& sh = p.sh;
   int MW = 0;
   if (masked && (rc = check_pair_mask(sh, "the partner scan", mask, &MW))) return rc;
+  int depth = 0, mode = 0;
+  if (stat && (rc = stat_plan(stat[0], stat[1], sh.nact, &depth, &mode))) return rc;
   if (Q == 0) return MMSBM_OK;
   if (!order || !queries_host || !theta || !pr || !out_scores || !out_ids || !out_count)
     return fail(MMSBM_ERR_INVALID, "null pointer");
@@ -687,6 +1033,8 @@ int partners_call(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_hos
   static_assert(sizeof(Sel) + W_LDS_MAX + PAIR_MASK_MAX_P / 8 + 2 * PARTNERS_MAX_N * 16 <= LDS_MAX,
                 "the query's bit row and the buffer stay in LDS");
   const bool select = env_override("MMSBM_PARTNERS_SELECT", 1) != 0;  // measurement: the bare score phase
+  // the quorum's early exit from slot ns - m on (ns: never); measurement: MMSBM_PARTNERS_STAT_EARLY=0
+  const bool early = stat && stat[0] == MMSBM_PARTNERS_STAT_QUORUM && env_override("MMSBM_PARTNERS_STAT_EARLY", 1) != 0;
 
   DeviceGuard g(sh.device);
   hipStream_t s = (hipStream_t)stream;
@@ -706,7 +1054,8 @@ int partners_call(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_hos
                                                      (double*)(w + p.off_T), (int*)(w + p.off_qpos), sh.K,
                                                      sh.KP, sh.R, sh.P, nq, s0);
     HIP_TRY(hipGetLastError());
-    PartMaskedArgs am{};
+    PartStatArgs as{};
+    PartMaskedArgs& am = as;
     PartArgs& a = am;
     am.mask = mask, am.MW = MW;
     a.thT = (const double*)(w + p.off_thT);
@@ -723,8 +1072,13 @@ int partners_call(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_hos
     a.ncc = std::max(1, std::min(nct, (p.gpq + nbq - 1) / nbq));  // enough items for the query's workgroups
     n_lists = p.gpq;
     const int G = nq * p.gpq;
+    as.mode = mode, as.first = early ? ns - stat[1] : ns;
     rc = dispatch_ks(sh.KP / 4, [&](auto ks) {
       constexpr int KS = decltype(ks)::value;
+      if (stat)
+        return dispatch_depth(depth, [&](auto d) {
+          return launch_lds(partners_stat_kernel<KS, decltype(d)::value>, G, lds, s, as);
+        });
       if (masked) return launch_lds(partners_masked_kernel<KS>, G, lds, s, am);
       return launch_lds(partners_kernel<KS>, G, lds, s, a);
     });
@@ -766,8 +1120,8 @@ int mmsbm_partners_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queri
                         const int64_t* known_off, const int64_t* known_pairs, const double* theta,
                         const double* pr, int32_t sample, int32_t N, void* ws, int64_t ws_bytes,
                         double* out_scores, int32_t* out_ids, int64_t* out_count, void* stream) {
-  return partners_call(c, order, queries_host, Q, known_off, known_pairs, nullptr, false, theta, pr, sample, N, ws,
-                       ws_bytes, out_scores, out_ids, out_count, stream);
+  return partners_call(c, order, queries_host, Q, known_off, known_pairs, nullptr, false, theta, pr, sample, nullptr,
+                       N, ws, ws_bytes, out_scores, out_ids, out_count, stream);
 }
 
 int mmsbm_partners_topn_masked(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_host, int64_t Q,
@@ -775,8 +1129,20 @@ int mmsbm_partners_topn_masked(mmsbm_ctx* c, const int32_t* order, const int32_t
                                const double* theta, const double* pr, int32_t sample, int32_t N, void* ws,
                                int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count,
                                void* stream) {
-  return partners_call(c, order, queries_host, Q, known_off, known_pairs, mask, true, theta, pr, sample, N, ws,
-                       ws_bytes, out_scores, out_ids, out_count, stream);
+  return partners_call(c, order, queries_host, Q, known_off, known_pairs, mask, true, theta, pr, sample, nullptr, N,
+                       ws, ws_bytes, out_scores, out_ids, out_count, stream);
+}
+
+int mmsbm_partners_stat_max_depth(void) { return STAT_MAX_DEPTH; }
+
+int mmsbm_partners_stat_topn(mmsbm_ctx* c, const int32_t* order, const int32_t* queries_host, int64_t Q,
+                             const int64_t* known_off, const int64_t* known_pairs, const uint32_t* mask,
+                             const double* theta, const double* pr, int32_t stat, int32_t arg, int32_t N, void* ws,
+                             int64_t ws_bytes, double* out_scores, int32_t* out_ids, int64_t* out_count,
+                             void* stream) {
+  const int32_t stat_arg[2] = {stat, arg};
+  return partners_call(c, order, queries_host, Q, known_off, known_pairs, mask, mask != nullptr, theta, pr, -1,
+                       stat_arg, N, ws, ws_bytes, out_scores, out_ids, out_count, stream);
 }
 
 }  // extern "C"

@@ -226,7 +226,8 @@ class EMEngine:
     def scan_workspace(self, family: str, *size_args) -> torch.Tensor:
         """The scratch of one family ("scan", "partners", "census", "pair_census", "scan_above",
         "scan_votes", "scan_quorum", "scan_spread", "screen"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device.
-        The screen scan's statistics (screen_quorum_*, screen_spread_*) run in the "screen" scratch."""
+        The screen scan's statistics (screen_quorum_*, screen_spread_*) run in the "screen" scratch,
+        the partner scan's (partners_quorum_*, partners_spread_*) in the "partners" scratch."""
         nbytes = ctypes.c_int64()
         _lib.check(getattr(self.lib, "mmsbm_%s_workspace_bytes" % family)(self.ctx, *size_args,
                                                                           ctypes.byref(nbytes)))
@@ -340,6 +341,69 @@ class EMEngine:
             stream.synchronize()
         counts, scores, ids = counts.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
         return [(scores[i, :int(m)].copy(), ids[i, :int(m)].copy()) for i, m in enumerate(counts)]
+
+    # ----------------------------------------------------- partner statistics
+    @property
+    def partners_stat_max_depth(self) -> int:
+        """mmsbm_partners_stat_max_depth(): the deepest per-element sorted lists the partner scan's
+        statistics kernel holds (quorum_max_depth, and spread_max_trim + 1)."""
+        return int(self.lib.mmsbm_partners_stat_max_depth())
+
+    def _partners_stat_top_async(self, queries, n, stat, arg, known, stream, mask):
+        """mmsbm_partners_stat_topn -> device tensors as partners_top_async returns them."""
+        n = int(n)
+        queries = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+        Q = int(queries.size)
+        off, pairs = (None, None) if known is None else check_partner_known(known, Q)
+        with self._scan_call(None, None, stream, mask) as ((ctx, order, _, _, *rest), s):   # no key table
+            # rest: the mask (if any), theta, pr and the sample, which the stat entry does not take
+            mask_p, (theta, pr, _) = (rest[0], rest[1:]) if mask is not None else (None, rest)
+            ws = self.scan_workspace("partners", Q, n)
+            off_d = pairs_d = None
+            if off is not None:
+                off_d = torch.from_numpy(off).to(self.device)
+                pairs_d = torch.from_numpy(pairs if pairs.size else np.zeros(1, np.int64)).to(self.device)
+            scores = torch.empty((Q, n), dtype=torch.float64, device=self.device)
+            ids = torch.empty((Q, n, 3), dtype=torch.int32, device=self.device)
+            counts = torch.empty(Q, dtype=torch.int64, device=self.device)
+            _lib.check(self.lib.mmsbm_partners_stat_topn(
+                ctx, order, _host_ptr(queries), Q, _ptr(off_d) if off_d is not None else None,
+                _ptr(pairs_d) if pairs_d is not None else None, mask_p, theta, pr, stat, arg, n, _ptr(ws),
+                ws.numel(), _ptr(scores), _ptr(ids), _ptr(counts), s.cuda_stream))
+        return scores, ids, counts
+
+    def partners_quorum_top_async(self, queries, n: int, min_votes: int = None, known=None, stream=None,
+                                  mask=None):
+        """partners_quorum_top without the host copy: -> device tensors as partners_top_async returns
+        them.  Nothing synchronises."""
+        m = self._screen_votes(min_votes)       # ValueError before anything is uploaded
+        return self._partners_stat_top_async(queries, n, _lib.MMSBM_PARTNERS_STAT_QUORUM, m, known, stream, mask)
+
+    def partners_quorum_top(self, queries, n: int, min_votes: int = None, known=None, stream=None, mask=None):
+        """For each query gene id, its n partner pairs with the highest quorum score (include/mmsbm.h
+        mmsbm_partners_stat_topn, MMSBM_PARTNERS_STAT_QUORUM): q_m = the m-th largest of the active
+        slots' own partners_top(sample=s) words, m = min_votes (None: every active slot, the minimum
+        over them; 1: the maximum).  At least m restarts score a pair at or above T exactly when its
+        q_m >= T.  -> lists as partners_top returns them, best first under its total order.
+        min_votes outside [1, active] raises ValueError; a depth min(m, active - m + 1) above
+        partners_stat_max_depth raises MMSBMError (MMSBM_ERR_UNSUPPORTED).  known, mask: as for
+        partners_top."""
+        return self._screen_lists(self.partners_quorum_top_async(queries, n, min_votes, known, stream, mask), stream)
+
+    def partners_spread_top_async(self, queries, n: int, trim: int = 0, known=None, stream=None, mask=None):
+        """partners_spread_top without the host copy: -> device tensors as partners_top_async returns
+        them.  Nothing synchronises."""
+        trim = self._spread_trim(trim)          # ValueError before anything is uploaded
+        return self._partners_stat_top_async(queries, n, _lib.MMSBM_PARTNERS_STAT_SPREAD, trim, known, stream, mask)
+
+    def partners_spread_top(self, queries, n: int, trim: int = 0, known=None, stream=None, mask=None):
+        """For each query gene id, the n partner pairs on which the active slots disagree most
+        (mmsbm_partners_stat_topn, MMSBM_PARTNERS_STAT_SPREAD): ranked by d_t = q_{1+t} - q_{ns-t},
+        t = trim, over the ns = active slots' own partners_top(sample=s) words (trim = 0: max - min).
+        -> lists as partners_top returns them.  Fewer than two active slots and a trim outside
+        spread_trims' rule raise ValueError; a legal trim above partners_stat_max_depth - 1 raises
+        MMSBMError (MMSBM_ERR_UNSUPPORTED).  known, mask: as for partners_top."""
+        return self._screen_lists(self.partners_spread_top_async(queries, n, trim, known, stream, mask), stream)
 
     # ----------------------------------------------------------- screen scan
     @contextlib.contextmanager

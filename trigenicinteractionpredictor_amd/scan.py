@@ -141,6 +141,22 @@ mean, min and max are the listed triple's ensemble mean and its lowest and highe
 the predict kernel.  --exclude, --allow-genes and --block-pairs apply as they do to --screen.  Not
 with --best (and --screen-disputed not with -n 1): one restart has no quorum and no spread.
 
+Two more come from the partner scan's statistics (`EMEngine.partners_quorum_top`,
+`partners_spread_top`, mmsbm_partners_stat_topn): --quorum and --disputed per query gene, over the
+query genes of --gene / --all-genes (which they need) and with the same --top rows per gene.
+    --partners-quorum FILE   per query gene, its --top partner pairs ranked by their quorum score, the
+                             M-th largest of the -n restarts' own P(r = 1), --partners-votes M (in
+                             [1, -n]; default -n; the depth rule of --quorum-votes).  The header
+                             comments give `# samples` and `# partners votes`; then the --gene table's
+                             rows with the quorum score in the probability's place: query, rank,
+                             quorum, ids, names.
+    --partners-disputed FILE per query gene, its --top partner pairs ranked by the spread of the -n
+                             restarts' own P(r = 1), --partners-trim T (default 0: max - min; the rule
+                             of --disputed-trim).  `# samples`, `# partners trim`; query, rank,
+                             spread, ids, names rows.
+--exclude applies as it does to the --gene table.  Not with --best (and --partners-disputed not with
+-n 1); with --allow-genes / --block-pairs they are refused as --gene is (`EMEngine` takes the mask).
+
 Exactness: the counts are exact for the scan's score bits.  A listed triple's probability comes from
 the predict kernel, which sums in another order, so a triple within rounding distance (about 1e-12
 relative) of another triple's score may be placed on either side of it.  (Listed triples are
@@ -169,6 +185,7 @@ DEFAULT_SCREEN_TOP = 20  # --screen without --screen-top: the rows per query pai
 MAX_SCREEN_QUERIES = 65535   # the most query pairs one mmsbm_screen_topn call takes
 MAX_QUORUM_DEPTH = 4     # mmsbm_scan_quorum_max_depth(): the deepest sorted list of the quorum scan
 MAX_SPREAD_TRIM = 3      # mmsbm_scan_spread_max_trim(): the largest trim of the dispute scan
+MAX_PARTNERS_STAT_DEPTH = 4  # mmsbm_partners_stat_max_depth(): the deepest sorted lists of the partner statistics
 MAX_SCREEN_STAT_DEPTH = 4    # mmsbm_screen_stat_max_depth(): the deepest sorted lists of the screen statistics
 DEFAULT_THRESHOLDS = (0.99, 0.95, 0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3, 0.2, 0.1, 0.05, 0.02, 0.01, 0.005,
                       0.002, 0.001)   # --census without --thresholds
@@ -704,6 +721,10 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [--screen-votes=] <M, an integer in [1, restarts]; default: all restarts (the minimum over them)>
     [--screen-disputed=] <TSV file: per query pair, its --screen-top third genes by the spread of the restarts' scores>
     [--screen-trim=] <T, an integer >= 0 with restarts - 2 T >= 2, at most 3; default 0 (max - min)>
+    [--partners-quorum=] <TSV file: per query gene (--gene / --all-genes), its --top partner pairs by their M-th best restart score>
+    [--partners-votes=] <M, an integer in [1, restarts]; default: all restarts (the minimum over them)>
+    [--partners-disputed=] <TSV file: per query gene, its --top partner pairs by the spread of the restarts' scores>
+    [--partners-trim=] <T, an integer >= 0 with restarts - 2 T >= 2, at most 3; default 0 (max - min)>
 """
 
 
@@ -722,7 +743,8 @@ def parse(argv):
     # its four (screen, screen_top, query_pairs, screen_best) in the same way, and --disputed its two
     # (disputed, disputed_trim); --screen-quorum and --screen-disputed add their two each
     # (screen_quorum, screen_votes; screen_disputed, screen_trim) and, being tables over --screen's
-    # query pairs, --screen's four
+    # query pairs, --screen's four; --partners-quorum and --partners-disputed add their two each
+    # (partners_quorum, partners_votes; partners_disputed, partners_trim)
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
@@ -735,7 +757,9 @@ def parse(argv):
                                                         "allow-genes=", "block-pairs=", "screen=",
                                                         "screen-top=", "query-pairs=", "screen-best=",
                                                         "disputed=", "disputed-trim=", "screen-quorum=",
-                                                        "screen-votes=", "screen-disputed=", "screen-trim="])
+                                                        "screen-votes=", "screen-disputed=", "screen-trim=",
+                                                        "partners-quorum=", "partners-votes=",
+                                                        "partners-disputed=", "partners-trim="])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -839,6 +863,20 @@ def parse(argv):
                     print("\n\nERROR: --screen-trim should be an integer number >= 0")
                     raise cli.ArgError()
                 cfg["screen_trim"] = int(arg)
+            elif opt == "--partners-quorum":
+                cfg["partners_quorum"] = arg
+            elif opt == "--partners-votes":
+                if not int(arg) >= 1:
+                    print("\n\nERROR: --partners-votes should be an integer number in [1, restarts (-n)]")
+                    raise cli.ArgError()
+                cfg["partners_votes"] = int(arg)
+            elif opt == "--partners-disputed":
+                cfg["partners_disputed"] = arg
+            elif opt == "--partners-trim":
+                if not int(arg) >= 0:
+                    print("\n\nERROR: --partners-trim should be an integer number >= 0")
+                    raise cli.ArgError()
+                cfg["partners_trim"] = int(arg)
             elif opt == "--allow-genes":
                 cfg["allow_genes"] = arg
             elif opt == "--block-pairs":
@@ -949,6 +987,42 @@ def parse(argv):
         if cfg["screen_disputed"] and cfg["best"]:
             print("\n\nERROR: --screen-disputed ranks by the spread across the restarts: it does not go with --best")
             raise cli.ArgError()
+    if any(key in cfg for key in ("partners_quorum", "partners_votes")):
+        cfg.setdefault("partners_quorum", None)
+        cfg.setdefault("partners_votes", cfg["samples"])    # every restart
+        if cfg["partners_votes"] > cfg["samples"]:          # -n may come after --partners-votes
+            print("\n\nERROR: --partners-votes should be an integer number in [1, restarts (-n)]")
+            raise cli.ArgError()
+        if quorum_depth(cfg["partners_votes"], cfg["samples"]) > MAX_PARTNERS_STAT_DEPTH:
+            print("\n\nERROR: --partners-votes %d of %d restarts: only the %d lowest and the %d highest values are "
+                  "supported" % (cfg["partners_votes"], cfg["samples"], MAX_PARTNERS_STAT_DEPTH,
+                                 MAX_PARTNERS_STAT_DEPTH))
+            raise cli.ArgError()
+        if cfg["partners_quorum"] and cfg["best"]:
+            print("\n\nERROR: --partners-quorum ranks by a score across the restarts: it does not go with --best")
+            raise cli.ArgError()
+    if any(key in cfg for key in ("partners_disputed", "partners_trim")):
+        cfg.setdefault("partners_disputed", None)
+        cfg.setdefault("partners_trim", 0)      # the range, max - min
+        if cfg["samples"] < 2:                  # -n may come after --partners-trim
+            print("\n\nERROR: --partners-disputed ranks by the spread across the restarts: it needs -n 2 or more")
+            raise cli.ArgError()
+        if cfg["partners_trim"] not in spread_trims(cfg["samples"], None):
+            print("\n\nERROR: --partners-trim %d of %d restarts: the trim must leave two scores "
+                  "(restarts - 2 T >= 2)" % (cfg["partners_trim"], cfg["samples"]))
+            raise cli.ArgError()
+        if cfg["partners_trim"] > MAX_PARTNERS_STAT_DEPTH - 1:
+            print("\n\nERROR: --partners-trim %d: only trims up to %d are supported"
+                  % (cfg["partners_trim"], MAX_PARTNERS_STAT_DEPTH - 1))
+            raise cli.ArgError()
+        if cfg["partners_disputed"] and cfg["best"]:
+            print("\n\nERROR: --partners-disputed ranks by the spread across the restarts: it does not go with "
+                  "--best")
+            raise cli.ArgError()
+    if _partner_stat_tables(cfg) and not (cfg["genes"] or cfg["all_genes"]):
+        print("\n\nERROR: --partners-quorum / --partners-disputed are tables per query gene: they need --gene or "
+              "--all-genes")
+        raise cli.ArgError()
     if any(key in cfg for key in ("allow_genes", "block_pairs")):
         cfg.setdefault("allow_genes", None)
         cfg.setdefault("block_pairs", None)
@@ -980,6 +1054,11 @@ def parse(argv):
         print("\n\nERROR: --heldout-ranks needs a test file (-e)")
         raise cli.ArgError()
     return cfg
+
+
+def _partner_stat_tables(cfg) -> bool:
+    """Whether cfg asks for a statistic's table over query genes: --partners-quorum or --partners-disputed."""
+    return bool(cfg.get("partners_quorum") or cfg.get("partners_disputed"))
 
 
 def _screen_tables(cfg) -> bool:
@@ -1084,6 +1163,27 @@ def screen_stat_rows(eng, id_gene, pairs, lists):
         rows += [[query] + r for r in quorum_rows(id_gene, scores, ids, probs[:, at:at + n])]
         at += n
     return rows
+
+
+def partner_stat_tables(eng, model, cfg, extras, queries):
+    """The driver's --partners-quorum and --partners-disputed tables into `extras` (see run), over
+    the query genes of --gene / --all-genes under the same --exclude as the partner table."""
+    if not _partner_stat_tables(cfg) or queries is None:
+        return
+    known = partner_known(model, queries, cfg["exclude"])
+    if cfg.get("partners_quorum"):
+        lists = eng.partners_quorum_top(queries, cfg["top"], cfg["partners_votes"], known)
+        extras["partners_quorum"] = (eng.active, cfg["partners_votes"], partner_rows(model.id_gene, queries, lists))
+    if cfg.get("partners_disputed"):
+        lists = eng.partners_spread_top(queries, cfg["top"], cfg["partners_trim"], known)
+        extras["partners_disputed"] = (eng.active, cfg["partners_trim"], partner_rows(model.id_gene, queries, lists))
+
+
+def partner_rows(id_gene, queries, lists):
+    """partners_top's (or a partner statistic's) lists for the query genes -> the driver's rows
+    [query, rank, value, "i_j_k", names], in query order and then by rank."""
+    return [[id_gene[g], i + 1, float(p), "_".join(str(x) for x in row), sorted(id_gene[int(x)] for x in row)]
+            for g, (scores, ids) in zip(queries, lists) for i, (p, row) in enumerate(zip(scores, ids))]
 
 
 def _masked(mask):
@@ -1223,7 +1323,9 @@ def run(cfg, out=print, extras=None):
     trim, rows [rank, spread, mean, min, max, ids, names]) for --disputed, and "screen_quorum" =
     (restarts, votes, rows [query, rank, quorum score, mean, min, max, ids, names]) and
     "screen_disputed" = (restarts, trim, rows of the same form) for --screen-quorum and
-    --screen-disputed."""
+    --screen-disputed, and "partners_quorum" = (restarts, votes, rows [query, rank, quorum score, ids,
+    names]) and "partners_disputed" = (restarts, trim, rows of the same form) for --partners-quorum and
+    --partners-disputed."""
     from .model import Model
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
@@ -1251,14 +1353,13 @@ def run(cfg, out=print, extras=None):
         quorum_table(eng, model, cfg, known, extras)
         screen_table(eng, model, cfg, known, sample, extras, pair_queries, mask)
         spread_table(eng, model, cfg, known, extras, mask)
+        partner_stat_tables(eng, model, cfg, extras, queries)
     if queries is not None:
         out("partner pairs of %d genes: %s" % (len(queries), "sample %d" % sample if sample is not None
                                                else "mean of %d samples" % B))
         lists = eng.partners_top(queries, cfg["top"], partner_known(model, queries, cfg["exclude"]), sample)
         eng.close()
-        return [[model.id_gene[g], i + 1, float(p), "_".join(str(x) for x in row),
-                 sorted(model.id_gene[int(x)] for x in row)]
-                for g, (scores, ids) in zip(queries, lists) for i, (p, row) in enumerate(zip(scores, ids))]
+        return partner_rows(model.id_gene, queries, lists)
     out("scanning %d genes: %s" % (model.P, "sample %d" % sample if sample is not None
                                    else "mean of %d samples" % B))
     if mask is not None:    # the masked top-N scan; above its cap masked censuses and the masked threshold scan
@@ -1325,6 +1426,16 @@ def write_screen_stat_tsv(samples, arg, rows, stream, what):
         stream.write("%s\t%d\t%r\t%r\t%r\t%r\t%s\t%s\n" % (query, rank, v, mean, lo, hi, key, "_".join(names)))
 
 
+def write_partners_stat_tsv(samples, arg, rows, stream, what):
+    """The --partners-quorum (what = "quorum", arg = the votes) or --partners-disputed (what =
+    "spread", arg = the trim) table: the --gene table with the statistic in the probability's place."""
+    stream.write("# samples\t%d\n" % samples)
+    stream.write("# partners %s\t%d\n" % ("votes" if what == "quorum" else "trim", arg))
+    stream.write("query\trank\t%s\tids\tnames\n" % what)
+    for query, rank, v, key, names in rows:
+        stream.write("%s\t%d\t%r\t%s\t%s\n" % (query, rank, v, key, "_".join(names)))
+
+
 def write_pairs_tsv(rows, stream):
     stream.write("rank\tcount\teligible\tids\tnames\n")
     for i, (count, eligible, key, names) in enumerate(rows):
@@ -1389,6 +1500,12 @@ def main(argv=None, out=print):
     if "screen_disputed" in extras:
         with open(cfg["screen_disputed"], "w", encoding="utf-8") as f:
             write_screen_stat_tsv(*extras["screen_disputed"], f, "spread")
+    if "partners_quorum" in extras:
+        with open(cfg["partners_quorum"], "w", encoding="utf-8") as f:
+            write_partners_stat_tsv(*extras["partners_quorum"], f, "quorum")
+    if "partners_disputed" in extras:
+        with open(cfg["partners_disputed"], "w", encoding="utf-8") as f:
+            write_partners_stat_tsv(*extras["partners_disputed"], f, "spread")
     partners = bool(cfg["genes"] or cfg["all_genes"])
     if cfg["out"]:
         with open(cfg["out"], "w", encoding="utf-8") as f:
