@@ -510,6 +510,62 @@ int mmsbm_scan_quorum_topn_masked(mmsbm_ctx *ctx, const int32_t *order, const in
                                   void *ws, int64_t ws_bytes, double *out_scores, int32_t *out_ids,
                                   int64_t *out_count, void *stream);
 
+/* Pair vote census: the vote scan's counts binned by pair.  For one threshold, M vote levels and
+ * every pair of rank positions x < y, the exact number of the scan's eligible triples that contain
+ * both x and y and that at least levels[m] of the scored slots (EM restarts) score >= threshold: the
+ * predicted, unmeasured interactions of a double-mutant query (x, y) that the restarts agree on,
+ * where mmsbm_pair_census counts on their mean.  order, known, n_known, theta, pr, sample, ws, stream
+ * and eligibility are mmsbm_scan_votes'; mmsbm_pair_votes_masked takes the pair mask behind n_known
+ * under mmsbm_scan_votes_masked's rule (device uint32[P16][MW] in RANK POSITIONS; a triple with a
+ * blocked pair is not eligible; a NULL mask is MMSBM_ERR_INVALID).
+ * The scored slots are the vote scan's: the ns = active-prefix slots for sample = -1, that one slot
+ * (ns = 1) for sample >= 0.  A slot's own score is the vote scan's too, the bits a single-sample call
+ * on that slot forms, and a triple's votes = the number of scored slots whose own score is
+ * >= threshold.
+ * levels_host int32[M] on the HOST: non-decreasing (duplicates are fine), each in [1, ns],
+ * 0 <= M <= mmsbm_pair_votes_max_m() (8).  The levels travel in the kernel's arguments by value (one
+ * byte each): they need no device copy and no LDS table, and the array may be freed on return.
+ * Result (device) out_counts int32[P][P][M] in rank positions, zeroed by the call on `stream`:
+ * out_counts[x][y][m], x < y = the eligible triples that contain positions x and y and have votes
+ * >= levels[m]; entries with x >= y stay 0.  A count is at most P - 2.  M = 0 writes nothing and
+ * returns MMSBM_OK; P < 3: all 0.
+ * Identities, exact:
+ *   - for every m the sum of out_counts[x][y][m] over x < y is three times the sum over
+ *     v >= levels[m] of mmsbm_scan_votes' out_hist[v] at the same threshold, sample and known keys
+ *     (and, for the masked entry, of mmsbm_scan_votes_masked's under the same mask);
+ *   - out_counts[.][.][m] is the scatter to their three pairs of mmsbm_scan_votes' hits at
+ *     (threshold, min_votes = levels[m]); by the quorum scan's identity, the triples that contain the
+ *     pair and have quorum score q_levels[m] >= threshold;
+ *   - with ns = 1, levels = {1} gives mmsbm_pair_census at thresholds = {threshold}, word for word;
+ *   - the masked entry with an all-zero mask returns the unmasked matrix; with a mask, the unmasked
+ *     matrix with the keys of every triple that holds a blocked pair added to `known`; a blocked
+ *     pair's entries are zero.
+ * Everything that crosses a lane or a workgroup is an integer (ballots, popcounts, integer
+ * cross-lane moves and relaxed agent-scope 32-bit atomic adds into out_counts), so the matrix does
+ * not depend on the grid, the batch the slots sit in or the arrival order.
+ * Checked before any device call: a NULL ctx, order, theta or pr, with M > 0 a NULL levels_host or
+ * out_counts, a NaN or infinite threshold, a bad sample, a bad known-key table, a missing, misaligned
+ * or small workspace, a level outside [1, ns] or below the one before it, M < 0, a NULL mask to the
+ * masked entry: MMSBM_ERR_INVALID; M > 8, K outside [1, MMSBM_MAX_K], P > 16384 (the pair census's
+ * cap) or an ensemble whose W tile exceeds the LDS (the census's rule and its 64 KiB):
+ * MMSBM_ERR_UNSUPPORTED.
+ * ws: mmsbm_pair_votes_workspace_bytes(ctx) bytes of device scratch, 16-byte aligned, the caller's;
+ * its size follows the context's shape only.  theta and pr are only read; all launches go to
+ * `stream` and nothing synchronises.  The environment variable MMSBM_PAIR_VOTES_GRID=<workgroups>
+ * overrides the grid (measurement; the matrix does not depend on it).  Needs R >= 2.  Replaces
+ * nothing in the reference. */
+int mmsbm_pair_votes_max_m(void);
+int mmsbm_pair_votes_workspace_bytes(const mmsbm_ctx *ctx, int64_t *bytes);
+int mmsbm_pair_votes(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known, int64_t n_known,
+                     const double *theta, const double *pr, int32_t sample, double threshold,
+                     const int32_t *levels_host, int32_t M, void *ws, int64_t ws_bytes,
+                     int32_t *out_counts, void *stream);
+int mmsbm_pair_votes_masked(mmsbm_ctx *ctx, const int32_t *order, const int64_t *known,
+                            int64_t n_known, const uint32_t *mask, const double *theta,
+                            const double *pr, int32_t sample, double threshold,
+                            const int32_t *levels_host, int32_t M, void *ws, int64_t ws_bytes,
+                            int32_t *out_counts, void *stream);
+
 /* Dispute scan: the exact top N of the scan's eligible triples ranked by the spread of their restart
  * scores: on which novel triples do the restarts disagree most.  order, known, n_known, theta, pr, N,
  * ws, stream, eligibility, the packed key and the total order (score descending; equal scores:

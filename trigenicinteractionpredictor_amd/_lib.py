@@ -93,6 +93,12 @@ SIGNATURES = {
                                          _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mmsbm_scan_quorum_topn_masked": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i32, _c_i32, _c_i32, _vp,
                                                _c_i64, _vp, _vp, _vp, _vp]),
+    "mmsbm_pair_votes_max_m": (_c_int, []),
+    "mmsbm_pair_votes_workspace_bytes": (_c_int, [_vp, ctypes.POINTER(_c_i64)]),
+    "mmsbm_pair_votes": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_i32, _c_dbl, _vp, _c_i32, _vp, _c_i64, _vp,
+                                  _vp]),
+    "mmsbm_pair_votes_masked": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i32, _c_dbl, _vp, _c_i32, _vp,
+                                         _c_i64, _vp, _vp]),
     "mmsbm_scan_spread_max_trim": (_c_int, []),
     "mmsbm_scan_spread_workspace_bytes": (_c_int, [_vp, _c_i32, ctypes.POINTER(_c_i64)]),
     "mmsbm_scan_spread_topn": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_i32, _c_i32, _c_i32, _vp, _c_i64, _vp,

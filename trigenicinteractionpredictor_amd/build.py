@@ -23,8 +23,9 @@ SRC_SCAN_VOTES = os.path.join(PKG, "csrc", "scan_votes.hip")   # vote scan (mmsb
 SRC_SCAN_QUORUM = os.path.join(PKG, "csrc", "scan_quorum.hip")   # quorum scan (mmsbm_scan_quorum_*)
 SRC_SCREEN = os.path.join(PKG, "csrc", "screen.hip")   # query-pair screen scan (mmsbm_screen_*)
 SRC_SCAN_SPREAD = os.path.join(PKG, "csrc", "scan_spread.hip")   # dispute scan (mmsbm_scan_spread_*)
+SRC_PAIR_VOTES = os.path.join(PKG, "csrc", "pair_votes.hip")   # pair vote census (mmsbm_pair_votes_*)
 SRCS = [SRC, SRC_PAIRS, SRC_SCAN, SRC_PARTNERS, SRC_CENSUS, SRC_PAIR_CENSUS, SRC_SCAN_ABOVE, SRC_SCAN_VOTES,
-        SRC_SCAN_QUORUM, SRC_SCREEN, SRC_SCAN_SPREAD]
+        SRC_SCAN_QUORUM, SRC_SCREEN, SRC_SCAN_SPREAD, SRC_PAIR_VOTES]
 INCLUDE = os.path.join(REPO, "include")
 OUT_DIR = os.path.join(PKG, "_build")
 LIB = os.path.join(OUT_DIR, "libmmsbm.so")
@@ -60,6 +61,9 @@ DEPS = {
     SRC_SCAN_SPREAD: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
                       os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(PKG, "csrc", "scan_topn.h"),
                       os.path.join(INCLUDE, "mmsbm.h")],
+    SRC_PAIR_VOTES: [os.path.join(PKG, "csrc", "scan_select.h"), os.path.join(PKG, "csrc", "scan_score.h"),
+                     os.path.join(PKG, "csrc", "scan_host.h"), os.path.join(PKG, "csrc", "scan_sweep.h"),
+                     os.path.join(INCLUDE, "mmsbm.h")],
 }
 
 

@@ -15,7 +15,8 @@ import torch
 
 from . import _lib
 from .scan import (LimitError, bracket_threshold, census_chunks, check_known_keys, check_pair_mask,
-                   check_partner_known, check_screen_known, pair_eligible, rank_of, rank_order, screen_pairs)
+                   check_partner_known, check_screen_known, pair_eligible, rank_of, rank_order, screen_pairs,
+                   vote_level_chunks)
 
 _CURRENT_STREAM = contextlib.nullcontext()     # a scan call without a stream: nothing to make current
 
@@ -225,7 +226,7 @@ class EMEngine:
 
     def scan_workspace(self, family: str, *size_args) -> torch.Tensor:
         """The scratch of one family ("scan", "partners", "census", "pair_census", "scan_above",
-        "scan_votes", "scan_quorum", "scan_spread", "screen"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device.
+        "scan_votes", "scan_quorum", "scan_spread", "screen", "pair_votes"), grown to what mmsbm_<family>_workspace_bytes(ctx, *size_args) asks: uint8 on the device.
         The screen scan's statistics (screen_quorum_*, screen_spread_*) run in the "screen" scratch,
         the partner scan's (partners_quorum_*, partners_spread_*) in the "partners" scratch."""
         nbytes = ctypes.c_int64()
@@ -911,15 +912,20 @@ class EMEngine:
                                          lambda m: (self.P, self.P, m), torch.int32, 2)
         return mat, call[1]
 
+    def _pair_matrix_ids(self, mat, s):
+        """A pair matrix in rank positions, filled for x < y (device int32 [P][P][.]) on its launch
+        stream s -> the symmetric matrix in gene ids."""
+        with torch.cuda.stream(s):
+            rank = torch.from_numpy(rank_of(rank_order(self.P))).to(self.device)
+            mat = mat + mat.transpose(0, 1)             # x < y was filled, the rest is zero
+            return mat[rank][:, rank].contiguous()      # [g1][g2] = [rank[g1]][rank[g2]]
+
     def pair_census_async(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None, mask=None):
         """pair_census without the host copy: -> a device tensor int32 [P][P][len(thresholds)] in
         gene ids, symmetric with a zero diagonal, thresholds in the caller's order.  Nothing
         synchronises."""
         mat, s = self._pair_census_rank(thresholds, known, sample, stream, mask)
-        with torch.cuda.stream(s):
-            rank = torch.from_numpy(rank_of(rank_order(self.P))).to(self.device)
-            mat = mat + mat.transpose(0, 1)             # x < y was filled, the rest is zero
-            return mat[rank][:, rank].contiguous()      # [g1][g2] = [rank[g1]][rank[g2]]
+        return self._pair_matrix_ids(mat, s)
 
     def pair_census(self, thresholds, known: np.ndarray = None, sample: int = None, stream=None, mask=None):
         """The pair census (include/mmsbm.h mmsbm_pair_census): -> int32 [P][P][len(thresholds)] on
@@ -944,6 +950,12 @@ class EMEngine:
         torch.topk on the device over count * P^2 + (P^2 - 1 - key).  mask: as for census; counts and
         eligible then are the masked ones (a blocked pair: 0 and 0)."""
         mat, s = self._pair_census_rank([float(threshold)], known, sample, None, mask)
+        return self._pairs_select(n, mat, s, known, mask)
+
+    def _pairs_select(self, n, mat, s, known, mask):
+        """pairs_top's and pairs_consensus_top's selection: the n best pairs of column 0 of a pair
+        matrix in rank positions (device int32 [P][P][.], filled for x < y) on its launch stream s ->
+        (counts, eligible, ids) as pairs_top documents them."""
         P = self.P
         n = max(0, min(int(n), P * (P - 1) // 2))
         with torch.cuda.stream(s):
@@ -965,6 +977,74 @@ class EMEngine:
         and score >= each threshold.  The row sums of the pair matrix halved: every triple of a gene
         sits in two of the gene's pairs.  mask: as for pair_census."""
         mat = self.pair_census_async(thresholds, known, sample, mask=mask)
+        return (mat.sum(dim=1, dtype=torch.int64) // 2).cpu().numpy()
+
+    # ------------------------------------------------------ pair vote census
+    def _pair_votes_rank(self, threshold, levels, known, sample, stream, mask=None):
+        """The pair vote census in rank positions: -> (device int32 [P][P][len(levels)], filled for
+        x < y only, levels in the caller's order; the launch stream).  One call of mmsbm_pair_votes
+        (with a mask: mmsbm_pair_votes_masked) per mmsbm_pair_votes_max_m() levels."""
+        threshold, _ = self._vote_args(threshold, None, sample)     # ValueError on a NaN or infinite one
+        ns = self.active if sample is None else 1
+        chunks, perm = vote_level_chunks(levels, ns, int(self.lib.mmsbm_pair_votes_max_m()))
+        entry = self.lib.mmsbm_pair_votes if mask is None else self.lib.mmsbm_pair_votes_masked
+        with self._scan_call(known, sample, stream, mask) as (head, s):
+            ws = self.scan_workspace("pair_votes")
+            outs = []
+            for chunk in chunks:    # the levels are read on the host before the call returns
+                out = torch.empty((self.P, self.P, chunk.size), dtype=torch.int32, device=self.device)
+                _lib.check(entry(*head, threshold, _host_ptr(chunk), int(chunk.size), _ptr(ws), ws.numel(),
+                                 _ptr(out) if out.numel() else None, s.cuda_stream))
+                outs.append(out)
+            if len(outs) == 1 and (perm == np.arange(perm.size)).all():
+                return outs[0], s   # one call, levels already ascending: nothing to put back
+            joined = torch.cat(outs, dim=2)     # sorted position i answers the caller's levels[perm[i]]
+            perm_d = torch.from_numpy(perm).to(self.device)
+            return torch.empty_like(joined).index_copy_(2, perm_d, joined), s
+
+    def pair_vote_census_async(self, threshold, levels=None, known: np.ndarray = None, sample: int = None,
+                               stream=None, mask=None):
+        """pair_vote_census without the host copy: -> a device tensor int32 [P][P][len(levels)] in
+        gene ids, symmetric with a zero diagonal, levels in the caller's order.  Nothing
+        synchronises."""
+        mat, s = self._pair_votes_rank(threshold, levels, known, sample, stream, mask)
+        return self._pair_matrix_ids(mat, s)
+
+    def pair_vote_census(self, threshold, levels=None, known: np.ndarray = None, sample: int = None, stream=None,
+                         mask=None):
+        """The pair vote census (include/mmsbm.h mmsbm_pair_votes): -> int32 [P][P][len(levels)] on
+        the host; [g1][g2][i] = the eligible triples (those scan_top ranks: distinct genes, key not
+        in `known`) that contain the genes g1 and g2 and that at least levels[i] of the scored slots
+        score >= threshold: the interactions of the double-mutant query (g1, g2) that the restarts
+        agree on, where pair_census counts on their mean.  Symmetric, zero diagonal.  The scored
+        slots are vote_census's: the ns = active slots for sample = None, that one slot otherwise.
+        levels = None: 1..ns.  The levels may come in any order, with duplicates, in any number or
+        none; one outside [1, ns] and a NaN or infinite threshold raise ValueError.  The sum over
+        g1 < g2 of column i is three times vote_census(threshold)[levels[i]:].sum(), and column i is
+        the scatter to their pairs of consensus(threshold, levels[i])'s triples.  known, sample,
+        mask: as for vote_census (mmsbm_pair_votes_masked): a blocked pair's entries are zero."""
+        mat = self.pair_vote_census_async(threshold, levels, known, sample, stream, mask)
+        if stream is not None:
+            stream.synchronize()
+        return mat.cpu().numpy()
+
+    def pairs_consensus_top(self, n: int, threshold: float, min_votes: int = None, known: np.ndarray = None,
+                            sample: int = None, mask=None):
+        """The n pairs with the most eligible triples that at least min_votes of the scored slots
+        (None: all of them) score >= threshold: -> (counts int64[n'], eligible int64[n'], ids
+        int32[n'][2]) exactly as pairs_top returns and orders them, the counts being
+        pair_vote_census's at levels = [min_votes].  With sample = s it is pairs_top(n, threshold,
+        sample=s).  min_votes outside [1, the scored slots] and a NaN or infinite threshold raise
+        ValueError."""
+        threshold, min_votes = self._vote_args(threshold, min_votes, sample)
+        mat, s = self._pair_votes_rank(threshold, [min_votes], known, sample, None, mask)
+        return self._pairs_select(n, mat, s, known, mask)
+
+    def gene_vote_census(self, threshold, levels=None, known: np.ndarray = None, sample: int = None, mask=None):
+        """-> int64 [P][len(levels)] on the host: the eligible triples that contain each gene and
+        have at least each level of votes at the threshold.  The row sums of pair_vote_census's
+        matrix halved, as gene_census forms its counts.  mask: as for pair_vote_census."""
+        mat = self.pair_vote_census_async(threshold, levels, known, sample, mask=mask)
         return (mat.sum(dim=1, dtype=torch.int64) // 2).cpu().numpy()
 
     # ---------------------------------------------------------- measurement

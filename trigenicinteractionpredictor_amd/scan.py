@@ -69,6 +69,18 @@ different optima, and a mean of 0.5 can be eight restarts at 0.5 or four at 0.95
                            ROWS (default 10,000,000) of them is refused, with the count, before
                            anything is written.  Not with --best: one restart has nothing to vote on.
 
+Two more come from the pair vote census (`EMEngine.pairs_consensus_top`, `EMEngine.gene_vote_census`,
+mmsbm_pair_votes): --pairs and --gene-census counted on the restarts' votes, not on their mean.  A
+pair can top --pairs on triples that half of the restarts reject.
+    --pair-consensus FILE  the --top pairs of genes with the most eligible triples (under --exclude)
+                           that at least --pair-votes M of the -n restarts score >= --pair-threshold
+                           (M in [1, -n]; default -n: the restarts agree).  The header comments give
+                           `# samples`, `# threshold` and `# min votes`; then --pairs' rows: rank,
+                           count, eligible, ids, names.
+    --gene-consensus FILE  one row per gene, in id order: gene, name and its count of eligible triples
+                           with at least v votes at --pair-threshold, for every v from -n down to 1.
+Not with --best: one restart has nothing to vote on.
+
 One more comes from the quorum scan (`EMEngine.quorum_top`, mmsbm_scan_quorum_topn): the consensus
 without a threshold chosen in advance.
     --quorum FILE          the --top eligible triples (under --exclude) ranked by their quorum score:
@@ -108,8 +120,8 @@ that contains a blocked pair is not eligible.
     --block-pairs FILE     two gene names or ids per line, tab or space separated: these pairs are
                            blocked, such as the pairs known to interact digenically.
 They apply to the main table (which then goes through `EMEngine.scan_top_any`: one masked top-N scan
-up to 4096 rows), --census, --network, --screen (with --screen-quorum and --screen-disputed) and
---disputed, and combine by OR.  With
+up to 4096 rows), --census, --network, --screen (with --screen-quorum and --screen-disputed),
+--disputed, --pair-consensus and --gene-consensus, and combine by OR.  With
 --gene / --all-genes, --pairs, --gene-census, --consensus and --quorum, which the driver does not
 restrict yet, they are refused.  --heldout-ranks is not restricted by them.
 
@@ -175,6 +187,7 @@ MAX_TOP = 4096   # mmsbm_scan_max_n() (include/mmsbm.h): the largest N one scan 
 MAX_PARTNER_TOP = 1024   # mmsbm_partners_max_n(): the largest N per query gene
 MAX_CENSUS_M = 1024      # mmsbm_census_max_m(): the most thresholds one census call takes
 MAX_PAIR_CENSUS_M = 8    # mmsbm_pair_census_max_m(): the most thresholds one pair census call takes
+MAX_PAIR_VOTES_M = 8     # mmsbm_pair_votes_max_m(): the most vote levels one pair vote census call takes
 DEFAULT_PAIR_THRESHOLD = 0.5   # --pairs without --pair-threshold
 DEFAULT_NETWORK_THRESHOLD = 0.5    # --network without --network-threshold
 DEFAULT_NETWORK_LIMIT = 10000000   # --network without --network-limit: the most rows it writes
@@ -526,6 +539,27 @@ def census_unsort(parts, perm) -> np.ndarray:
     return out
 
 
+def vote_level_chunks(levels, ns: int, max_m: int = MAX_PAIR_VOTES_M):
+    """The binding's plan for any list of vote levels of the pair vote census -> (chunks, perm), as
+    census_chunks plans thresholds: the levels sorted ascending (stable) and cut into int32 arrays of
+    at most max_m, one mmsbm_pair_votes call each (no level: one empty chunk), and perm with
+    sorted[i] = levels[perm[i]].  levels = None: 1..ns.  ValueError on a level that is no whole
+    number or lies outside [1, ns], the scored slots, in EMEngine._vote_args' words."""
+    ns = int(ns)
+    raw = np.arange(1, ns + 1) if levels is None else np.array(levels).reshape(-1)
+    if raw.size and (raw.dtype.kind not in "iuf" or not (np.isfinite(raw) & (raw == np.floor(raw))).all()):
+        raise ValueError("vote levels must be whole numbers")
+    lv = raw.astype(np.int64)
+    for v in lv:
+        if not 1 <= v <= ns:
+            raise ValueError("min_votes %d outside [1, %d], the scored slots" % (v, ns))
+    perm = np.argsort(lv, kind="stable")
+    ordered = np.ascontiguousarray(lv[perm].astype(np.int32))
+    step = max(int(max_m), 1)
+    chunks = [ordered[i:i + step] for i in range(0, ordered.size, step)] or [ordered]
+    return chunks, perm
+
+
 # ----------------------------------------------------------------------------- threshold scan
 class LimitError(ValueError):
     """A threshold scan would return more rows than its limit; nothing was launched for the list."""
@@ -700,6 +734,9 @@ python -m trigenicinteractionpredictor_amd.scan [-h|--help] [-t|--train=] <train
     [--pairs=] <TSV file: the --top gene pairs with the most eligible triples at or above T>
     [--pair-threshold=] <T, a float in (0, 1]; default 0.5>
     [--gene-census=] <TSV file: per gene, its eligible triples at or above each of --thresholds>
+    [--pair-consensus=] <TSV file: the --top gene pairs with the most eligible triples that >= M restarts score >= --pair-threshold>
+    [--pair-votes=] <M, an integer in [1, restarts]; default: all restarts>
+    [--gene-consensus=] <TSV file: per gene, its eligible triples at every vote level at --pair-threshold>
     [--network=] <TSV file: every eligible triple at or above T, best first>
     [--network-threshold=] <T, a float in (0, 1]; default 0.5>
     [--network-limit=] <the most rows --network may write; default 10000000>
@@ -744,7 +781,8 @@ def parse(argv):
     # (disputed, disputed_trim); --screen-quorum and --screen-disputed add their two each
     # (screen_quorum, screen_votes; screen_disputed, screen_trim) and, being tables over --screen's
     # query pairs, --screen's four; --partners-quorum and --partners-disputed add their two each
-    # (partners_quorum, partners_votes; partners_disputed, partners_trim)
+    # (partners_quorum, partners_votes; partners_disputed, partners_trim); --pair-consensus,
+    # --pair-votes and --gene-consensus add their three (pair_consensus, pair_votes, gene_consensus)
     try:
         opts, _ = getopt.getopt(argv, "ht:e:k:n:i:o:", ["help", "train=", "test=", "k=", "num_samples=",
                                                         "num_iterations=", "seed=", "top=", "exclude=",
@@ -759,7 +797,8 @@ def parse(argv):
                                                         "disputed=", "disputed-trim=", "screen-quorum=",
                                                         "screen-votes=", "screen-disputed=", "screen-trim=",
                                                         "partners-quorum=", "partners-votes=",
-                                                        "partners-disputed=", "partners-trim="])
+                                                        "partners-disputed=", "partners-trim=",
+                                                        "pair-consensus=", "pair-votes=", "gene-consensus="])
     except getopt.GetoptError:
         print("Argument error. Aborting")
         raise cli.ArgError()
@@ -877,6 +916,15 @@ def parse(argv):
                     print("\n\nERROR: --partners-trim should be an integer number >= 0")
                     raise cli.ArgError()
                 cfg["partners_trim"] = int(arg)
+            elif opt == "--pair-consensus":
+                cfg["pair_consensus"] = arg
+            elif opt == "--pair-votes":
+                if not int(arg) >= 1:
+                    print("\n\nERROR: --pair-votes should be an integer number in [1, restarts (-n)]")
+                    raise cli.ArgError()
+                cfg["pair_votes"] = int(arg)
+            elif opt == "--gene-consensus":
+                cfg["gene_consensus"] = arg
             elif opt == "--allow-genes":
                 cfg["allow_genes"] = arg
             elif opt == "--block-pairs":
@@ -1019,6 +1067,18 @@ def parse(argv):
             print("\n\nERROR: --partners-disputed ranks by the spread across the restarts: it does not go with "
                   "--best")
             raise cli.ArgError()
+    if any(key in cfg for key in ("pair_consensus", "pair_votes", "gene_consensus")):
+        cfg.setdefault("pair_consensus", None)
+        cfg.setdefault("pair_votes", cfg["samples"])    # every restart
+        cfg.setdefault("gene_consensus", None)
+        if cfg["pair_votes"] > cfg["samples"]:          # -n may come after --pair-votes
+            print("\n\nERROR: --pair-votes should be an integer number in [1, restarts (-n)]")
+            raise cli.ArgError()
+        for name in ("pair_consensus", "gene_consensus"):
+            if cfg[name] and cfg["best"]:
+                print("\n\nERROR: --%s counts votes across the restarts: it does not go with --best"
+                      % name.replace("_", "-"))
+                raise cli.ArgError()
     if _partner_stat_tables(cfg) and not (cfg["genes"] or cfg["all_genes"]):
         print("\n\nERROR: --partners-quorum / --partners-disputed are tables per query gene: they need --gene or "
               "--all-genes")
@@ -1216,6 +1276,19 @@ def pair_tables(eng, model, cfg, known, sample, extras):
         extras["gene_census"] = (thresholds, [model.id_gene[g] for g in range(model.P)], counts)
 
 
+def pair_vote_tables(eng, model, cfg, known, extras, mask=None):
+    """The driver's --pair-consensus and --gene-consensus tables into `extras` (see run); `mask`: the
+    pair mask of --allow-genes / --block-pairs."""
+    T = cfg.get("pair_threshold")
+    if cfg.get("pair_consensus"):
+        counts, eligible, ids = eng.pairs_consensus_top(cfg["top"], T, cfg["pair_votes"], known, **_masked(mask))
+        extras["pair_consensus"] = (eng.active, T, cfg["pair_votes"], pair_rows(model.id_gene, counts, eligible, ids))
+    if cfg.get("gene_consensus"):
+        levels = list(range(eng.active, 0, -1))
+        counts = eng.gene_vote_census(T, levels, known, **_masked(mask))
+        extras["gene_consensus"] = (eng.active, T, levels, [model.id_gene[g] for g in range(model.P)], counts)
+
+
 def network_table(eng, model, cfg, known, sample, extras, mask=None):
     """The driver's --network table into `extras` (see run); cli.ArgError when it would hold more
     rows than --network-limit."""
@@ -1325,7 +1398,9 @@ def run(cfg, out=print, extras=None):
     "screen_disputed" = (restarts, trim, rows of the same form) for --screen-quorum and
     --screen-disputed, and "partners_quorum" = (restarts, votes, rows [query, rank, quorum score, ids,
     names]) and "partners_disputed" = (restarts, trim, rows of the same form) for --partners-quorum and
-    --partners-disputed."""
+    --partners-disputed, and "pair_consensus" = (restarts, threshold, min votes, rows [count, eligible,
+    ids, names]) and "gene_consensus" = (restarts, threshold, levels, names, counts int64[P][restarts])
+    for --pair-consensus and --gene-consensus."""
     from .model import Model
     model = Model()
     model.get_traintest(cfg["train"], cfg["test"])
@@ -1348,6 +1423,7 @@ def run(cfg, out=print, extras=None):
     if extras is not None:
         census_tables(eng, model, cfg, known, sample, extras, mask)
         pair_tables(eng, model, cfg, known, sample, extras)
+        pair_vote_tables(eng, model, cfg, known, extras, mask)
         network_table(eng, model, cfg, known, sample, extras, mask)
         consensus_table(eng, model, cfg, known, extras)
         quorum_table(eng, model, cfg, known, extras)
@@ -1448,6 +1524,22 @@ def write_gene_census_tsv(thresholds, names, counts, stream):
         stream.write("%d\t%s\t%s\n" % (g, name, "\t".join("%d" % int(c) for c in row)))
 
 
+def write_pair_consensus_tsv(samples, threshold, votes, rows, stream):
+    stream.write("# samples\t%d\n" % samples)
+    stream.write("# threshold\t%r\n" % float(threshold))
+    stream.write("# min votes\t%d\n" % votes)
+    write_pairs_tsv(rows, stream)
+
+
+def write_gene_consensus_tsv(samples, threshold, levels, names, counts, stream):
+    """counts[g][i]: gene g's eligible triples with at least levels[i] votes at the threshold."""
+    stream.write("# samples\t%d\n" % samples)
+    stream.write("# threshold\t%r\n" % float(threshold))
+    stream.write("gene\tname\t" + "\t".join("%d" % int(v) for v in levels) + "\n")
+    for g, (name, row) in enumerate(zip(names, counts)):
+        stream.write("%d\t%s\t%s\n" % (g, name, "\t".join("%d" % int(c) for c in row)))
+
+
 def write_heldout_tsv(rows, stream):
     stream.write("rank\tprobability\tids\treal\n")
     for rank, p, key, real in rows:
@@ -1479,6 +1571,12 @@ def main(argv=None, out=print):
     if "gene_census" in extras:
         with open(cfg["gene_census"], "w", encoding="utf-8") as f:
             write_gene_census_tsv(*extras["gene_census"], f)
+    if "pair_consensus" in extras:
+        with open(cfg["pair_consensus"], "w", encoding="utf-8") as f:
+            write_pair_consensus_tsv(*extras["pair_consensus"], f)
+    if "gene_consensus" in extras:
+        with open(cfg["gene_consensus"], "w", encoding="utf-8") as f:
+            write_gene_consensus_tsv(*extras["gene_consensus"], f)
     if "network" in extras:
         with open(cfg["network"], "w", encoding="utf-8") as f:
             write_tsv(extras["network"], f)
