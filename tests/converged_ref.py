@@ -235,6 +235,42 @@ def check_set_cut(got_scores, got_ids, ref_scores, ref_keys, n, known, P):
     return got_k
 
 
+def clear_cuts_abs(desc, lo, hi):
+    """clear_cuts for spreads: the cut positions n in [lo, hi] of a DESCENDING spread list at which
+    the ABSOLUTE gap between the n-th and the (n + 1)-th spread exceeds census_ref.GAP."""
+    s = np.asarray(desc, dtype=np.float64)
+    assert (s[:-1] >= s[1:]).all()
+    n = np.arange(max(int(lo), 1), min(int(hi), s.size - 1) + 1)
+    return n[(s[n - 1] - s[n]) > census_ref.GAP]
+
+
+def check_set_cut_abs(got_scores, got_ids, d, tol, ref_keys, n, known, P):
+    """check_set_cut for spreads: on the reference alone, n is a clear cut (absolute gap); then the
+    returned key set is the reference's top-n set, every spread is within its own key's absolute
+    tolerance `tol` (spread_ref.atol) of the reference, and the list is sorted by its own bits under
+    the scan's order."""
+    want_s, want_k = scan_ref.top(d, ref_keys, n, known)
+    assert want_s.size == n + 1 and clear_cuts_abs(want_s, n, n).size == 1, ("not a clear cut", n)
+    assert got_ids.dtype == np.int32 and got_scores.dtype == np.float64
+    assert got_ids.shape == (n, 3) and got_scores.shape == (n,)
+    assert np.isfinite(got_scores).all() and (got_scores >= 0).all()
+    got_k = scan_ref.packed(got_ids, P)
+    np.testing.assert_array_equal(got_ids, scan_ref.keys_to_ids(got_k, P))
+    assert np.unique(got_k).size == n, "repeated keys"
+    missing, extra = np.setdiff1d(want_k[:n], got_k), np.setdiff1d(got_k, want_k[:n])
+    assert not missing.size and not extra.size, ("missing", missing[:5], "extra", extra[:5])
+    at = np.searchsorted(ref_keys, got_k)
+    np.testing.assert_array_equal(ref_keys[at], got_k)
+    assert (np.abs(got_scores - d[at]) <= tol[at]).all(), float(np.max(np.abs(got_scores - d[at]) - tol[at]))
+    down = got_scores[:-1] > got_scores[1:]
+    tie = (got_scores[:-1] == got_scores[1:]) & (got_k[:-1] < got_k[1:])
+    bad = np.flatnonzero(~(down | tie))
+    assert not bad.size, ("not in the scan's order at", bad[:5], got_scores[bad[:5]], got_k[bad[:5]])
+    if known is not None and len(known):
+        assert not np.isin(got_k, known).any()
+    return got_k
+
+
 def pick_cuts(desc):
     """The two N of the scan tests: the largest clear cut <= 4096 and the middle one of [64, 512]."""
     big = clear_cuts(desc, 513, 4096)

@@ -10,7 +10,9 @@ import pytest
 
 import census_ref
 import converged_ref as cr
+import partners_converged_ref as pc
 import partners_ref
+import partners_stat_ref
 import pivot_model
 import quorum_ref
 import scan_ref
@@ -247,3 +249,36 @@ def test_every_partner_query_has_clear_cuts():
         assert cuts.size and cuts[0] <= 64, (q, cuts[:3])
         tight += cr.tight_gaps(sc, int(cuts[-1]))
     assert tight > 0
+
+
+@pytest.mark.parametrize("label", pc.SETS)
+def test_every_partner_list_has_both_cuts_and_a_crowded_top(label):
+    """The preconditions of tests/test_gpu_partners_converged.py, on the reference alone, for every
+    gene as a query, both `known` tables, with and without the shared pair mask, and for the ensemble,
+    every slot, every quorum score and the spread: a clear cut in [8, 256] and one in [257, 1024]
+    (partners_converged_ref.plan asserts them, and that enough tops crowd), and the facts the exact
+    check builds on: every query keeps and loses candidates under the mask, and its chunks of at most
+    1024 candidates are disjoint and cover them."""
+    B = len(cr.SCAN_SETS[label])
+    stats = pc.lists_of(B) + (partners_stat_ref.stat_calls(B) if label in pc.STAT_SETS else [])
+    if label in pc.STAT_SETS:
+        assert partners_stat_ref.stat_calls(B) == [("quorum", 1), ("quorum", 2), ("quorum", 3), ("spread", 0)]
+    for known in pc.KNOWN:
+        whole = pc.case(label, known, False)
+        assert whole.P == (60 if label in pc.STAT_SETS else 80) and whole.genes == list(range(whole.P))
+        for masked in (False, True):
+            c = pc.case(label, known, masked)
+            for stat in stats:
+                p = pc.plan(label, known, masked, stat)
+                print("%s %s %s %-14s %2d N, %2d of %d queries crowded" % (label, known, "masked" if masked else "all   ",
+                                                                        stat, len(p.by_n), p.crowded, c.P))
+                assert sum(len(v) for v in p.by_n.values()) == 2 * c.P
+                if label in pc.STAT_SETS and not masked and stat[0] != "slot":
+                    assert p.crowded >= 57
+            for r, w in zip(c.refs, whole.refs):
+                assert w.total == (c.P - 1) * (c.P - 2) // 2 and (known == "fold" or w.tkeys.size == w.total)
+                assert 0 < r.tkeys.size <= w.tkeys.size and (r.tkeys.size < w.tkeys.size) == masked
+                ch = pc.chunks(r)
+                assert all(0 < x.size <= pc.FULL for x in ch) and len(ch) == -(-r.tkeys.size // pc.FULL)
+                assert np.array_equal(np.concatenate(ch), np.sort(r.pkeys)) and np.unique(r.pkeys).size == r.pkeys.size
+            assert max(r.tkeys.size for r in c.refs) > pc.FULL

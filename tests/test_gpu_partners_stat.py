@@ -19,6 +19,7 @@ import sys
 import numpy as np
 import pytest
 
+import partners_converged_ref as pc
 import partners_masked_ref as pm
 import partners_stat_ref as ref
 import quorum_ref
@@ -389,6 +390,116 @@ def test_the_early_exit_does_not_change_a_list():
     for m in (1, 5):
         here = eng.partners_quorum_top(genes, 5, m)
         assert [[s.tobytes().hex(), ids.tobytes().hex()] for s, ids in here] == on["%d 5 4" % m]
+    eng.close()
+
+
+# ------------------------------------------------------------------ 5b. long lists out of many candidates
+@pytest.mark.parametrize("K,P,B,seed", pc.LONG_CASES, ids=lambda v: str(v))
+def test_long_lists_out_of_many_candidates(K, P, B, seed):
+    """N = 300 and 1024 where a query has 4851 (P = 100: 49 workgroups at Q = 1) and 44 551 candidates
+    (P = 300: hundreds of workgroups, several column chunks, two merge levels): the statistic's
+    candidate buffer fills and is cut back to the best N, per workgroup and again in the merge.
+    Against the independent reference by the set rule at clear cuts (asserted on the reference alone;
+    tests/test_partners_stat_host.py shows 300 and 1024 are clear for every query and statistic), the
+    seven queries in one call and each alone, bit-equal.  At P = 100 also exactly: numpy's order
+    statistic and lexsort of the slots' own words of every candidate, from 5 chunks x 5 slots of
+    partners_top under a `known` table.  At P = 300 that would take 44 chunks per slot and is left
+    out."""
+    c = pc.long_case(K, P, B, seed)
+    eng = make_engine(c.theta, c.pr)
+    calls = ref.stat_calls(B)
+    kept = {}
+    for stat in calls:
+        cuts = [pc.long_cuts(r, stat) for r in c.refs]         # the precondition
+        for n in sorted({n for two in cuts for n in two}):
+            idx = [i for i, two in enumerate(cuts) if n in two]
+            got = stat_top(eng, [c.genes[i] for i in idx], n, *stat)
+            for i, lst in zip(idx, got):
+                pc.check_list(lst, c.refs[i], stat, n, P, c.genes[i])
+                (solo,) = stat_top(eng, [c.genes[i]], n, *stat)
+                same_list(solo, lst, ("alone", stat, n, i))
+                kept[stat, n, i] = lst
+    assert len(kept) == len(calls) * 2 * len(c.genes)
+    if P == 100:
+        parts = 5
+        assert all(len(pc.chunks(r)) == parts for r in c.refs)
+        words = []      # [slot][query]
+        for s in range(B):
+            by_part = [eng.partners_top(c.genes, FULL, pc.chunk_known(P, c.positions, c.refs, part), sample=s)
+                       for part in range(parts)]
+            words.append([pc.words_from_chunks([by_part[part][i] for part in range(parts)], r, P)
+                          for i, r in enumerate(c.refs)])
+        for (stat, n, i), lst in kept.items():
+            v = ref.stat(np.stack([words[s][i] for s in range(B)]), *stat)
+            same_list(lst, ref.top_list(v, c.refs[i].tkeys, P, n), (stat, n, i))
+            if stat[0] == "spread":
+                assert not np.signbit(lst[0]).any()
+        # each query confined to ONE workgroup (eight queries per compute unit leave it no more): 4851
+        # candidates go through its buffer of 2 N <= 2048 entries, which fills and is cut back to the best N
+        genes, idx = confined(eng, c.genes)
+        for stat in calls:
+            for n in pc.LONG_NS:
+                for i, lst in zip(idx, stat_top(eng, genes, n, *stat)):
+                    same_list(lst, kept[stat, n, i], ("one workgroup", stat, n, i))
+    eng.close()
+
+
+def confined(eng, genes):
+    """The queries repeated until the call has at least eight per compute unit -> (gene ids, the index
+    of each into `genes`)."""
+    import torch
+    units = torch.cuda.get_device_properties(eng.device).multi_processor_count
+    reps = -(-8 * units // len(genes)) + 1
+    assert 8 * units <= reps * len(genes) <= 65535
+    return list(genes) * reps, list(range(len(genes))) * reps
+
+
+def test_total_ties_under_a_live_bound(monkeypatch):
+    """Every candidate of a query has the same word in a slot (partners_converged_ref.tie_case: exact
+    in any order of the sums), so every statistic ties all 1711 of them and the list is the N smallest
+    triple keys.  A query confined to one workgroup overflows its buffer of 512 entries, which is cut
+    back to N: from then on EVERY value sits exactly on the bound, while tiles still to come hold
+    smaller keys than the bound's (a row block is walked tile by tile, not in key order).  A tile may
+    end early only if no element can reach the bound; an element that equals it still can.  In bits
+    and ids against the numpy reference, with the early exit and without it."""
+    c = pc.tie_case()
+    K, P, B = pc.TIE_SHAPE
+    eng = make_engine(c.theta, c.pr)
+    monkeypatch.delenv("MMSBM_PARTNERS_STAT_EARLY", raising=False)
+    genes, idx = confined(eng, c.genes)
+    for stat in ref.stat_calls(B):
+        for n in pc.TIE_NS:
+            want = [ref.top_list(ref.stat(r.per, *stat), r.tkeys, P, n) for r in c.refs]
+            for q, i in ((c.genes, range(len(c.genes))), (genes, idx)):
+                got = stat_top(eng, q, n, *stat)
+                for j, lst in zip(i, got):
+                    same_list(lst, want[j], (stat, n, j, len(q)))
+                if stat[0] == "quorum":
+                    monkeypatch.setenv("MMSBM_PARTNERS_STAT_EARLY", "0")
+                    again = stat_top(eng, q, n, *stat)
+                    monkeypatch.delenv("MMSBM_PARTNERS_STAT_EARLY")
+                    for a, b in zip(got, again):
+                        same_list(a, b, ("early exit", stat, n))
+    eng.close()
+
+
+def test_the_early_exit_keeps_a_long_list(monkeypatch):
+    """N = 1024 out of 4851 candidates, every m of five slots, the seven queries in one call, one alone
+    and each confined to one workgroup: MMSBM_PARTNERS_STAT_EARLY is read at every call."""
+    K, P, B, seed = pc.LONG_CASES[0]
+    c = pc.long_case(K, P, B, seed)
+    eng = make_engine(c.theta, c.pr)
+    monkeypatch.delenv("MMSBM_PARTNERS_STAT_EARLY", raising=False)
+    for m in range(1, B + 1):
+        for genes in (c.genes, c.genes[1:2], confined(eng, c.genes)[0]):       # the last: the buffer fills, the bound is set
+            on = eng.partners_quorum_top(genes, FULL, m)
+            monkeypatch.setenv("MMSBM_PARTNERS_STAT_EARLY", "0")
+            off = eng.partners_quorum_top(genes, FULL, m)
+            monkeypatch.delenv("MMSBM_PARTNERS_STAT_EARLY")
+            assert len(on) == len(off) == len(genes)
+            for a, b in zip(on, off):
+                assert a[0].size == FULL
+                same_list(a, b, (m, len(genes)))
     eng.close()
 
 

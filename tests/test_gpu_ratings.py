@@ -526,6 +526,253 @@ def test_the_later_scan_families_read_the_rating_1_slice(R, K, B):
     eng.close()
 
 
+# ------------------------------------------------------------------ (f3) the newest families, the masked entries
+NEWEST_N = 16
+NEWEST_QUERIES = (0, 7, 19, 20, 39)     # gene ids: the five queries of (f) at P = 40
+
+
+def newest_samples(B):
+    """The ensemble, and slot 1 of two for the families that take `sample`."""
+    return (None, 1) if B == 2 else (None,)
+
+
+@functools.lru_cache(maxsize=None)
+def newest_case(R, K, B):
+    """The numpy side of (f3), computed once and shared with tests/test_ratings_host.py: every
+    reference answer of the test below over scan_case(R, K, B), and, asserted here on the reference
+    alone before anything is compared, that ratings 0 and 2 in rating 1's place give another answer.
+    -> {"mask", "blocked", "merged", "partners_stat", (sample, masked): {family: reference}}."""
+    import census_ref
+    import converged_ref
+    import pair_census_ref
+    import pair_votes_ref
+    import partners_masked_ref
+    import partners_ref
+    import partners_stat_ref
+    import quorum_ref
+    import scan_ref
+    import spread_ref
+    import votes_ref
+    N = NEWEST_N
+    P, th, pr, mean, keys, wrong_mean = scan_case(R, K, B)
+    assert P == NEWEST_QUERIES[-1] + 1
+    rolled = [np.roll(pr, shift, axis=-1) for shift in (1, -1)]        # ratings 0 and 2 in rating 1's place
+    per = np.stack([scan_ref.ref_scores(th[b], pr[b])[0] for b in range(B)])
+    wrong_per = [np.stack([scan_ref.ref_scores(th[b], w[b])[0] for b in range(B)]) for w in rolled]
+    mask, blocked = converged_ref.random_pair_mask(P)       # scan.pair_mask of 10 % of the pairs, masked_ref.expand
+    _, rank = scan_ref.rank_tables(P)
+    queries = list(NEWEST_QUERIES)
+    merged = partners_masked_ref.merged_known(mask, P, queries)
+    out = {"mask": np.ascontiguousarray(mask), "blocked": blocked, "merged": merged, "queries": queries}
+
+    def differ(a, b):
+        assert not np.array_equal(a, b), "another rating's slice gives the same answer"
+
+    # the partner statistics: the ensemble's only (the entry takes no sample)
+    stats = {}
+    calls = [("quorum", m) for m in sorted({1, B})] + ([("spread", 0)] if B >= 2 else [])
+    for g in queries:
+        q = int(rank[g])
+        slots, tk, pk = partners_stat_ref.ref_slots(th, pr, q)
+        others = [partners_stat_ref.ref_slots(th, w, q)[0] for w in rolled]
+        for tab, keep in (("all", None), ("masked", ~np.isin(pk, partners_masked_ref.blocked_pairs(mask, P, q)))):
+            for what, arg in calls:
+                v = partners_stat_ref.stat(slots, what, arg)
+                ok, gap = partners_stat_ref.gap_ok(v if keep is None else v[keep], what, N)
+                assert ok, (g, what, arg, gap)
+                want = partners_stat_ref.top_list(v, tk, P, N, keep)
+                for o in others:
+                    differ(partners_stat_ref.top_list(partners_stat_ref.stat(o, what, arg), tk, P, N, keep)[1], want[1])
+                bound = partners_stat_ref.top_list(spread_ref.atol(slots, arg), tk, P, N, keep, order_by=v)[0] \
+                    if what == "spread" else None
+                stats[g, tab, what, arg] = want + (bound,)
+    out["partners_stat"], out["stat_calls"] = stats, calls
+
+    for sample in newest_samples(B):
+        scored = slice(0, B) if sample is None else slice(sample, sample + 1)
+        ns = scored.stop - scored.start
+        scores = mean if sample is None else per[sample]
+        wrong = wrong_mean if sample is None else [w[sample] for w in wrong_per]
+        for tab, kn in (("all", None), ("masked", blocked)):
+            e = out[sample, tab] = {"ns": ns}
+            # the dispute scan: at least two scored slots
+            if ns >= 2:
+                want_s, want_k = spread_ref.ref_top(per[scored], keys, 0, N, kn)        # asserts the gaps
+                for w in wrong_per:
+                    differ(scan_ref.top(spread_ref.spread(w[scored], 0), keys, N, kn)[1][:N], want_k[:N])
+                tol = spread_ref.atol(per[scored], 0)[np.searchsorted(keys, want_k[:N])]
+                e["spread"] = (want_s[:N], want_k[:N], tol)
+            # the pair vote census at a threshold clear of every scored slot's scores, the levels descending
+            tv = votes_ref.at_quantile(per[scored], votes_ref.clear_thresholds(per[scored], 41), 0.8)
+            census_ref.assert_clear(per[scored].reshape(-1), [tv])
+            levels = list(range(ns, 0, -1))
+            want = pair_votes_ref.ref_pairs(per[scored], keys, P, tv, levels, known=kn)[1]
+            assert want.any()
+            for w in wrong_per:
+                differ(pair_votes_ref.ref_pairs(w[scored], keys, P, tv, levels, known=kn)[1], want)
+            e["pair_votes"] = (tv, levels, want)
+            if kn is None:
+                continue        # (f) and (f2) hold the other unmasked entries
+            # the masked entries that are also held against the reference
+            top_s, top_k = scan_ref.top(scores, keys, N, kn)
+            scan_ref.assert_gaps(top_s)
+            for o in wrong:
+                differ(scan_ref.top(o, keys, N, kn)[1][:N], top_k[:N])
+            e["scan_top"] = (top_s[:N], top_k[:N])
+            thresholds = census_ref.gap_thresholds(scores, 40)[:8]
+            census_ref.assert_clear(scores, thresholds)
+            counts = census_ref.ref_census(scores, keys, thresholds, kn)
+            pairs = pair_census_ref.ref_pairs(scores, keys, P, thresholds, kn)[1]
+            for o in wrong:
+                differ(census_ref.ref_census(o, keys, thresholds, kn)[0], counts[0])
+                differ(pair_census_ref.ref_pairs(o, keys, P, thresholds, kn)[1], pairs)
+            e["census"] = (thresholds, counts[0], counts[1], pairs)
+            clear = np.sort(census_ref.gap_thresholds(scores, 40))[1:-1]
+            t = float(clear[np.argmin(np.abs(clear - np.quantile(scores, 0.95)))])
+            census_ref.assert_clear(scores, [t])
+            keep = ~np.isin(keys, kn)
+            hit = (scores >= t) & keep
+            assert 0 < hit.sum() < keep.sum()
+            for o in wrong:
+                differ((o >= t) & keep, hit)
+            e["scan_above"] = (t, keys[hit])
+            hist = votes_ref.ref_votes(per[scored], keys, tv, known=kn)[3]
+            for w in wrong_per:
+                differ(votes_ref.ref_votes(w[scored], keys, tv, known=kn)[3], hist)
+            e["votes"] = (tv, hist)
+            q_s, q_k = quorum_ref.ref_top(per[scored], keys, ns, N, kn)         # asserts the gaps
+            for w in wrong_per:
+                differ(scan_ref.top(quorum_ref.quorum(w[scored], ns), keys, N, kn)[1][:N], q_k[:N])
+            e["quorum"] = (ns, q_s[:N], q_k[:N])
+            # the partner scan of the five queries under the mask
+            rows = []
+            for i, g in enumerate(queries):
+                q = int(rank[g])
+                mine = [partners_ref.ref_query(th[b], pr[b], q)[0] for b in range(B)][scored]
+                qmean = scan_ref.prefix_mean(np.stack(mine), ns)
+                known_pairs = merged[1][merged[0][i]:merged[0][i + 1]]
+                want_ids = partners_ref.want_list(th[0], pr[0], g, N, known_pairs, qmean)[1]
+                for w in rolled:
+                    other = [partners_ref.ref_query(th[b], w[b], q)[0] for b in range(B)][scored]
+                    differ(partners_ref.want_list(th[0], pr[0], g, N, known_pairs,
+                                                  scan_ref.prefix_mean(np.stack(other), ns))[1], want_ids)
+                rows.append((known_pairs, qmean))
+            e["partners"] = rows
+    return out
+
+
+@pytest.mark.parametrize("R,K,B", SCAN_PARAMS, ids=["R%d-K%d-B%d" % c for c in SCAN_PARAMS])
+def test_the_newest_families_and_the_masked_entries_read_the_rating_1_slice(R, K, B):
+    """The dispute scan, the pair vote census and the partner statistics, and every *_masked entry, at
+    R = 3 and 8: scan_spread.hip and pair_votes.hip have host entries and prep launches of their own,
+    and each masked entry hands its prep launch the rating count apart from the unmasked one.  The
+    references and their preconditions (another rating's slice gives another answer) are newest_case's.
+    A masked call equals the unmasked call with the key table the mask stands for (the blocked pairs
+    of the query, for the partner scan): exactly for counts, in bits and ids for lists; and one call
+    of every family is also held against the reference, so the identity cannot hold between two calls
+    that are wrong alike."""
+    import partners_ref
+    import scan_ref
+    from test_gpu_scan import check
+    from test_gpu_scan_above import assert_list_properties
+    from trigenicinteractionpredictor_amd import EMEngine
+    N = NEWEST_N
+    c = newest_case(R, K, B)
+    P, th, pr = scan_case(R, K, B)[:3]
+    keys = scan_case(R, K, B)[4]
+    mask, blocked, merged, queries = c["mask"], c["blocked"], c["merged"], c["queries"]
+    eng = EMEngine(K, P, B=B, R=R)
+    eng.upload(th, pr)
+
+    def same(x, y):
+        if isinstance(x, (tuple, list)):
+            assert len(x) == len(y)
+            for u, v in zip(x, y):
+                same(u, v)
+        elif isinstance(x, np.ndarray):
+            assert x.dtype == y.dtype and x.shape == y.shape and scan_ref.bits(x) == scan_ref.bits(y)
+        else:
+            assert x == y
+
+    # the partner statistics of the five queries, unmasked and masked
+    for tab, kw, table in (("all", {}, None), ("masked", {"mask": mask}, merged)):
+        for what, arg in c["stat_calls"]:
+            f = eng.partners_quorum_top if what == "quorum" else eng.partners_spread_top
+            got = f(queries, N, arg, **kw)
+            if table is not None:
+                same(got, f(queries, N, arg, table))
+            for g, (s, ids) in zip(queries, got):
+                want_s, want_ids, bound = c["partners_stat"][g, tab, what, arg]
+                np.testing.assert_array_equal(ids, want_ids, err_msg=str((g, tab, what, arg)))
+                if what == "quorum":
+                    np.testing.assert_allclose(s, want_s, rtol=scan_ref.RTOL, atol=0)
+                else:
+                    assert (np.abs(s - want_s) <= bound).all() and not np.signbit(s).any()
+
+    for sample in newest_samples(B):
+        for tab, kw, table in (("all", {}, None), ("masked", {"mask": mask}, blocked)):
+            e = c[sample, tab]
+            # the dispute scan (the ensemble of two slots: it takes no sample)
+            if "spread" in e:
+                assert sample is None
+                want_s, want_k, tol = e["spread"]
+                s, ids = eng.spread_top(N, 0, **kw)
+                np.testing.assert_array_equal(ids, scan_ref.keys_to_ids(want_k, P))
+                assert (np.abs(s - want_s) <= tol).all() and not np.signbit(s).any()
+                if table is not None:
+                    same(eng.spread_top(N, 0, table), (s, ids))
+            # the pair vote census
+            tv, levels, want = e["pair_votes"]
+            mat = eng.pair_vote_census(tv, levels, sample=sample, **kw)
+            np.testing.assert_array_equal(mat, want)
+            if table is None:
+                continue
+            same(eng.pair_vote_census(tv, levels, table, sample=sample), mat)
+            # the other masked entries: the identity, and the reference
+            want_s, want_k = e["scan_top"]
+            got = eng.scan_top(N, sample=sample, mask=mask)
+            check(got[0], got[1], c_scores(R, K, B, sample), keys, N, P, blocked)
+            np.testing.assert_array_equal(got[1], scan_ref.keys_to_ids(want_k, P))
+            same(eng.scan_top(N, blocked, sample=sample), got)
+            thresholds, counts, total, pairs = e["census"]
+            got = eng.census(thresholds, sample=sample, mask=mask)
+            np.testing.assert_array_equal(got[0], counts)
+            assert got[1] == total
+            same(eng.census(thresholds, blocked, sample=sample), got)
+            got = eng.pair_census(thresholds, sample=sample, mask=mask)
+            np.testing.assert_array_equal(got, pairs)
+            same(eng.pair_census(thresholds, blocked, sample=sample), got)
+            t, hits = e["scan_above"]
+            got = eng.scan_above(t, sample=sample, mask=mask)
+            got_k = assert_list_properties(got[0], got[1], P)
+            np.testing.assert_array_equal(np.sort(got_k), hits)
+            np.testing.assert_allclose(got[0], c_scores(R, K, B, sample)[np.searchsorted(keys, got_k)], rtol=scan_ref.RTOL, atol=0)
+            same(eng.scan_above(t, blocked, sample=sample), got)
+            tv, hist = e["votes"]
+            got = eng.vote_census(tv, sample=sample, mask=mask)
+            np.testing.assert_array_equal(got, hist)
+            same(eng.vote_census(tv, blocked, sample=sample), got)
+            for m in sorted({1, e["ns"]}):
+                same(eng.consensus(tv, m, blocked, sample=sample), eng.consensus(tv, m, sample=sample, mask=mask))
+            m, want_s, want_k = e["quorum"]
+            got = eng.quorum_top(N, m, sample=sample, mask=mask)
+            np.testing.assert_array_equal(got[1], scan_ref.keys_to_ids(want_k, P))
+            np.testing.assert_allclose(got[0], want_s, rtol=scan_ref.RTOL, atol=0)
+            same(eng.quorum_top(N, m, blocked, sample=sample), got)
+            rows = eng.partners_top(queries, N, sample=sample, mask=mask)
+            same(eng.partners_top(queries, N, merged, sample=sample), rows)
+            for g, row, (known_pairs, qmean) in zip(queries, rows, e["partners"]):
+                partners_ref.check_query(row, th[0], pr[0], g, N, known_pairs, qmean)
+    eng.close()
+
+
+def c_scores(R, K, B, sample):
+    """The reference scores the scans of (f3) rank: the ensemble's, or one slot's."""
+    import scan_ref
+    P, th, pr, mean, keys, _ = scan_case(R, K, B)
+    return mean if sample is None else scan_ref.ref_scores(th[sample], pr[sample])[0]
+
+
 # ------------------------------------------------------------------ (g) eps
 EPS = [1e-3, 1e-30]
 

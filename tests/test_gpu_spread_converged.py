@@ -14,7 +14,6 @@ from math import comb
 import numpy as np
 import pytest
 
-import census_ref
 import converged_ref as cr
 import scan_ref
 import spread_ref
@@ -40,13 +39,7 @@ def same(x, y):
         assert u.dtype == v.dtype and u.shape == v.shape and bits(u) == bits(v)
 
 
-def clear_cuts(desc, lo, hi):
-    """The cut positions n in [lo, hi] of a DESCENDING spread list at which a top-n set is
-    determined: the ABSOLUTE gap between the n-th and the (n + 1)-th spread exceeds census_ref.GAP."""
-    s = np.asarray(desc, dtype=np.float64)
-    assert (s[:-1] >= s[1:]).all()
-    n = np.arange(max(int(lo), 1), min(int(hi), s.size - 1) + 1)
-    return n[(s[n - 1] - s[n]) > census_ref.GAP]
+clear_cuts, check_set_cut = cr.clear_cuts_abs, cr.check_set_cut_abs     # the set rule with absolute gaps and bounds
 
 
 def pick_cuts(desc):
@@ -54,31 +47,6 @@ def pick_cuts(desc):
     big, small = clear_cuts(desc, 513, 4096), clear_cuts(desc, 64, 512)
     assert big.size and small.size
     return int(big[-1]), int(small[small.size // 2])
-
-
-def check_set_cut(got_scores, got_ids, d, tol, ref_keys, n, known, P):
-    """converged_ref.check_set_cut for spreads: on the reference alone, n is a clear cut; then the
-    returned key set is the reference's top-n set, every spread is within its own key's absolute
-    tolerance of the reference, and the list is sorted by its own bits under the scan's order."""
-    want_s, want_k = scan_ref.top(d, ref_keys, n, known)
-    assert want_s.size == n + 1 and clear_cuts(want_s, n, n).size == 1, ("not a clear cut", n)
-    assert got_ids.dtype == np.int32 and got_scores.dtype == np.float64
-    assert got_ids.shape == (n, 3) and got_scores.shape == (n,)
-    assert np.isfinite(got_scores).all() and (got_scores >= 0).all()
-    got_k = packed(got_ids, P)
-    np.testing.assert_array_equal(got_ids, scan_ref.keys_to_ids(got_k, P))
-    assert np.unique(got_k).size == n, "repeated keys"
-    missing, extra = np.setdiff1d(want_k[:n], got_k), np.setdiff1d(got_k, want_k[:n])
-    assert not missing.size and not extra.size, ("missing", missing[:5], "extra", extra[:5])
-    at = np.searchsorted(ref_keys, got_k)
-    np.testing.assert_array_equal(ref_keys[at], got_k)
-    assert (np.abs(got_scores - d[at]) <= tol[at]).all(), float(np.max(np.abs(got_scores - d[at]) - tol[at]))
-    down = got_scores[:-1] > got_scores[1:]
-    tie = (got_scores[:-1] == got_scores[1:]) & (got_k[:-1] < got_k[1:])
-    bad = np.flatnonzero(~(down | tie))
-    assert not bad.size, ("not in the scan's order at", bad[:5], got_scores[bad[:5]], got_k[bad[:5]])
-    if known is not None and len(known):
-        assert not np.isin(got_k, known).any()
 
 
 @cases

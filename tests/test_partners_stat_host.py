@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import partners_converged_ref as pc
 import partners_stat_ref as ref
 import scan_ref
 from golden_util import GOLDEN
@@ -225,3 +226,36 @@ def test_reference_gaps(K, P, B, seed):
                 assert ok, (q, what, arg, n, gap)
                 worst[what] = min(worst[what], gap)
     assert worst["quorum"] > ref.QUORUM_GAP and worst["spread"] > ref.SPREAD_GAP
+
+
+@pytest.mark.parametrize("K,P,B,seed", pc.LONG_CASES, ids=lambda v: str(v))
+def test_long_lists_have_clear_cuts(K, P, B, seed):
+    """The precondition of test_gpu_partners_stat.py's long lists, on the reference alone: for every
+    query and every legal statistic N = 1024 is a clear cut (census_ref.GAP, relative for a quorum
+    score, absolute for a spread), and so is 300 or a cut near below it; the candidates exceed what one
+    workgroup's buffer and one slot's list hold."""
+    c = pc.long_case(K, P, B, seed)
+    assert len(c.refs) == 7 and all(r.tkeys.size == r.total == (P - 1) * (P - 2) // 2 > 4 * pc.FULL for r in c.refs)
+    seen = set()
+    for q, r in zip(c.positions, c.refs):
+        for stat in ref.stat_calls(B):
+            cuts = pc.long_cuts(r, stat)
+            assert cuts[1] == pc.FULL
+            seen.add(cuts)
+        assert len(pc.chunks(r)) == -(-r.total // pc.FULL) == (5 if P == 100 else 44)
+    print("K %d P %d B %d: N = %s" % (K, P, B, sorted(seen)))
+
+
+def test_the_tie_case_ties_every_candidate():
+    """test_gpu_partners_stat.py's total tie, on the reference alone: every statistic is one value for
+    every candidate of a query, so its list is the N smallest triple keys; and a workgroup's buffer of
+    512 entries cannot hold a query's candidates."""
+    c = pc.tie_case()
+    K, P, B = pc.TIE_SHAPE
+    for r in c.refs:
+        assert r.tkeys.size == 1711 > 512 >= 2 * max(pc.TIE_NS) and (np.diff(r.tkeys) > 0).all()
+        for what, arg in ref.stat_calls(B):
+            v = ref.stat(r.per, what, arg)
+            assert np.unique(v).size == 1 and v[0] in (0.25, 0.5, 0.75)
+            s, ids = ref.top_list(v, r.tkeys, P, 64)
+            assert scan_ref.packed(ids, P).tolist() == r.tkeys[:64].tolist()

@@ -167,3 +167,36 @@ def test_plan_links_helper_is_unchanged_at_two_ratings_and_valid_above():
     assert a.shape == (400, 5) and ((a[:, 3:] > 0).sum(axis=1) == 2).any()
     b = _links(50, 400, seed=3, R=5, both=0.5)
     assert b.shape == (400, 8) and (b[:, 3:] >= 0).all() and ((b[:, 3:] > 0).sum(axis=1) == 2).any()
+
+
+# ------------------------------------------------------------------ the newest scan families' references
+def newest_params():
+    from test_gpu_ratings import SCAN_PARAMS
+    return SCAN_PARAMS
+
+
+@pytest.mark.parametrize("R,K,B", newest_params(), ids=["R%d-K%d-B%d" % c for c in newest_params()])
+def test_the_newest_families_references_tell_the_rating_slices_apart(R, K, B):
+    """The preconditions of tests/test_gpu_ratings.py (f3), on the reference alone: newest_case asserts,
+    for the dispute scan, the pair vote census, the partner statistics and every masked entry, that
+    ratings 0 and 2 in rating 1's place give another answer, that the lists' gaps determine their
+    order and that the thresholds are clear of every score.  Here also: nothing is empty."""
+    from test_gpu_ratings import NEWEST_N, newest_case, newest_samples
+    c = newest_case(R, K, B)
+    assert 0 < c["blocked"].size and c["mask"].any()
+    for i in range(len(c["queries"])):
+        assert c["merged"][0][i + 1] > c["merged"][0][i]         # every query loses candidates to the mask
+    assert len(c["partners_stat"]) == 5 * 2 * len(c["stat_calls"]) and len(c["stat_calls"]) == (3 if B == 2 else 1)
+    for want_s, want_ids, bound in c["partners_stat"].values():
+        assert want_s.shape == (NEWEST_N,) and want_ids.shape == (NEWEST_N, 3)
+    families = 0
+    for sample in newest_samples(B):
+        for tab in ("all", "masked"):
+            e = c[sample, tab]
+            assert ("spread" in e) == (B == 2 and sample is None)
+            assert e["pair_votes"][2].any() and len(e["pair_votes"][1]) == e["ns"]
+            if tab == "masked":
+                assert {"scan_top", "census", "scan_above", "votes", "quorum", "partners"} <= set(e)
+                assert e["census"][1].max() > 0 and e["votes"][1][1:].sum() > 0
+            families += len(e) - 1
+    print("R %d K %d B %d: %d references, every one differs from ratings 0 and 2" % (R, K, B, families + len(c["partners_stat"])))
