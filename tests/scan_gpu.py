@@ -101,3 +101,37 @@ class Raw:
 
     def intact(self):
         return all(bool((o == SENTINEL).all()) for o in self.outs)
+
+
+# ------------------------------------------------------------------ the planted model's scale cases
+def planted_engine(model, mode="prefix"):
+    """The engine of a planted model (tests/planted_ref.py).  mode "single": a B = 1 engine on
+    slot 0; "prefix": all its slots with an active prefix of planted_ref.SCALE_ACTIVE."""
+    import planted_ref
+    if mode == "single":
+        return engine(model.theta[:1], model.pr[:1])
+    eng = engine(model.theta, model.pr)
+    eng.set_active(planted_ref.SCALE_ACTIVE)
+    return eng
+
+
+def known_of(model, with_known, stats=None):
+    """The scale cases' known keys (planted_ref.scale_known; the 50 best elites under `stats`,
+    default the ensemble mean and slot 0, among them), or None."""
+    import planted_ref as pl
+    if not with_known:
+        return None
+    return pl.scale_known(model, [pl.stat(model, ns=pl.SCALE_ACTIVE), pl.stat(model, sample=0)]
+                          if stats is None else stats)
+
+
+def check_list(got, want, P, atol=None):
+    """A top-N list (scores, ids) against the reference's (scores, packed keys): ids exactly and in
+    order; scores at scan_ref.RTOL (a spread: the absolute bound `atol`)."""
+    (s, ids), (want_s, want_k) = got, want
+    assert s.dtype == np.float64 and ids.dtype == np.int32 and ids.shape == (want_k.size, 3)
+    np.testing.assert_array_equal(ids, scan_ref.keys_to_ids(want_k, P))
+    if atol is None:
+        np.testing.assert_allclose(s, want_s, rtol=scan_ref.RTOL, atol=0)
+    else:
+        np.testing.assert_allclose(s, want_s, rtol=0, atol=atol)
